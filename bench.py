@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- `train.py`-equivalent iterations/s of the SelfRecon SDF-optimisation hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--stage coarse|fine] [--lr LR] [--no-fine] [--no-extra-records] [--scaling weak|strong] [--frames-per-gpu F] [--simulate-world R]
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] [--stage coarse|fine] [--lr LR] [--no-fine] [--no-extra-records] [--scaling weak|strong] [--frames-per-gpu F] [--simulate-world R]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 (a plain `python bench.py --gpus N` with N > 1 and no launcher environment re-executes itself through torch.distributed.run, one rank
 per GPU -- all ranks on device 0 if the box has fewer than N GPUs, which is a functional run, not a measurement)
@@ -33,13 +33,17 @@ At lr 1e-4 the refiner accepts 7-16 % of the rays between two remeshes: Adam's l
 60*mean|f(TmpVs)| keeps the seeds ~3e-3 off the zero set, 60x the acceptance threshold |f| < 5e-5 (profiles/r02_convergence.md).
 The reference's own run does the same: tests/test_trajectory_long_gpu.py holds the product's acceptance rate to the reference's
 (0.09 / 0.25 / 0.15 / 0.26 per 16 iterations of a 64-iteration run at lr 1e-4 with four remeshes).  At the late rate ~75 % converge.
-Other records of the default single-GPU run: `fine_stage`, `strong_scaling_model`
-(configs[2]: 8 frames on one GPU against the workload of one rank of 8), `seg3d_mc_513` (configs[3]), `loose1080` (configs[4]).
 The timed window always contains exactly one remesh when K <= the remesh interval (for K = 20 that over-counts its share:
-1/20 instead of 1/30 or 1/120); its duration is reported, with the properly amortised figure beside.  The K timed steps run
-twice: the first pass carries no instrumentation and gives `value` (refiner on the side stream, concurrent with the template
-branch); the second repeats them with HIP-event pairs around every layer-GEMM launch (roofline leg), the remesh and the refiner,
-with the refiner and the weight-gradient GEMMs on the main stream so that an event interval is one kernel's duration.
+1/20 instead of 1/30 or 1/120).  A plain run sets up, warms up, times the K steps once with no instrumentation (`value`,
+`ms_per_step`; refiner on the side stream, concurrent with the template branch) and prints the line: nothing else.
+`--full` adds everything else this benchmark measures, as separate passes and records:
+  * the K steps again with HIP-event pairs around every layer-GEMM launch (roofline leg), the remesh and the refiner, with the
+    refiner and the weight-gradient GEMMs on the main stream so that an event interval is one kernel's duration (`roofline`,
+    `ms_per_step_instrumented`, the remesh's duration and the properly amortised figure `ms_per_step_remesh_amortised`);
+  * the SDF-MLP forward throughput (`sdf_mlp_gsamples_per_s`) and the CPU oracle's iteration (`cpu_baseline`);
+  * on one GPU: `late_schedule_lr`, `fine_stage`, `strong_scaling_model` (configs[2]: 8 frames on one GPU against the workload of one
+    rank of 8), `seg3d_mc_513` (configs[3]), `loose1080` (configs[4]).
+`--dump-outputs DIR` writes what the last timed step computed, as DIR/<name>.npy (see dump_outputs).
 Camera focal length, principal point and T are learnable as in config.conf:10-15 (quaternion fixed).
 Inputs are synthetic and resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
 """
@@ -111,10 +115,58 @@ def frames_per_rank(stage, args, world):
     return args.frames_per_gpu or STAGES[stage]["frames"]
 
 
-def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_low, gemm_events, timed_lr=None, late_lr=None, frames=None, scene=None):
+DUMP_MAX_BYTES = 64 << 20          # all arrays of one --dump-outputs directory together
+DUMP_MAX_ELEMS = 1 << 21           # a larger array is written as a fixed, seeded sample of this many of its elements
+
+
+def dump_outputs(out_dir, net, ds, loss):
+    """What the last timed step hands its caller, as <out_dir>/<name>.npy (float32, or float64 where the tensor is float64 or integral):
+    `loss` (the total loss), `info.<term>` (the loss terms and ray counts the step records in net.info), `param.<name>` and
+    `grad.<name>` (every learnable tensor after the Adam step, and its gradient of that step), `template.TmpVs` / `template.Tmpfs` (the
+    template mesh after the step's template update).  An array of more than DUMP_MAX_ELEMS elements is flattened and sampled at the
+    same seeded positions in every run.  The scene, its seed and the step's random draws are fixed by the arguments, so two builds run
+    with the same arguments can be compared array by array."""
+    import numpy as np
+    arrays = {"loss": loss}
+    for k, v in net.info.items():
+        for kk, vv in (v.items() if isinstance(v, dict) else [(None, v)]):
+            name = "info." + k + ("" if kk is None else "." + kk)
+            if isinstance(vv, (tuple, list)):
+                vv = [float(x) for x in vv]
+            if isinstance(vv, (torch.Tensor, float, int, list)):
+                arrays[name] = vv
+    named = {id(c): f"conds{i}" for i, c in enumerate(ds.conds)}
+    named.update({id(v): f"camera.{k}" for k, v in ds.camera_params.items()})
+    named.update({id(ds.poses): "poses", id(ds.trans): "trans"})
+    learn = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
+    learn += [("data." + named.get(id(w), str(i)), w) for i, w in enumerate(ds.learnable_weights())]
+    for n, p in learn:
+        arrays["param." + n] = p
+        if p.grad is not None:
+            arrays["grad." + n] = p.grad
+    arrays["template.TmpVs"], arrays["template.Tmpfs"] = net.TmpVs, net.Tmpfs
+    total = 0
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in arrays.items():
+        t = v.detach().cpu() if isinstance(v, torch.Tensor) else torch.tensor(v, dtype=torch.float64)
+        a = t.numpy().astype(np.float64 if t.dtype == torch.float64 or not t.is_floating_point() else np.float32)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs (at {name})")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
+def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_low, gemm_events, timed_lr=None, late_lr=None, frames=None, scene=None,
+              full=True, dump=None):
     """`timed_lr`: Adam learning rate of the timed region (None: the configuration's own 1e-4, no change after the settle phase);
     `late_lr`: additionally time the same workload at this later rate of the schedule (secondary record `late_schedule_lr`);
-    `frames`: frames per rank and step (default: frames_per_rank); `scene`: keyword overrides of build_synthetic_scene (image size, config)."""
+    `frames`: frames per rank and step (default: frames_per_rank); `scene`: keyword overrides of build_synthetic_scene (image size, config);
+    `full`: also the records beside the headline -- `regime_lr_config` and the second, instrumented pass over the K steps (False: the
+    headline pass alone);
+    `dump`: directory for dump_outputs of the last headline step (rank 0)."""
     from selfreconcode_amd import dist as srdist
     from selfreconcode_amd import mlp_engine
     from selfreconcode_amd.synthetic import build_synthetic_scene
@@ -148,6 +200,8 @@ def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_lo
         f = frames_of(it)
         opt.zero_grad(set_to_none=True)
         loss = net(ds.batch(f), RAYS, ratio_of(it), f)
+        if dump:
+            state["loss"] = loss.detach()
         loss.backward()
         net.propagateTmpPsGrad(f, ratio_of(it), overlap=bucket)
         if coll["on"]:
@@ -214,7 +268,7 @@ def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_lo
         ds.attach_rendered_observations(net, ratio_of(0))
     timed_lr = lr0 if timed_lr is None else timed_lr
     if settle > 0:                                                        # phase 2: lr 1e-4
-        if timed_lr == lr0:
+        if timed_lr == lr0 or not full:
             for _ in range(settle):
                 step()
         else:
@@ -241,31 +295,35 @@ def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_lo
     net.remesh_events = net.refiner_events = None
     mlp_engine.PROFILE.reset(enabled=False)
     el, rays, cf = timed(steps, sense=True)
-    # Pass 2 -- the same K steps again with the HIP-event pairs (roofline leg, per-shape table), the remesh and refiner events
-    prof, shapes, rem, refiner_ms, el_i = {}, None, [], None, None
-    net.refiner_stream = "main"          # instrumented pass: one stream of GEMMs, so that an event interval is a kernel's own duration
-    if gemm_events:
-        net.forward_time = (-(steps // 2)) % Rm or Rm
-        net.remesh_events, net.refiner_events = [], []
-        mlp_engine.PROFILE.reset(enabled=True, reserve=1100 * steps)
-        el_i, _, _ = timed(steps)
-        prof = mlp_engine.PROFILE.summary()
-        shapes = mlp_engine.PROFILE.by_shape()
-        mlp_engine.PROFILE.reset(enabled=False)
-        torch.cuda.synchronize()
-        rem = [a.elapsed_time(b) for a, b in net.remesh_events]
-        if net.refiner_events:
-            refiner_ms = sum(a.elapsed_time(b) for a, b in net.refiner_events) / steps
-        net.remesh_events = net.refiner_events = None
-    else:                                                                 # (fine-stage record: remesh / refiner durations only, a handful of events)
-        net.forward_time = (-(steps // 2)) % Rm or Rm
-        net.remesh_events, net.refiner_events = [], []
-        el_i, _, _ = timed(steps)
-        torch.cuda.synchronize()
-        rem = [a.elapsed_time(b) for a, b in net.remesh_events]
-        if net.refiner_events:
-            refiner_ms = sum(a.elapsed_time(b) for a, b in net.refiner_events) / steps
-        net.remesh_events = net.refiner_events = None
+    if dump and rank == 0:
+        dump_outputs(dump, net, ds, state["loss"])
+    # Pass 2 (`full` only) -- the same K steps again with the HIP-event pairs (roofline leg, per-shape table), the remesh and refiner events
+    prof, shapes, rem, refiner_ms, el_i = {}, None, None, None, None
+    if full:
+        rem = []
+        net.refiner_stream = "main"          # instrumented pass: one stream of GEMMs, so that an event interval is a kernel's own duration
+        if gemm_events:
+            net.forward_time = (-(steps // 2)) % Rm or Rm
+            net.remesh_events, net.refiner_events = [], []
+            mlp_engine.PROFILE.reset(enabled=True, reserve=1100 * steps)
+            el_i, _, _ = timed(steps)
+            prof = mlp_engine.PROFILE.summary()
+            shapes = mlp_engine.PROFILE.by_shape()
+            mlp_engine.PROFILE.reset(enabled=False)
+            torch.cuda.synchronize()
+            rem = [a.elapsed_time(b) for a, b in net.remesh_events]
+            if net.refiner_events:
+                refiner_ms = sum(a.elapsed_time(b) for a, b in net.refiner_events) / steps
+            net.remesh_events = net.refiner_events = None
+        else:                                                                 # (fine-stage record: remesh / refiner durations only, a handful of events)
+            net.forward_time = (-(steps // 2)) % Rm or Rm
+            net.remesh_events, net.refiner_events = [], []
+            el_i, _, _ = timed(steps)
+            torch.cuda.synchronize()
+            rem = [a.elapsed_time(b) for a, b in net.remesh_events]
+            if net.refiner_events:
+                refiner_ms = sum(a.elapsed_time(b) for a, b in net.refiner_events) / steps
+            net.remesh_events = net.refiner_events = None
     if late_lr is not None:          # the same workload at a later rate of the MultiStepLR schedule (more rays converge: a heavier colour / normal branch)
         net.refiner_stream = args.refiner_stream
         for g in opt.param_groups:
@@ -283,7 +341,7 @@ def run_stage(stage, args, rank, world, device, steps, warmup, settle, settle_lo
     ms = el / steps * 1e3
     rem_each = sum(rem) / len(rem) if rem else None
     rec.update({"ms_per_step": round(ms, 3), "elapsed": el, "ms_per_step_instrumented": None if el_i is None else round(el_i / steps * 1e3, 3), "rays_per_iter": round(rays, 1), "rays_converged_frac": round(cf, 4),
-                "template_vertices": int(net.TmpVs.shape[0]), "remesh": {"in_window": len(rem), "ms_each": None if rem_each is None else round(rem_each, 3),
+                "template_vertices": int(net.TmpVs.shape[0]), "remesh": {"in_window": None if rem is None else len(rem), "ms_each": None if rem_each is None else round(rem_each, 3),
                                                                         "interval": Rm},
                 "ms_per_step_remesh_amortised": None if rem_each is None else round((el * 1e3 - rem_each) / steps + rem_each / Rm, 3),
                 "refiner_ms_per_step": None if refiner_ms is None else round(refiner_ms, 3),
@@ -413,7 +471,12 @@ def main():
                     "reference does).  The headline workload (3 x 2048 rays) is above the default and unaffected; one frame per rank (configs[2]) is below it")
     ap.add_argument("--torch-adam", action="store_true", help="torch.optim.Adam (multi-tensor launches) instead of the one-launch FusedAdam")
     ap.add_argument("--no-gemm-events", action="store_true", help="skip the HIP-event pairs around the layer GEMMs (roofline leg) to see their cost")
-    ap.add_argument("--shape-log", default=None, help="write the per-(M,N,K) GEMM launch table (events) to this JSON file")
+    ap.add_argument("--shape-log", default=None, help="write the per-(M,N,K) GEMM launch table (events) to this JSON file (--full)")
+    ap.add_argument("--full", action="store_true", help="besides the headline pass, run everything else this benchmark measures: the instrumented second pass "
+                    "(roofline, remesh / refiner durations), the SDF-MLP throughput, the CPU baseline and, on one GPU, the late-rate, fine-stage, "
+                    "strong-scaling-model, configs[3] and configs[4] records (default: the headline pass alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (loss and its terms, parameters and "
+                    "gradients after the step, template mesh) to DIR/<name>.npy, float32 / float64, at most 64 MB")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -435,24 +498,26 @@ def main():
     # The learning rate of a record is the one config.conf runs that stage at: the coarse stage is epochs 0-5, all at 1e-4
     # (config.conf:16-34); the fine stage starts at epoch 12 and spends epochs 80-129 at 1e-4 * 0.333^3 (the MultiStepLR milestones).
     lr_of = lambda stage: args.lr if args.lr is not None else (None if stage == "coarse" else args.late_lr)
-    extras = world == 1 and not args.no_extra_records and not args.simulate_world and args.scaling == "weak" and not args.frames_per_gpu
+    extras = args.full and world == 1 and not args.no_extra_records and not args.simulate_world and args.scaling == "weak" and not args.frames_per_gpu
     main_rec = run_stage(args.stage, args, rank, world, device, args.steps, args.warmup, args.settle, args.settle_low, not args.no_gemm_events,
-                         timed_lr=lr_of(args.stage), late_lr=args.late_lr if (extras and args.stage == "coarse" and args.lr is None) else None)
+                         timed_lr=lr_of(args.stage), late_lr=args.late_lr if (extras and args.stage == "coarse" and args.lr is None) else None,
+                         full=args.full, dump=args.dump_outputs)
     net = main_rec.pop("net")
     prof, shapes = main_rec.pop("prof"), main_rec.pop("shapes")
     elapsed = main_rec.pop("elapsed")
     lr_timed = main_rec["lr_timed"]
 
-    # secondary headline: SDF MLP forward throughput (no-grad, 393216 samples per call)
-    sdf_gs = 0.0
-    with torch.no_grad():
-        x = (torch.rand(393216 if not args.no_sdf_throughput else 0, 3, device=device) - 0.5) * 1.6
-        for _ in range(2):
-            net.sdf(x, 1.0)
-        torch.cuda.synchronize(); s = time.perf_counter()
-        for _ in range(5):
-            net.sdf(x, 1.0)
-        torch.cuda.synchronize(); sdf_gs = 5 * x.shape[0] / (time.perf_counter() - s) / 1e9 if x.shape[0] else 0.0
+    # secondary headline (--full): SDF MLP forward throughput (no-grad, 393216 samples per call)
+    sdf_gs = None
+    if args.full:
+        with torch.no_grad():
+            x = (torch.rand(393216 if not args.no_sdf_throughput else 0, 3, device=device) - 0.5) * 1.6
+            for _ in range(2):
+                net.sdf(x, 1.0)
+            torch.cuda.synchronize(); s = time.perf_counter()
+            for _ in range(5):
+                net.sdf(x, 1.0)
+            torch.cuda.synchronize(); sdf_gs = 5 * x.shape[0] / (time.perf_counter() - s) / 1e9 if x.shape[0] else 0.0
     V = main_rec["template_vertices"]
     hbm = {"peak_allocated_gb": round(torch.cuda.max_memory_allocated(device) / 2 ** 30, 2), "reserved_gb": round(torch.cuda.memory_reserved(device) / 2 ** 30, 2),
            "device_allocations": torch.cuda.memory_stats(device).get("num_device_alloc", None)}
@@ -466,7 +531,7 @@ def main():
         return r
 
     fine_rec = None
-    if world == 1 and args.stage == "coarse" and not args.no_fine and args.scaling == "weak" and not args.frames_per_gpu and not args.simulate_world:
+    if args.full and world == 1 and args.stage == "coarse" and not args.no_fine and args.scaling == "weak" and not args.frames_per_gpu and not args.simulate_world:
         fine_rec = strip(run_stage("fine", args, rank, world, device, args.steps, args.warmup, max(args.settle // 2, 0), args.settle_low, False, timed_lr=lr_of("fine")))
         fine_rec["workload"] = "fine stage (1 frame x 6144 rays, 321x417x225 grid, remesh every 120: config.conf:39-48,113) at the MultiStepLR rate of epochs 80-129"
 
@@ -538,7 +603,7 @@ def main():
         "metric": f"train.py-equivalent iterations/sec (540x540, {RAYS} rays/frame x {FR} frame{'s' if FR > 1 else ''} per GPU; {args.stage} stage at Adam lr {lr_timed:.3g})",
         "value": round(args.steps * world * FR / FR_REF / elapsed, 4), "unit": "iterations/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": main_rec["ms_per_step"],
-        "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "higher_is_better": True, "full": args.full, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "methodology": {"version": 2, "since": "round 4",
                         "note": "version 2 times the coarse stage at the learning rate config.conf runs it at (1e-4: 7-22 % of the rays converge); rounds 2-3 (version 1) "
                                 "timed it at the late MultiStepLR rate (~75 % converge: a heavier colour / normal branch) -- compare BENCH_r02 / r03 with "
@@ -577,7 +642,7 @@ def main():
         "strong_scaling_model": strong_rec,
         "seg3d_mc_513": seg_rec,
         "loose1080": loose_rec,
-        "sdf_mlp_gsamples_per_s": round(sdf_gs, 5),
+        "sdf_mlp_gsamples_per_s": None if sdf_gs is None else round(sdf_gs, 5),
         "hbm": hbm,
         "roofline": {"bound": "mfma", "kernel": "gemm_nt_kernel / mlp_layer_pair_kernel (fp32 MFMA 32x32x2 layer GEMM tile code with fused epilogue; the layer-pair kernel runs one layer of the refiner's two networks per launch on the device-side live-ray count), EVERY launch of the timed region with >= 128 rows and > 32 columns and every chain launch; "
                                                 "launches issued while two streams feed the GPU are included (their event intervals can contain the other stream's kernels, "
@@ -606,10 +671,12 @@ def main():
                 f"passes (profiles/{name}; algorithmic bytes of the same launches: "
                 f"{round(t.get('gemm_nt_wide', {}).get('algorithmic_bytes_per_launch', 0))})")
             break
+    if not args.full:
+        out["roofline"] = None                                # (from the instrumented pass, which only --full runs)
     if shapes is not None and args.shape_log:
         with open(args.shape_log, "w") as fh:
             json.dump(shapes, fh, indent=1)
-    if world == 1 and not args.no_cpu_baseline and not args.simulate_world:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.simulate_world:
         from selfreconcode_amd import affinity
         affinity.restore()                                    # the CPU leg gets the machine the process was started with
         out["cpu_baseline"] = cpu_baseline_record(args, device)

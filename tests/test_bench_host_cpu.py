@@ -40,11 +40,52 @@ def test_bench_command_line_contract():
     finishes within minutes."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--frames-per-gpu", "--global-frames", "--no-cpu-baseline", "--simulate-world"):
+    for flag in ("--gpus", "--steps", "--warmup", "--scaling", "--frames-per-gpu", "--global-frames", "--no-cpu-baseline", "--simulate-world",
+                 "--full", "--dump-outputs"):
         assert flag in r.stdout, flag
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert 'add_argument("--gpus", type=int, default=1)' in src
     assert 'add_argument("--steps", type=int, default=30)' in src and 'add_argument("--warmup", type=int, default=5)' in src
+
+
+def test_dump_outputs_names_dtypes_and_sampling(tmp_path):
+    """`--dump-outputs`: one .npy per array in float32 / float64, the loss terms of net.info, parameters and gradients by name, and an
+    array above the element cap written as the same seeded sample every time."""
+    import numpy as np
+    bench = importlib.import_module("bench")
+
+    class Net(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.lin = torch.nn.Linear(3, 2)
+            self.info = {"rayInfo": (7, torch.tensor(3)), "color_loss": torch.tensor(0.5), "pc_loss": {"mask_loss": torch.tensor(0.25)}, "remesh": None}
+            self.TmpVs = torch.arange((bench.DUMP_MAX_ELEMS // 3 + 2) * 3, dtype=torch.float32).view(-1, 3)
+            self.Tmpfs = torch.tensor([[0, 1, 2]])
+
+    class Data:
+        conds = [torch.ones(4, 2, requires_grad=True)]
+        camera_params = {"focal_length": torch.ones(2, dtype=torch.float64, requires_grad=True)}
+        poses, trans = torch.zeros(4, 3, requires_grad=True), torch.zeros(4, 3)
+
+        def learnable_weights(self):
+            return self.conds + list(self.camera_params.values()) + [self.poses]
+
+    net, ds = Net(), Data()
+    net.lin.weight.grad = torch.full((2, 3), 2.0)
+    names = bench.dump_outputs(str(tmp_path / "a"), net, ds, torch.tensor(1.5))
+    bench.dump_outputs(str(tmp_path / "b"), net, ds, torch.tensor(1.5))
+    for n in ("loss", "info.rayInfo", "info.color_loss", "info.pc_loss.mask_loss", "param.lin.weight", "grad.lin.weight", "param.data.conds0",
+              "param.data.camera.focal_length", "param.data.poses", "template.TmpVs", "template.Tmpfs"):
+        assert n in names and (tmp_path / "a" / (n + ".npy")).is_file(), n
+    assert not (tmp_path / "a" / "info.remesh.npy").exists()
+    ld = lambda d, n: np.load(str(tmp_path / d / (n + ".npy")))
+    assert ld("a", "loss").dtype == np.float32 and float(ld("a", "loss")) == 1.5
+    assert ld("a", "info.rayInfo").dtype == np.float64 and ld("a", "info.rayInfo").tolist() == [7.0, 3.0]
+    assert ld("a", "param.data.camera.focal_length").dtype == np.float64 and ld("a", "template.Tmpfs").dtype == np.float64
+    assert (ld("a", "grad.lin.weight") == 2.0).all() and ld("a", "param.lin.weight").shape == (2, 3)
+    v = ld("a", "template.TmpVs")
+    assert v.shape == (bench.DUMP_MAX_ELEMS,) and (np.diff(v) > 0).all() and (v == ld("b", "template.TmpVs")).all()
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES + 4096 * len(names)
 
 
 def test_fused_adam_refuses_what_it_does_not_implement():

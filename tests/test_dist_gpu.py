@@ -16,7 +16,7 @@ def test_two_ranks_on_one_gpu_run_the_real_step():
     env = dict(os.environ, SR_ALL_RANKS_ON_DEVICE0="1", SR_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--settle", "3", "--settle-low", "1", "--noise-observations",
-           "--no-cpu-baseline", "--no-gemm-events"]
+           "--no-cpu-baseline", "--no-gemm-events", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
