@@ -17,6 +17,7 @@ Deliberate differences (all documented in DESIGN.md):
 import contextlib
 import os
 import time
+from collections import namedtuple
 import numpy as np
 import torch
 import torch.nn as nn
@@ -60,17 +61,41 @@ FUSED_SELECTION = os.environ.get('SR_FUSED_SELECTION', '1') != '0'
 _SIDE_STREAMS = {}
 
 
-def scatter_mean(vals, index, dim_size):
-    """torch_scatter.scatter(reduce='mean', dim_size=N) as used at network.py:617,637 (empty bins give 0)."""
-    s = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, vals)
-    c = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, torch.ones_like(vals))
+def scatter_mean(vals, index, dim_size, valid=None):
+    """torch_scatter.scatter(reduce='mean', dim_size=N) as used at network.py:617,637 (empty bins give 0).  `valid`: only the rows
+    where it is true count -- masked sums over masked counts, without materialising the subset (no host sync)."""
+    if valid is None:
+        s = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, vals)
+        c = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, torch.ones_like(vals))
+    else:
+        zero = torch.zeros((), dtype=vals.dtype, device=vals.device)
+        s = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, torch.where(valid, vals, zero))
+        c = torch.zeros(dim_size, dtype=vals.dtype, device=vals.device).index_add(0, index, valid.to(vals.dtype))
     return s / c.clamp(min=1)
+
+
+def _random(rand, key, draw, n, *shape, device):
+    """rand[key][:n] when the caller injected it, else draw(n, *shape).  A draw advances the Philox offset: forward() draws in the order
+    ray_select, vert_select, vert_select2, eik_local, eik_global, regu_local, and an uninjected run depends on that order."""
+    return rand[key][:n] if key in rand else draw(n, *shape, device=device)
+
+
+def _vertex_subset(rand, key, V, device):
+    """Bernoulli subset of the V template vertices of mean size 4096 (utils.py:74-84 via network.py:543,565), as a boolean mask."""
+    return _random(rand, key, torch.rand, V, device=device) < 4096. / float(V)
 
 
 def cross_matrix(v):
     """[v]_x for a batch of vectors (network.py:757-764)."""
     z = torch.zeros_like(v[:, 0])
     return torch.stack([z, -v[:, 2], v[:, 1], v[:, 2], z, -v[:, 0], -v[:, 1], v[:, 0], z], dim=1).view(-1, 3, 3)
+
+
+# The selected rays, made on the side stream (then `selected` is recorded there); the vertex subsets if the fused selection made them.
+_Selection = namedtuple('_Selection', 'batch_inds row_inds col_inds seeds rays pixels eik_idx regu_idx selected')
+# An open ray branch (EAGER_RAY_BRANCH), closed by _finish_ray_branch: its stream, the caller's, the (real tensor, stand-in) pairs, its
+# camera object and stand-ins (poses, trans, d_cond), and the event recorded on its stream after the inner backward.
+_RayBranch = namedtuple('_RayBranch', 'stream main pairs cameras frame bwd_done')
 
 
 class OptimNetwork(nn.Module):
@@ -91,13 +116,12 @@ class OptimNetwork(nn.Module):
         self.remesh_time = 0.
         self.point_radius = 0.006             # train.coarse.point_render.radius (config.conf:30)
         self.sdfShrinkRadius = 0.0
-        self.seed_mode = "mesh"               # "mesh": triangle rasteriser + FindSurfacePs; "vertex": vertex z-buffer stand-in
         self.TmpPs = None
         self.info = {}
         self.dataset = None
         self.dctnull = None
         self._ray_ctx = None                  # an open ray branch (EAGER_RAY_BRANCH): closed by propagateTmpPsGrad / the next forward
-        self.masked_ray_branch_below = 0      # > 0: with at most this many selected rays the ray branch runs on all of them, masked (see forward())
+        self.masked_ray_branch_below = 0      # > 0: with at most this many selected rays the ray branch runs on all of them, masked (see _ray_branch)
         self.ray_valid = None
         self.next_conf = None                 # set by utils.checkpoint.set_hierarchical_config: the stage switch takes effect at the
         self.next_train_conf = None           # next scheduled remesh (update_hierarchical_config, network.py:172-205,464)
@@ -332,25 +356,6 @@ class OptimNetwork(nn.Module):
             st[key] = torch.cuda.Stream(device=device, priority=-1)
         return st[key]
 
-    def _seed_rays(self, defTmpVs, cameras, H, W, canonical=None):
-        """Stand-in for MeshRasterizer + FindSurfacePs: nearest projected template vertex per pixel (packed
-        depth|index min-reduction); the seed is that vertex's canonical position."""
-        N, V = defTmpVs.shape[0], defTmpVs.shape[1]
-        pix, z = cameras.project(defTmpVs.reshape(-1, 3))
-        col = torch.floor(pix[:, 0] + 0.5).long(); row = torch.floor(pix[:, 1] + 0.5).long()
-        ok = (z > 0) & (col >= 0) & (col < W) & (row >= 0) & (row < H)
-        b = torch.arange(N, device=pix.device).repeat_interleave(V)
-        vid = torch.arange(V, device=pix.device).repeat(N)
-        key = (z.float().view(torch.int32).long() << 32) | vid
-        big = torch.full((N * H * W,), torch.iinfo(torch.int64).max, dtype=torch.int64, device=pix.device)
-        lin = (b * H + row) * W + col
-        big.scatter_reduce_(0, lin[ok], key[ok], reduce='amin', include_self=True)
-        hit = big != torch.iinfo(torch.int64).max
-        idx = hit.nonzero(as_tuple=False).view(-1)
-        batch_inds = idx // (H * W); row_inds = (idx // W) % H; col_inds = idx % W
-        seeds = (self.TmpVs.detach() if canonical is None else canonical)[big[idx] & 0xFFFFFFFF]
-        return batch_inds, row_inds, col_inds, seeds
-
     def _silhouette(self, defTmpVs, cameras, H, W, radius):
         """pcRender of the reference (network.py:178-190, 497): PointsRasterizer(radius, points_per_pixel=50) + AlphaCompositor
         over the deformed template vertices with one all-ones feature -> masks [N,H,W]."""
@@ -375,7 +380,8 @@ class OptimNetwork(nn.Module):
         regu_local; each may be longer than needed, the head is used) so that a parity test feeds both sides the same numbers;
         `rand['refined'] = (points, flags)` replaces the refiner's output for the selected rays (its |f| < 5e-5 acceptance flips
         on single ulps: tests compare the refiner separately and everything after it on identical ray sets);
-        `debug` (extension): a dict that receives the selected rays, their seeds and the refiner's output."""
+        `debug` (extension): a dict that receives the selected rays, their seeds and the refiner's output.
+        The phases below issue in program order; each one's docstring names the stream it issues on and what it waits for or records."""
         device = frame_ids.device
         rand = rand or {}
         gtCs = datas['img'].to(device)
@@ -396,23 +402,64 @@ class OptimNetwork(nn.Module):
             self.angThred = cameras.angThreshold(0.5)
         self.info = {}
         self._finish_ray_branch()                    # (a branch of the previous call that no propagateTmpPsGrad closed)
-        if self.TmpVs is None or self.Tmpfs is None or self.forward_time % self.remesh_intersect == 0:
-            ev = getattr(self, 'remesh_events', None)
-            if ev is not None:                       # bench.py: duration of the remesh inside the timed window
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            self.update_hierarchical_config(device)          # a pending stage switch takes effect with this remesh (network.py:464)
-            self.TmpVs, self.Tmpfs = self.discretizeSDF(ratio, None, -self.sdfShrinkRadius)
-            if ev is not None:
-                e1.record(); ev.append((e0, e1))
-            if self.TmpVs.shape[0] == 0:
-                raise AssertionError('tmp sdf vanished...')
-            srdist.assert_same_across_ranks(self.TmpVs.shape[0], "template vertex count after the remesh")
-            self.remesh_time = 1. + np.floor(self.remesh_time)
-            self.TmpVs.requires_grad = True
-            self.TmpOptimizer = torch.optim.SGD([self.TmpVs], lr=0.05, momentum=0.9)
-        TmpVnum = self.TmpVs.shape[0]
-        poses, trans, d_cond, rendcond = self.dataset.get_grad_parameters(frame_ids, device)
+        self._remesh_if_due(ratio, device)
+        main = torch.cuda.current_stream(device)
+        side = self._side_stream(device)
+        defTmpVs, seedVs, fork, total_loss = self._template_branch(main, gtMs, cameras_sil, frame_ids, N, H, W, ratio, debug)
+
+        use_regu = 'def_regu' in self.conf and self.conf.get_float('def_regu.weight') > 0.
+        sample_pix = self.conf.get_int('sample_pix_num') if 'sample_pix_num' in self.conf else sample_pix
+        sel = self._select_rays(side, fork, datas, gtMs, cameras, defTmpVs, seedVs, H, W, sample_pix * N, use_regu, rand, debug)
+        self._mark('rays selected')
+        on_side = getattr(self, 'refiner_stream', 'side') == 'side'
+        points, check, refined = self._refine(side if on_side else main, main, sel, cameras, frame_ids, ratio, rand)
+        self._mark('refiner issued')
+        eik_idx, regu_idx = sel.eik_idx, sel.regu_idx
+        if eik_idx is None:                          # (sequential selection: the vertex subsets are drawn after the refiner is issued)
+            aux = self._side_stream(device, 1)
+            eik_idx, regu_idx = self._vertex_subsets(aux, fork, use_regu, rand, device)
+        self._debug_delay('main_before_join')
+        main.wait_stream(aux) if sel.eik_idx is None else main.wait_event(sel.selected)     # (fused: the lists came with the rays)
+        for t in (eik_idx, regu_idx):
+            if t is not None:
+                t.record_stream(main)
+        frame = self.dataset.get_grad_parameters(frame_ids, device)     # (the inner backward freed the first set's graph)
+        total_loss = self._sampled_terms(total_loss, main, side, sel, points, check, eik_idx, regu_idx, frame, frame_ids, N, ratio, rand, debug)
+        self._mark('dct issued')
+        total_loss = self._ray_branch(total_loss, main, side, on_side, refined, sel, points, check, datas, gtCs, cameras, cam_learn, frame, frame_ids, H, W, ratio)
+        # guard of the eager contract (docstring (a)): remember one gradient tensor the inner backwards of this call deposited
+        lw = getattr(self.dataset, 'learnable_weights', None)
+        armed = torch.is_grad_enabled() and (EAGER_TEMPLATE_TERM or EAGER_RAY_BRANCH) and lw is not None
+        self._eager_guard = next(((leaf, leaf.grad) for leaf in lw() if leaf.grad is not None), None) if armed else None
+        self.remesh_time = np.floor(self.remesh_time) + float(self.forward_time % self.remesh_intersect) / float(self.remesh_intersect)
+        self.info['remesh'] = self.remesh_time
+        self.forward_time += 1
+        self._mark('forward issued')
+        return total_loss
+
+    def _remesh_if_due(self, ratio, device):
+        """On the main stream, every `remesh_intersect` calls: a pending stage switch, marching cubes (`remesh_events`), a new template."""
+        if self.TmpVs is not None and self.Tmpfs is not None and self.forward_time % self.remesh_intersect != 0:
+            return
+        ev = getattr(self, 'remesh_events', None)
+        if ev is not None:                       # bench.py: duration of the remesh inside the timed window
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        self.update_hierarchical_config(device)          # a pending stage switch takes effect with this remesh (network.py:464)
+        self.TmpVs, self.Tmpfs = self.discretizeSDF(ratio, None, -self.sdfShrinkRadius)
+        if ev is not None:
+            e1.record(); ev.append((e0, e1))
+        if self.TmpVs.shape[0] == 0:
+            raise AssertionError('tmp sdf vanished...')
+        srdist.assert_same_across_ranks(self.TmpVs.shape[0], "template vertex count after the remesh")
+        self.remesh_time = 1. + np.floor(self.remesh_time)
+        self.TmpVs.requires_grad = True
+        self.TmpOptimizer = torch.optim.SGD([self.TmpVs], lr=0.05, momentum=0.9)
+
+    def _template_branch(self, main, gtMs, cameras_sil, frame_ids, N, H, W, ratio, debug):
+        """The template branch on the main stream: deform the template, record `fork` (what the side streams wait for), then the
+        silhouette, the mask loss, its inner backward and the template step (computeTmpPcLoss).  -> (defTmpVs, seedVs, fork, loss)"""
+        poses, trans, d_cond, _ = self.dataset.get_grad_parameters(frame_ids, frame_ids.device)
         defconds = [d_cond, [poses, trans]]
         self._mark('start')
         defTmpVs = self.deformer(self.TmpVs[None, :, :].expand(N, -1, 3), defconds, ratio=ratio)
@@ -428,8 +475,6 @@ class OptimNetwork(nn.Module):
         # main stream; the selection runs on a side stream that only waits for the deformed template, so its syncs return
         # while the GPU is still busy with the template branch; the (sync-free) refiner is then issued behind it.
         # The seeds are taken from the canonical vertices as they are now (the template step moves TmpVs).
-        main = torch.cuda.current_stream(device)
-        side = self._side_stream(device)
         seedVs = self.TmpVs.detach().clone()
         self.sdf.packed_weights(); self.deformer.defs[0].packed_weights()   # the per-step weight packs are made HERE, on the main
         fork = torch.cuda.Event()                                           # stream, before the fork: the side stream reads them
@@ -440,104 +485,105 @@ class OptimNetwork(nn.Module):
         masks = self._silhouette(defTmpVs, cameras_sil, H, W, self.point_radius)
         radius = int(np.round(self.point_radius / 2. * float(min(H, W)) / 1.2))
         mgtMs = F.max_pool2d(gtMs, kernel_size=2 * radius + 1, stride=1, padding=radius) if radius > 0 else gtMs
-        total_loss = self.computeTmpPcLoss(defTmpVs, defconds, masks, mgtMs, ratio)
+        loss = self.computeTmpPcLoss(defTmpVs, defconds, masks, mgtMs, ratio)
         self._mark('template branch issued')
+        return defTmpVs, seedVs, fork, loss
 
-        use_regu = 'def_regu' in self.conf and self.conf.get_float('def_regu.weight') > 0.
-        sample_pix = self.conf.get_int('sample_pix_num') if 'sample_pix_num' in self.conf else sample_pix
-        fused_sel = FUSED_SELECTION and 'frags' not in datas and self.seed_mode == "mesh"
-        eik_idx = regu_idx = None
+    def _select_rays(self, side, fork, datas, gtMs, cameras, defTmpVs, seedVs, H, W, n_max, use_regu, rand, debug):
+        """Ray selection on the side stream after `fork` (fused or sequential), then the rays; records `selected` on the side stream."""
         with torch.cuda.stream(side):
             side.wait_event(fork)
             self._debug_delay('side_after_wait')
-            if fused_sel:
-                with torch.no_grad():
-                    self._mark('sel: entered')
-                    xy, z = cameras.project_ndc(defTmpVs.detach())
-                    self._mark('sel: projected')
-                    frags = rasterize_meshes(xy, z, self.Tmpfs, H, W)
-                    self._mark('sel: rasterised')
-                    if debug is not None:
-                        debug.update(proj_xy=xy.clone(), proj_z=z.clone(), pix_to_face=frags.pix_to_face.clone())
-                    # FindSurfacePs' pixel test (first fragment inside its face) AND the ground-truth mask, as one image-shaped flag
-                    K = frags.pix_to_face.shape[-1]
-                    inner = (frags.bary_coords > 0.0).all(-1) & (frags.pix_to_face >= 0)
-                    ks = torch.arange(K, device=device).view(1, 1, 1, K).expand_as(inner)
-                    first = torch.where(inner, ks, torch.full_like(ks, K)).amin(dim=-1)
-                    flag = ((first < K) & (gtMs > 0.)).view(-1)
-                    # the Bernoulli subsample: pixel i of the filtered list keeps its place when u[i] < sample / count -- i is the
-                    # exclusive prefix sum of the flags, the count its last element; the reference's float(sample) / float(count)
-                    # is a double division rounded to float32 by the comparison, and so is this
-                    rank = torch.cumsum(flag, 0) - 1
-                    pnum_dev = rank[-1] + 1
-                    u = rand['ray_select'] if 'ray_select' in rand else torch.rand(flag.numel(), device=device)
-                    cap = float(sample_pix * N)
-                    thr = torch.where(pnum_dev > sample_pix * N, (cap / pnum_dev.double()).float(), torch.full((), 2., device=device))
-                    keep = flag & (u[rank.clamp(min=0, max=u.numel() - 1)] < thr)
-                    masks_1d = [keep]
-                    vsel = rand['vert_select'][:TmpVnum] if 'vert_select' in rand else torch.rand(TmpVnum, device=device)
-                    masks_1d.append(vsel < 4096. / float(TmpVnum))
-                    if use_regu:
-                        vsel2 = rand['vert_select2'][:TmpVnum] if 'vert_select2' in rand else torch.rand(TmpVnum, device=device)
-                        masks_1d.append(vsel2 < 4096. / float(TmpVnum))
-                    lists, (pnum_all,) = hostsync.nonzero_many(masks_1d, also=[pnum_dev])        # THE round trip of the selection
-                    if pnum_all > u.numel():
-                        raise ValueError(f"rand['ray_select'] holds {u.numel()} numbers, {pnum_all} pixels passed the two mask filters")
-                    self._debug_delay('side_lists_made')
-                    self._mark('sel: inside the mask')
-                    lin = lists[0]
-                    batch_inds, row_inds, col_inds = lin // (H * W), (lin // W) % H, lin % W
-                    eik_idx = lists[1]
-                    regu_idx = lists[2] if use_regu else None
-                    kk = first.view(-1)[lin].clamp(max=K - 1).view(-1, 1)
-                    finds = torch.gather(frags.pix_to_face.view(-1, K)[lin], 1, kk).view(-1) % self.Tmpfs.shape[0]
-                    ws = torch.gather(frags.bary_coords.view(-1, K, 3)[lin], 1, kk.view(-1, 1, 1).expand(-1, 1, 3)).view(-1, 3)
-                    initTmpPs = (seedVs[self.Tmpfs[finds].view(-1)].view(-1, 3, 3) * ws[:, :, None]).sum(1)
-                    pnum = batch_inds.shape[0]
-            else:
-                with torch.no_grad():
-                    if 'frags' in datas:
-                        batch_inds, row_inds, col_inds, initTmpPs, _ = FindSurfacePs(seedVs, self.Tmpfs, datas['frags'])
-                    elif self.seed_mode == "mesh":            # in-repo hard mesh rasteriser -> FindSurfacePs, as the reference does with pytorch3d
-                        self._mark('sel: entered')
-                        xy, z = cameras.project_ndc(defTmpVs.detach())
-                        self._mark('sel: projected')
-                        frags = rasterize_meshes(xy, z, self.Tmpfs, H, W)
-                        self._mark('sel: rasterised')
-                        if debug is not None:
-                            debug.update(proj_xy=xy.clone(), proj_z=z.clone(), pix_to_face=(frags[0] if isinstance(frags, (tuple, list)) else frags.pix_to_face).clone())
-                        batch_inds, row_inds, col_inds, initTmpPs, _ = FindSurfacePs(seedVs, self.Tmpfs, frags)
-                        self._mark('sel: seeds found')
-                    else:
-                        batch_inds, row_inds, col_inds, initTmpPs = self._seed_rays(defTmpVs.detach(), cameras, H, W, seedVs)
-                # boolean masks are turned into index lists ONCE (each `x[mask]` is its own nonzero + host sync)
-                sel = hostsync.nonzero(gtMs[batch_inds, row_inds, col_inds] > 0.).view(-1)
-                batch_inds, row_inds, col_inds, initTmpPs = batch_inds[sel], row_inds[sel], col_inds[sel], initTmpPs[sel]
-                self._mark('sel: inside the mask')
-                pnum = batch_inds.shape[0]
-                if pnum > sample_pix * N:
-                    u = rand['ray_select'][:pnum] if 'ray_select' in rand else torch.rand(pnum, device=device)
-                    sel = hostsync.nonzero(u < float(sample_pix * N) / float(pnum)).view(-1)
-                    batch_inds, row_inds, col_inds, initTmpPs = batch_inds[sel], row_inds[sel], col_inds[sel], initTmpPs[sel]
-                    pnum = batch_inds.shape[0]
+            select = self._select_rays_fused if FUSED_SELECTION and 'frags' not in datas else self._select_rays_sequential
+            with torch.no_grad():
+                batch_inds, row_inds, col_inds, seeds, eik_idx, regu_idx = select(datas, gtMs, cameras, defTmpVs, seedVs, H, W, n_max, use_regu, rand, debug)
             pixels = torch.stack([col_inds, row_inds, torch.ones_like(col_inds)], dim=-1).float()
             rays = cameras.view_rays(pixels)
-            initTmpPs = initTmpPs.contiguous()
+            seeds = seeds.contiguous()
             if debug is not None:
-                debug.update(batch_inds=batch_inds, row_inds=row_inds, col_inds=col_inds, seeds=initTmpPs.clone())
+                debug.update(batch_inds=batch_inds, row_inds=row_inds, col_inds=col_inds, seeds=seeds.clone())
             selected = torch.cuda.Event()
             selected.record(side)
+        return _Selection(batch_inds, row_inds, col_inds, seeds, rays, pixels, eik_idx, regu_idx, selected)
+
+    def _select_rays_fused(self, datas, gtMs, cameras, defTmpVs, seedVs, H, W, n_max, use_regu, rand, debug):
+        """Fused selection on the current (side) stream: the three pixel filters as one image-shaped flag and the two vertex
+        subsets, with ONE host round trip for the three counts.  -> (batch, row, col, seeds, eik_idx, regu_idx)"""
+        device, TmpVnum = gtMs.device, self.TmpVs.shape[0]
+        frags = self._rasterise_template(cameras, defTmpVs, H, W, debug)
+        # FindSurfacePs' pixel test (first fragment inside its face) AND the ground-truth mask, as one image-shaped flag
+        K = frags.pix_to_face.shape[-1]
+        inner = (frags.bary_coords > 0.0).all(-1) & (frags.pix_to_face >= 0)
+        ks = torch.arange(K, device=device).view(1, 1, 1, K).expand_as(inner)
+        first = torch.where(inner, ks, torch.full_like(ks, K)).amin(dim=-1)
+        flag = ((first < K) & (gtMs > 0.)).view(-1)
+        # the Bernoulli subsample: pixel i of the filtered list keeps its place when u[i] < sample / count -- i is the
+        # exclusive prefix sum of the flags, the count its last element; the reference's float(sample) / float(count)
+        # is a double division rounded to float32 by the comparison, and so is this
+        rank = torch.cumsum(flag, 0) - 1
+        pnum_dev = rank[-1] + 1
+        u = _random(rand, 'ray_select', torch.rand, flag.numel(), device=device)
+        thr = torch.where(pnum_dev > n_max, (float(n_max) / pnum_dev.double()).float(), torch.full((), 2., device=device))
+        keep = flag & (u[rank.clamp(min=0, max=u.numel() - 1)] < thr)
+        masks_1d = [keep, _vertex_subset(rand, 'vert_select', TmpVnum, device)]
+        if use_regu:
+            masks_1d.append(_vertex_subset(rand, 'vert_select2', TmpVnum, device))
+        lists, (pnum_all,) = hostsync.nonzero_many(masks_1d, also=[pnum_dev])        # THE round trip of the selection
+        if pnum_all > u.numel():
+            raise ValueError(f"rand['ray_select'] holds {u.numel()} numbers, {pnum_all} pixels passed the two mask filters")
+        self._debug_delay('side_lists_made')
+        self._mark('sel: inside the mask')
+        lin = lists[0]
+        batch_inds, row_inds, col_inds = lin // (H * W), (lin // W) % H, lin % W
+        kk = first.view(-1)[lin].clamp(max=K - 1).view(-1, 1)
+        finds = torch.gather(frags.pix_to_face.view(-1, K)[lin], 1, kk).view(-1) % self.Tmpfs.shape[0]
+        ws = torch.gather(frags.bary_coords.view(-1, K, 3)[lin], 1, kk.view(-1, 1, 1).expand(-1, 1, 3)).view(-1, 3)
+        seeds = (seedVs[self.Tmpfs[finds].view(-1)].view(-1, 3, 3) * ws[:, :, None]).sum(1)
+        return batch_inds, row_inds, col_inds, seeds, lists[1], (lists[2] if use_regu else None)
+
+    def _select_rays_sequential(self, datas, gtMs, cameras, defTmpVs, seedVs, H, W, n_max, use_regu, rand, debug):
+        """Sequential selection on the current (side) stream, one host round trip per filter as network.py:519-526 writes them:
+        FindSurfacePs (on `datas['frags']` or the mesh rasteriser's), inside the mask, the subsample; no vertex subsets yet."""
+        if 'frags' in datas:
+            batch_inds, row_inds, col_inds, seeds, _ = FindSurfacePs(seedVs, self.Tmpfs, datas['frags'])
+        else:                                        # in-repo hard mesh rasteriser -> FindSurfacePs, as the reference does with pytorch3d
+            frags = self._rasterise_template(cameras, defTmpVs, H, W, debug)
+            batch_inds, row_inds, col_inds, seeds, _ = FindSurfacePs(seedVs, self.Tmpfs, frags)
+            self._mark('sel: seeds found')
+        # boolean masks are turned into index lists ONCE (each `x[mask]` is its own nonzero + host sync)
+        sel = hostsync.nonzero(gtMs[batch_inds, row_inds, col_inds] > 0.).view(-1)
+        batch_inds, row_inds, col_inds, seeds = batch_inds[sel], row_inds[sel], col_inds[sel], seeds[sel]
+        self._mark('sel: inside the mask')
+        pnum = batch_inds.shape[0]
+        if pnum > n_max:
+            u = _random(rand, 'ray_select', torch.rand, pnum, device=gtMs.device)
+            sel = hostsync.nonzero(u < float(n_max) / float(pnum)).view(-1)
+            batch_inds, row_inds, col_inds, seeds = batch_inds[sel], row_inds[sel], col_inds[sel], seeds[sel]
+        return batch_inds, row_inds, col_inds, seeds, None, None
+
+    def _rasterise_template(self, cameras, defTmpVs, H, W, debug):
+        """The mesh rasteriser over the deformed template on the current stream -> fragments (fills the `debug` projection keys)."""
+        self._mark('sel: entered')
+        xy, z = cameras.project_ndc(defTmpVs.detach())
+        self._mark('sel: projected')
+        frags = rasterize_meshes(xy, z, self.Tmpfs, H, W)
+        self._mark('sel: rasterised')
+        if debug is not None:
+            debug.update(proj_xy=xy.clone(), proj_z=z.clone(), pix_to_face=frags.pix_to_face.clone())
+        return frags
+
+    def _refine(self, rstream, main, sel, cameras, frame_ids, ratio, rand):
+        """The refiner on `rstream` (main waits for `selected` first when that is main); records the `refiner_events` pair and
+        `refined` on `rstream`.  -> (points, check, refined)"""
         # The refiner (no autograd) stays on the side stream and runs CONCURRENTLY with the template branch (refiner_stream = "side",
         # the default: its short layer launches fill the gaps and tails of the template branch's large kernels, ~2 ms / iteration),
         # or follows it on the main stream ("main": what bench.py's instrumented pass uses, because with two streams of GEMMs no
         # per-kernel duration -- events or rocprof -- is a kernel's own any more).
-        self._mark('rays selected')
-        on_side = getattr(self, 'refiner_stream', 'side') == 'side'
-        rstream = side if on_side else main
-        if not on_side:
-            main.wait_event(selected)
+        device = frame_ids.device
+        if rstream is main:
+            main.wait_event(sel.selected)
             mlp_engine.PROFILE.overlap = False
-            for t in (batch_inds, row_inds, col_inds, initTmpPs, rays, pixels):
+            for t in (sel.batch_inds, sel.row_inds, sel.col_inds, sel.seeds, sel.rays, sel.pixels):
                 t.record_stream(main)
         with torch.cuda.stream(rstream), torch.no_grad():
             self._debug_delay('refiner_start')
@@ -547,71 +593,57 @@ class OptimNetwork(nn.Module):
                 r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 r0.record(rstream)
             if 'refined' in rand:                # parity tests: the refiner's output for exactly these rays, taken from the other side
-                initTmpPs, check = rand['refined'][0].to(device).float().contiguous(), rand['refined'][1].to(device).bool()
-                assert initTmpPs.shape[0] == batch_inds.shape[0] and check.shape[0] == batch_inds.shape[0]
-            else:
-                initTmpPs, check = OptimizeSurfacePs(cameras.cam_pos().detach(), rays.detach(), initTmpPs, batch_inds, self.sdf, ratio,
-                                                     self.deformer, [d_cond_s, [poses_s, trans_s]], dthreshold=5.e-5,
-                                                     athreshold=self.angThred, w1=3.05, w2=1., times=10)
+                points, check = rand['refined'][0].to(device).float().contiguous(), rand['refined'][1].to(device).bool()
+                assert points.shape[0] == sel.batch_inds.shape[0] and check.shape[0] == sel.batch_inds.shape[0]
+            else:                                # (the module global, looked up at call time: tests/_inject.py replaces it)
+                points, check = OptimizeSurfacePs(cameras.cam_pos().detach(), sel.rays.detach(), sel.seeds, sel.batch_inds, self.sdf, ratio,
+                                                  self.deformer, [d_cond_s, [poses_s, trans_s]], dthreshold=5.e-5,
+                                                  athreshold=self.angThred, w1=3.05, w2=1., times=10)
             if rev is not None:
                 r1.record(rstream); rev.append((r0, r1))
             refined = torch.cuda.Event()
             refined.record(rstream)
             self._mark('refiner done (its stream)')
-        self._mark('refiner issued')
-        if eik_idx is None:
-            aux = self._side_stream(device, 1)
-            with torch.cuda.stream(aux), torch.no_grad():
-                # (sequential selection) vertex subsets of the eikonal / def-regu samples: the Bernoulli masks do not depend on the vertex
-                # positions, so their index lists (one host sync each) are made on a stream of their own AFTER the refiner has been issued
-                # -- nothing before the refiner waits for them, and they do not wait for the refiner; the gathers happen after the
-                # template step, as in the reference
-                aux.wait_event(fork)
-                self._debug_delay('aux_after_wait')
-                vsel = rand['vert_select'][:TmpVnum] if 'vert_select' in rand else torch.rand(TmpVnum, device=device)
-                eik_idx = hostsync.nonzero(vsel < 4096. / float(TmpVnum)).view(-1)
-                if use_regu:
-                    vsel2 = rand['vert_select2'][:TmpVnum] if 'vert_select2' in rand else torch.rand(TmpVnum, device=device)
-                    regu_idx = hostsync.nonzero(vsel2 < 4096. / float(TmpVnum)).view(-1)
-            join_vertex_lists = lambda: main.wait_stream(aux)
-        else:
-            join_vertex_lists = lambda: main.wait_event(selected)       # (made with the ray selection, on its stream)
+        return points, check, refined
+
+    def _vertex_subsets(self, aux, fork, use_regu, rand, device):
+        """(sequential selection) The eikonal / def-regu vertex subsets on the aux stream after `fork`, one host round trip each."""
+        TmpVnum = self.TmpVs.shape[0]
+        with torch.cuda.stream(aux), torch.no_grad():
+            # the Bernoulli masks do not depend on the vertex positions: nothing before the refiner waits for their lists, and they do not
+            # wait for the refiner; the gathers happen after the template step, as in the reference
+            aux.wait_event(fork)
+            self._debug_delay('aux_after_wait')
+            eik_idx = hostsync.nonzero(_vertex_subset(rand, 'vert_select', TmpVnum, device)).view(-1)
+            regu_idx = hostsync.nonzero(_vertex_subset(rand, 'vert_select2', TmpVnum, device)).view(-1) if use_regu else None
+        return eik_idx, regu_idx
+
+    def _sampled_terms(self, total_loss, main, side, sel, points, check, eik_idx, regu_idx, frame, frame_ids, N, ratio, rand, debug):
+        """On the main stream: the samples' noise, the join with the side stream, then the eikonal, offset, def-regu and DCT terms."""
         # The eikonal and deformation-regulariser samples are [refined ray points ; a random subset of the template vertices] (+ uniform
-        # samples), one batch each as the reference writes it.  (Rounds 3-5 carried a split form -- the refiner-independent part first --
-        # that never paid: the refiner then shares the machine and ends later.)
-        self._debug_delay('main_before_join')
-        join_vertex_lists()
-        for t in (eik_idx, regu_idx):
-            if t is not None:
-                t.record_stream(main)
-        poses, trans, d_cond, rendcond = self.dataset.get_grad_parameters(frame_ids, device)     # (the inner backward freed the first set's graph)
-        defconds = [d_cond, [poses, trans]]
-        nr = batch_inds.shape[0]
+        # samples), one batch each as the reference writes it (a split form, the refiner-independent part first, never paid).
+        device = frame_ids.device
+        poses, trans, d_cond, _ = frame
+        nr = sel.batch_inds.shape[0]
         n_base = nr + eik_idx.shape[0]
-        n_glob = n_base // 6
-        nl = rand['eik_local'][:n_base] if 'eik_local' in rand else torch.randn(n_base, 3, device=device)
-        ng = rand['eik_global'][:n_glob] if 'eik_global' in rand else torch.rand(n_glob, 3, device=device)
-        if use_regu:
+        nl = _random(rand, 'eik_local', torch.randn, n_base, 3, device=device)
+        ng = _random(rand, 'eik_global', torch.rand, n_base // 6, 3, device=device)
+        if regu_idx is not None:
             n_regu = nr + regu_idx.shape[0]
-            nl2 = rand['regu_local'][:n_regu] if 'regu_local' in rand else torch.randn(n_regu, 3, device=device)
+            nl2 = _random(rand, 'regu_local', torch.randn, n_regu, 3, device=device)
         self._mark('vertex-part samples issued')
 
         main.wait_stream(side)
         mlp_engine.PROFILE.overlap = False
-        for t in (batch_inds, row_inds, col_inds, initTmpPs, rays, pixels, check):
-            if t is not None:
-                t.record_stream(main)
-
+        for t in (sel.batch_inds, sel.row_inds, sel.col_inds, points, sel.rays, sel.pixels, check):
+            t.record_stream(main)
         self.info['rayInfo'] = (check.numel(), check.sum())
         self.TmpPs = None
         if debug is not None:
-            debug.update(initTmpPs=initTmpPs, check=check, rays=rays)
+            debug.update(initTmpPs=points, check=check, rays=sel.rays)
 
         # --- eikonal (network.py:543-549; sample_points utils.py:74-84)
-        base = torch.cat([initTmpPs, self.TmpVs.detach()[eik_idx]], dim=0)
-        pts = torch.cat([base + nl * 0.01, ng * (1.8 * 2) - 1.8], dim=0)
-        self._eik_pts = pts.detach()
-        grad_loss = self._eikonal_mean(pts, ratio)
+        grad_loss = self.loss_eikonal(torch.cat([points, self.TmpVs.detach()[eik_idx]], dim=0), ratio, nl, ng)
         self._mark('eikonal issued')
         self.info['grad_loss'] = grad_loss.detach()
         wpool = srdist.pooled_mean_weight(n_base, device)      # N > 1 ranks: pooled mean over the points of all ranks (caveat B)
@@ -633,9 +665,8 @@ class OptimNetwork(nn.Module):
                 self.info['offset_loss'] = self.deformer.defs[0].offset.view(-1, 3).norm(p=2, dim=-1).mean()
 
         # --- deformation regulariser (network.py:565-582)
-        if use_regu:
-            pts = torch.cat([initTmpPs, self.TmpVs.detach()[regu_idx]], dim=0)
-            def_loss = self._def_regu_mean(torch.cat([pts, pts + nl2 * 0.01], dim=0), d_cond, N, ratio)
+        if regu_idx is not None:
+            def_loss = self.loss_def_regu(torch.cat([points, self.TmpVs.detach()[regu_idx]], dim=0), d_cond, N, ratio, nl2)
             self.info['def_loss'] = def_loss.detach()
             wpool = srdist.pooled_mean_weight(n_regu, device)
             if wpool is not None:
@@ -647,12 +678,15 @@ class OptimNetwork(nn.Module):
             dct_loss = self.loss_dct(frame_ids, N)
             total_loss = total_loss + dct_loss * self.conf.get_float('dct_weight')
             self.info['dct_loss'] = dct_loss.detach()
+        return total_loss
 
-        # --- colour + normal branches on the converged rays (network.py:599-639)
+    def _ray_branch(self, total_loss, main, side, on_side, refined, sel, points, check, datas, gtCs, cameras, cam_learn, frame, frame_ids, H, W, ratio):
+        """Colour + normal terms on the converged rays, added to `total_loss`: the count on the side stream after `refined`, then the
+        branch on the side stream or on main (after it joins the side stream); eager: back-propagated here, the context in `_ray_ctx`."""
+        N, nr = gtCs.shape[0], sel.batch_inds.shape[0]
         self.info['color_loss'] = -1.0
         # one host sync for all the gathers below -- taken on the side stream, which waits for the refiner only: the eikonal /
-        # def-regu / DCT work queued above keeps the GPU busy while the host learns the count and issues the next branch
-        self._mark('dct issued')
+        # def-regu / DCT work queued before keeps the GPU busy while the host learns the count and issues the next branch.
         # MASKED ray branch (round 6, `masked_ray_branch_below`, off by default): with few selected rays -- one frame per rank: 2048 -- the
         # colour / normal terms and the implicit-gradient pass run on ALL selected rays, the rays the refiner did not accept carrying a
         # frame index of -1 into the two loss reductions (no term, no count, exact-zero gradients; a zero row of dl/dTmpPs gives zero
@@ -675,70 +709,53 @@ class OptimNetwork(nn.Module):
             main.wait_stream(side)
             if conv_idx is not None:
                 conv_idx.record_stream(main)
-        if nconv > 0:
-            ctx = None
+        if nconv == 0:
+            return total_loss
+        if eager:
+            # the real per-frame / camera tensors (graph to the dataset's leaves, made on the MAIN stream): only the hand-over of
+            # the stand-ins' gradients goes through them, after the streams have joined
+            dep = self._frame_tensors(frame_ids, N, cam_learn)
+        with torch.cuda.stream(rb):
+            self._debug_delay('ray_branch_start')
             if eager:
-                # the real per-frame / camera tensors (graph to the dataset's leaves, made on the MAIN stream): only the hand-over of
-                # the stand-ins' gradients goes through them, after the streams have joined
-                dep = [t for t in self.dataset.get_grad_parameters(frame_ids, device)] + (list(self.dataset.get_camera_parameters(N, device)[:4]) if cam_learn else [])
-            with torch.cuda.stream(rb):
-                self._debug_delay('ray_branch_start')
-                if eager:
-                    with torch.no_grad():
-                        vals = list(self.dataset.get_grad_parameters(frame_ids, device)) + (list(self.dataset.get_camera_parameters(N, device)[:4]) if cam_learn else [])
-                    prox = [v.detach().requires_grad_(o.requires_grad) for v, o in zip(vals, dep)]
-                    r_poses, r_trans, r_dcond, r_rendcond = prox[:4]
-                    r_cameras = RectifiedPerspectiveCameras(*prox[4:8], image_size=[(W, H)]) if cam_learn else cameras
-                    ctx = {'stream': rb, 'pairs': [(o, p_) for o, p_ in zip(dep, prox) if o.requires_grad], 'cameras': r_cameras,
-                           'frame': (r_poses, r_trans, r_dcond), 'main': main}
-                    for t in (gtCs, datas['normal']) if 'normal' in datas else (gtCs,):
-                        if on_rb_side and torch.is_tensor(t) and t.is_cuda:
-                            t.record_stream(rb)
-                else:
-                    r_poses, r_trans, r_dcond, r_rendcond, r_cameras = poses, trans, d_cond, rendcond, cameras
-                if masked:
-                    self.TmpPs = initTmpPs.detach().clone()
-                    self.TmpPs.requires_grad = True
-                    self.batch_inds, self.col_inds, self.row_inds = batch_inds, col_inds, row_inds
-                    self.ray_valid = check
-                    self.rays = r_cameras.view_rays(pixels) if (eager and cam_learn) else rays
-                else:
-                    self.TmpPs = initTmpPs[conv_idx]
-                    self.TmpPs.requires_grad = True
-                    self.batch_inds, self.col_inds, self.row_inds = batch_inds[conv_idx], col_inds[conv_idx], row_inds[conv_idx]
-                    self.ray_valid = None
-                    # (the rays of the converged pixels from the branch's own camera object: the same rows as rays[conv_idx], bit for bit)
-                    self.rays = r_cameras.view_rays(pixels[conv_idx]) if (eager and cam_learn) else rays[conv_idx]
-                extra = self.loss_color_normal(datas, gtCs, r_cameras, [r_dcond, [r_poses, r_trans]], r_rendcond, ratio, N)
-                if on_rb_side and torch.is_tensor(extra):
-                    known = torch.cuda.Event()           # the VALUE of the two terms joins the returned loss on the main stream; the forward
-                    known.record(rb)                     # of the branch is queued long before the main stream gets to that addition
-                    main.wait_event(known)
-                    extra.detach().record_stream(main)
-                if eager and torch.is_tensor(extra) and extra.requires_grad:
-                    self._mark('ray branch forward issued')
-                    value = extra.detach()
-                    extra.backward()                     # inner backward: TmpPs.grad, the stand-ins' gradients, the deferred weight gradients
-                    ctx['bwd_done'] = torch.cuda.Event()
-                    ctx['bwd_done'].record(rb)
-                    self._mark('ray branch backward done (its stream)')
-                    self._ray_ctx = ctx
-                    extra = value
-            total_loss = total_loss + extra
+                with torch.no_grad():
+                    vals = self._frame_tensors(frame_ids, N, cam_learn)
+                prox = [v.detach().requires_grad_(o.requires_grad) for v, o in zip(vals, dep)]
+                r_poses, r_trans, r_dcond, r_rendcond = prox[:4]
+                r_cameras = RectifiedPerspectiveCameras(*prox[4:8], image_size=[(W, H)]) if cam_learn else cameras
+                for t in (gtCs, datas['normal']) if 'normal' in datas else (gtCs,):
+                    if on_rb_side and torch.is_tensor(t) and t.is_cuda:
+                        t.record_stream(rb)
+            else:
+                (r_poses, r_trans, r_dcond, r_rendcond), r_cameras = frame, cameras
+            rows = (lambda t: t) if masked else (lambda t: t[conv_idx])     # masked: every selected ray, else the converged ones
+            self.TmpPs = points.detach().clone() if masked else points[conv_idx]
+            self.TmpPs.requires_grad = True
+            self.batch_inds, self.col_inds, self.row_inds = rows(sel.batch_inds), rows(sel.col_inds), rows(sel.row_inds)
+            self.ray_valid = check if masked else None
+            # (with learnable cameras, the rays from the branch's own camera object: the same rows as rows(rays), bit for bit)
+            self.rays = r_cameras.view_rays(rows(sel.pixels)) if (eager and cam_learn) else rows(sel.rays)
+            extra = self.loss_color_normal(datas, gtCs, r_cameras, [r_dcond, [r_poses, r_trans]], r_rendcond, ratio, N)
+            if on_rb_side and torch.is_tensor(extra):
+                known = torch.cuda.Event()           # the VALUE of the two terms joins the returned loss on the main stream; the forward
+                known.record(rb)                     # of the branch is queued long before the main stream gets to that addition
+                main.wait_event(known)
+                extra.detach().record_stream(main)
+            if eager and torch.is_tensor(extra) and extra.requires_grad:
+                self._mark('ray branch forward issued')
+                value = extra.detach()
+                extra.backward()                     # inner backward: TmpPs.grad, the stand-ins' gradients, the deferred weight gradients
+                bwd_done = torch.cuda.Event()
+                bwd_done.record(rb)
+                self._mark('ray branch backward done (its stream)')
+                self._ray_ctx = _RayBranch(rb, main, [(o, p_) for o, p_ in zip(dep, prox) if o.requires_grad], r_cameras, (r_poses, r_trans, r_dcond), bwd_done)
+                extra = value
+        return total_loss + extra
 
-        # guard of the eager contract (docstring (a)): remember one gradient tensor the inner backwards of this call deposited
-        self._eager_guard = None
-        if torch.is_grad_enabled() and (EAGER_TEMPLATE_TERM or EAGER_RAY_BRANCH):
-            lw = getattr(self.dataset, 'learnable_weights', None)
-            for leaf in (lw() if lw is not None else ()):
-                if leaf.grad is not None:
-                    self._eager_guard = (leaf, leaf.grad)
-                    break
-        self.remesh_time = np.floor(self.remesh_time) + float(self.forward_time % self.remesh_intersect) / float(self.remesh_intersect)
-        self.info['remesh'] = self.remesh_time
-        self.forward_time += 1
-        self._mark('forward issued')
-        return total_loss
+    def _frame_tensors(self, frame_ids, N, cam_learn):
+        """The per-frame tensors of `frame_ids` (+ the four camera tensors when they are learnable) on the current stream."""
+        out = list(self.dataset.get_grad_parameters(frame_ids, frame_ids.device))
+        return out + (list(self.dataset.get_camera_parameters(N, frame_ids.device)[:4]) if cam_learn else [])
 
     def _finish_ray_branch(self, final=True):
         """Hands the gradients the ray branch's stand-ins have collected (colour / normal backward, implicit-gradient pass) to the
@@ -748,15 +765,15 @@ class OptimNetwork(nn.Module):
         ctx = getattr(self, '_ray_ctx', None)
         if ctx is None:
             return
-        main, rb = ctx['main'], ctx['stream']
+        main, rb = ctx.main, ctx.stream
         if final:
             self._ray_ctx = None
             with torch.cuda.stream(main):
                 self._debug_delay('main_before_ray_join')
         if rb is not main:
-            main.wait_stream(rb) if final else main.wait_event(ctx['bwd_done'])
+            main.wait_stream(rb) if final else main.wait_event(ctx.bwd_done)
         outs, grads = [], []
-        for o, p_ in ctx['pairs']:
+        for o, p_ in ctx.pairs:
             if p_.grad is not None:
                 outs.append(o); grads.append(p_.grad)
                 if rb is not main:
@@ -767,8 +784,13 @@ class OptimNetwork(nn.Module):
                 torch.autograd.backward(outs, grads, retain_graph=not final)
 
     # ------------------------------------------------------------------ loss terms (a14)
-    def _eikonal_mean(self, pts, ratio):
-        """((|grad f| - 1)^2).mean() over the given points (network.py:547-549)."""
+    def loss_eikonal(self, base, ratio, noise_local=None, noise_global=None):
+        """sample_points (utils.py:74-84) + ((|grad f| - 1)^2).mean() over those points (network.py:543-549)."""
+        n_global = base.shape[0] // 6
+        noise_local = torch.randn_like(base) if noise_local is None else noise_local[:base.shape[0]]
+        noise_global = torch.rand(n_global, 3, device=base.device) if noise_global is None else noise_global[:n_global]
+        pts = torch.cat([base + noise_local * 0.01, noise_global * (1.8 * 2) - 1.8], dim=0)
+        self._eik_pts = pts.detach()
         pts = pts.detach().requires_grad_()
         pred = self.sdf(pts, ratio, sdf_only=True)
         grad = self.sdf.gradient(pts, pred)
@@ -776,28 +798,17 @@ class OptimNetwork(nn.Module):
             return step_ops.EikonalLoss.apply(grad)
         return ((grad.norm(2, dim=-1) - 1) ** 2).mean()
 
-    def loss_eikonal(self, base, ratio, noise_local=None, noise_global=None):
-        """sample_points (utils.py:74-84) + ((|grad f| - 1)^2).mean()."""
-        n_global = base.shape[0] // 6
-        noise_local = torch.randn_like(base) if noise_local is None else noise_local[:base.shape[0]]
-        noise_global = torch.rand(n_global, 3, device=base.device) if noise_global is None else noise_global[:n_global]
-        pts = torch.cat([base + noise_local * 0.01, noise_global * (1.8 * 2) - 1.8], dim=0)
-        self._eik_pts = pts.detach()
-        return self._eikonal_mean(pts, ratio)
-
-    def _def_regu_mean(self, pts, d_cond, N, ratio):
-        """GMRobustError(sum log^2 s(J)).mean() of the translator's Jacobian at `pts` for each of the N frames (network.py:565-582)."""
+    def loss_def_regu(self, pts, d_cond, N, ratio, noise_local=None):
+        """GMRobustError(sum log^2 s(J)).mean() of the translator's Jacobian at [pts ; pts + noise] for each of the N frames
+        (network.py:565-582)."""
         from .Deformer import translator_value_jacobian
-        pts = pts.view(1, -1, 3).expand(N, -1, 3)
+        noise_local = torch.randn_like(pts) if noise_local is None else noise_local[:pts.shape[0]]
+        pts = torch.cat([pts, pts + noise_local * 0.01], dim=0).view(1, -1, 3).expand(N, -1, 3)
         _, Jacobs = translator_value_jacobian(self.deformer.defs[0], pts.contiguous(), d_cond, None, ratio)   # forward-mode Jacobian
         if step_ops.ENABLED and Jacobs.is_cuda and Jacobs.numel() > 0:
             return step_ops.DefReguLoss.apply(Jacobs, self.conf.get_float('def_regu.c'))
         s = torch.log(singular_values_3x3(Jacobs))
         return U.GMRobustError((s * s).sum(1), self.conf.get_float('def_regu.c'), True).mean()
-
-    def loss_def_regu(self, pts, d_cond, N, ratio, noise_local=None):
-        noise_local = torch.randn_like(pts) if noise_local is None else noise_local[:pts.shape[0]]
-        return self._def_regu_mean(torch.cat([pts, pts + noise_local * 0.01], dim=0), d_cond, N, ratio)
 
     def loss_dct(self, frame_ids, N):
         klen, Nlen = self.dctnull.shape
@@ -829,13 +840,7 @@ class OptimNetwork(nn.Module):
                 color_loss = step_ops.ColorLoss.apply(colors, gtCs, b_loss, self.row_inds, self.col_inds)
             else:
                 color_loss = (gtCs[self.batch_inds, self.row_inds, self.col_inds, :] - colors).abs().sum(1)
-                if valid is None:
-                    color_loss = scatter_mean(color_loss, self.batch_inds, N).mean()
-                else:
-                    zero_ = torch.zeros((), dtype=color_loss.dtype, device=device)
-                    s_ = torch.zeros(N, dtype=color_loss.dtype, device=device).index_add(0, self.batch_inds, torch.where(valid, color_loss, zero_))
-                    c_ = torch.zeros(N, dtype=color_loss.dtype, device=device).index_add(0, self.batch_inds, valid.to(color_loss.dtype))
-                    color_loss = (s_ / c_.clamp(min=1)).mean()
+                color_loss = scatter_mean(color_loss, self.batch_inds, N, valid).mean()
             self.info['color_loss'] = color_loss.detach()
             total = total + self.conf.get_float('color_weight') * color_loss
         if 'normal' in datas and 'normal_weight' in self.conf and self.conf.get_float('normal_weight') > 0.:
@@ -854,21 +859,15 @@ class OptimNetwork(nn.Module):
                 gtnormals = datas['normal'].to(device)[self.batch_inds, self.row_inds, self.col_inds, :]
                 if getattr(self, "_flip", None) is None or self._flip.device != device:
                     self._flip = torch.tensor([[-1., 0., 0.], [0., 1., 0.], [0., 0., -1.]], device=device)      # cached: an H2D copy is a sync point
-                flip = self._flip
-                gtnormals = gtnormals.view(-1, 3) @ (cameras.R[0] @ flip).t()
+                gtnormals = gtnormals.view(-1, 3) @ (cameras.R[0] @ self._flip).t()
                 gtnorms = gtnormals.norm(dim=1, keepdim=True)
                 valid_mask = (gtnorms > 0.0001)[..., 0]
                 if valid is not None:
                     valid_mask = valid_mask & valid
                 gtnormals = torch.where(valid_mask[:, None], gtnormals / gtnorms.clamp(min=1e-12), gtnormals)
-                grad_d_p = jac['J']
-                gtnormals = U.small_matvec(grad_d_p.transpose(-2, -1), gtnormals.view(-1, 3))
+                gtnormals = U.small_matvec(jac['J'].transpose(-2, -1), gtnormals.view(-1, 3))
                 normal_loss = (gtnormals - nx).norm(2, dim=1) * weights
-                # scatter-mean over the valid rows without materialising the subset (no host sync): masked sums / masked counts
-                zero = torch.zeros((), dtype=normal_loss.dtype, device=device)
-                ssum = torch.zeros(N, dtype=normal_loss.dtype, device=device).index_add(0, self.batch_inds, torch.where(valid_mask, normal_loss, zero))
-                scnt = torch.zeros(N, dtype=normal_loss.dtype, device=device).index_add(0, self.batch_inds, valid_mask.to(normal_loss.dtype))
-                normal_loss = (ssum / scnt.clamp(min=1)).mean()
+                normal_loss = scatter_mean(normal_loss, self.batch_inds, N, valid_mask).mean()
             self.info['normal_loss'] = normal_loss.detach()
             total = total + self.conf.get_float('normal_weight') * normal_loss
         return total
@@ -950,10 +949,10 @@ class OptimNetwork(nn.Module):
         device = self.TmpPs.device
         # With a pending ray branch (forward() back-propagated the colour / normal terms on its stream, EAGER_RAY_BRANCH) the pass runs
         # on that stream with the branch's stand-ins of the per-frame / camera tensors; called on its own it uses the real ones.
-        with torch.cuda.stream(ctx['stream']) if ctx is not None else contextlib.nullcontext():
+        with torch.cuda.stream(ctx.stream) if ctx is not None else contextlib.nullcontext():
             if ctx is not None:
                 self._debug_delay('ray_branch_propagate_start')
-                (poses, trans, d_cond), cameras = ctx['frame'], ctx['cameras']
+                (poses, trans, d_cond), cameras = ctx.frame, ctx.cameras
             else:
                 poses, trans, d_cond, _ = self.dataset.get_grad_parameters(frame_ids, device)
                 cameras, H, W = self._cameras(frame_ids.numel(), device)        # rays / camera centre: rebuilt from the (possibly learnable) camera parameters, network.py:715-719
@@ -1004,7 +1003,7 @@ class OptimNetwork(nn.Module):
                 torch.autograd.backward(outs, cots)               # (TmpPs.grad also receives a contribution nobody reads)
             else:
                 leaves, seen = [], set()
-                frame_leaves = list(lw()) if ctx is None else [p_ for _, p_ in ctx['pairs']]
+                frame_leaves = list(lw()) if ctx is None else [p_ for _, p_ in ctx.pairs]
                 for t in list(self.sdf.parameters()) + list(self.deformer.parameters()) + frame_leaves:
                     if t.requires_grad and t.is_leaf and id(t) not in seen:
                         seen.add(id(t)); leaves.append(t)
