@@ -410,6 +410,31 @@ int sr_points_silhouette_bwd(const float* xy_ndc, const float* z, int64_t nimg, 
 int sr_rasterize_meshes(const float* xy_ndc, const float* z, const int64_t* faces, int64_t nimg, int64_t V, int64_t F, int32_t H, int32_t W,
                         void* zbuf_u64, int64_t* pix_to_face, float* bary, float* zout, void* stream);
 
+/* ---------------------------------------------------------------- shaded mesh previews of infer (csrc/shade.hip)
+ * The reference's infer renders two previews with pytorch3d 0.4.0's HardPhongShader (model/network.py:306-337, installed by
+ * infer.py:80-90): third-party code, restated from its published semantics, parity unpinned.  faces [F,3] int64 is
+ * one template shared by N deformed copies verts [N,V,3].  A face with an index outside [0, V) -- the -1 border faces of marching
+ * cubes -- is skipped; indices are NOT checked against V as an error (that would need a device-to-host copy).
+ * sr_vertex_adjacency: once per template: the vertex -> (face, corner) lists as CSR, sorted by 3 f + corner within a vertex:
+ *   offsets [V+1] int64 (offsets[V] = 3 x the number of used faces), nbr [3F,2] int32, 8-byte aligned = for corner c of face f the
+ *   pair (faces[f][(c+1)%3], faces[f][(c+2)%3]).  cursor: scratch of V int32.  V <= 2^31 - 1.
+ * sr_vertex_normals: Meshes.verts_normals_packed: n[v] = sum over its corners, in CSR order, of cross(p_next - p_v, p_prev - p_v),
+ *   then n / max(|n|, 1e-6) (a vertex in no face: 0) -> normals [N,V,3].  Fixed summation order: two calls return identical bits.
+ * sr_shade_phong: phong_shading + hard_rgb_blend with TexturesVertex of ones and one point light per image, on the fragments of
+ *   sr_rasterize_meshes (pix_to_face [N,H,W] packed img*F + f, bary [N,H,W,3]); cam_pos, light_loc [N,3] world space; host_phong[13]
+ *   = ambient rgb, diffuse rgb, specular rgb (each the light's colour times the material's), shininess, background rgb.  Per covered
+ *   pixel, p / n = the barycentric blends of verts / normals, texel = b0 + b1 + b2, L = normalize(light - p), n = normalize(n),
+ *   V = normalize(cam - p) (normalize: x / max(|x|, 1e-6)), c = n.L:
+ *     rgb = (ambient + diffuse relu(c)) texel + specular (relu(V.(2 c n - L)) [c > 0])^shininess
+ *   Background (pix_to_face < 0; also one outside [0, N F) or on a skipped face): the background colour.  rgba [N,H,W,4], 16-byte
+ *   aligned.  Alpha is written as 1: what pytorch3d 0.4.0's hard_rgb_blend is believed to concatenate -- UNPINNED (nothing here
+ *   could run pytorch3d; the reference's infer.py never reads it). */
+int sr_vertex_adjacency(const int64_t* faces, int64_t V, int64_t F, int64_t* offsets, int32_t* cursor, int32_t* nbr, void* stream);
+int sr_vertex_normals(const float* verts, int64_t N, int64_t V, const int64_t* offsets, const int32_t* nbr, float* normals, void* stream);
+int sr_shade_phong(const float* verts, const float* normals, const int64_t* faces, int64_t N, int64_t V, int64_t F, int32_t H, int32_t W,
+                   const int64_t* pix_to_face, const float* bary, const float* cam_pos, const float* light_loc, const float* host_phong,
+                   float* rgba, void* stream);
+
 /* ---------------------------------------------------------------- fused per-ray / per-vertex tails of one step (csrc/step_ops.hip)
  * Each pair replaces a block of elementwise torch ops of the reference's training step (and their autograd mirror) with one
  * launch for the value and one for the gradient.  Reductions are deterministic (fixed summation order, no float atomics).

@@ -29,7 +29,7 @@ from .. import mlp_engine
 from .. import step_ops
 from ..ext import MCGpu
 from ..ext.FastMinv import Fast3x3Minv
-from ..ops import singular_values_3x3, points_silhouette, rasterize_meshes
+from ..ops import singular_values_3x3, points_silhouette, rasterize_meshes, shade_phong, vertex_adjacency, vertex_normals
 from ..utils import utils as U
 from ..utils.FindSurfacePs import FindSurfacePs, OptimizeSurfacePs
 from .CameraMine import RectifiedPerspectiveCameras
@@ -123,6 +123,8 @@ class OptimNetwork(nn.Module):
         self._ray_ctx = None                  # an open ray branch (EAGER_RAY_BRANCH): closed by propagateTmpPsGrad / the next forward
         self.masked_ray_branch_below = 0      # > 0: with at most this many selected rays the ray branch runs on all of them, masked (see _ray_branch)
         self.ray_valid = None
+        self.shaded_previews = False          # infer also returns the two Phong-shaded previews (imgs, def1imgs): what the reference's
+                                              # infer.py turns on by installing a HardPhongShader (infer.py:89)
         self.next_conf = None                 # set by utils.checkpoint.set_hierarchical_config: the stage switch takes effect at the
         self.next_train_conf = None           # next scheduled remesh (update_hierarchical_config, network.py:172-205,464)
 
@@ -225,7 +227,7 @@ class OptimNetwork(nn.Module):
         (FindSurfacePs), refine it on its ray with the looser inference tolerances (dthreshold 1e-4, 30 steps, chunks of rays),
         then normal -> canonical view direction -> render MLP.  Returns dict(img [N,H,W,3] in [-1,1] (background 1), mask [N,H,W]
         (rasterised silhouette), normal [N,H,W,3] in the image convention the normal loss reads (network.py:626-631: world normal
-        = R [diag(-1,1,-1)] n_img; background 0), converged [N,H,W] bool)."""
+        = R [diag(-1,1,-1)] n_img; background 0), converged [N,H,W] bool, def_verts [N,V,3], frags (the rasterisation))."""
         device = frame_ids.device
         N = frame_ids.numel()
         if TmpVs is None:
@@ -268,18 +270,18 @@ class OptimNetwork(nn.Module):
                 if with_normals:
                     dn, _ = U.compute_deformed_normals(self.sdf, self.deformer, ps_, defconds, bi_, ratio, 'test', cache=jac, onx=nx_raw)
                     nimg[bi_, r_, c_] = dn @ flipRt.t()
-        return {'img': img, 'mask': mask, 'normal': nimg, 'converged': okimg, 'def_verts': defTmpVs}
+        return {'img': img, 'mask': mask, 'normal': nimg, 'converged': okimg, 'def_verts': defTmpVs, 'frags': frags}
 
     def infer(self, TmpVs, Tmpfs, H, W, ratio, frame_ids, notcolor=False, gts=None):
         """Same call as the reference's `infer` (network.py:306-372): (colors, imgs, def1imgs, defMeshVs).  `colors` [N,H,W,3] uint8 is
         the rendering-network image of the deformed template (tanh output mapped from [-1,1] to [0,255], background 255 or
         `gts['image']`), `defMeshVs` the deformed template vertices [N,V,3] (numpy); `gts['maskE']` receives the per-frame mask IoU
-        error of the rasterised silhouette.  `imgs` / `def1imgs` -- the Phong-shaded previews of pytorch3d's mesh renderer -- are not
-        produced (None): third-party shading, outside this path."""
+        error of the rasterised silhouette.  `imgs` / `def1imgs` -- the Phong-shaded previews of pytorch3d's mesh renderer -- are None
+        unless `self.shaded_previews` is set (`_shaded_previews`); they leave the other outputs unchanged."""
         with_color = not notcolor
         if with_color:
             out = self.render_frames(frame_ids, ratio, TmpVs=TmpVs.detach(), Tmpfs=Tmpfs, chunk=10000, dthreshold=1.e-4, times=30, with_normals=False)
-            masks, defV = out['mask'], out['def_verts']
+            masks, defV, frags = out['mask'], out['def_verts'], out['frags']
         else:
             device = frame_ids.device
             N = frame_ids.numel()
@@ -288,20 +290,57 @@ class OptimNetwork(nn.Module):
                 poses, trans, d_cond, _ = [t.detach() for t in self.dataset.get_grad_parameters(frame_ids, device)]
                 defV = self.deformer(TmpVs.detach()[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio)
                 xy, z = cameras.project_ndc(defV)
-                masks = (rasterize_meshes(xy, z, Tmpfs, H, W).pix_to_face[..., 0] >= 0).float()
+                frags = rasterize_meshes(xy, z, Tmpfs, H, W)
+                masks = (frags.pix_to_face[..., 0] >= 0).float()
         N = masks.shape[0]
         if gts:
             gtMs = gts['mask'].to(masks.device)
             gts['maskE'] = (1. - (masks * gtMs).view(N, -1).sum(1) / (masks + gtMs - masks * gtMs).abs().view(N, -1).sum(1)).cpu().numpy()
         defMeshVs = defV.detach().cpu().numpy()
+        imgs = def1imgs = None
+        if self.shaded_previews:
+            imgs, def1imgs = self._shaded_previews(TmpVs.detach(), Tmpfs, ratio, frame_ids, defV.detach(), frags, gts)
         if not with_color:
-            return None, None, None, defMeshVs
+            return None, imgs, def1imgs, defMeshVs
         colors = torch.clamp((out['img'] / 2. + 0.5) * 255., min=0., max=255.)
         covered = masks > 0.
         colors[~covered] = 255.
         if gts and 'image' in gts:
             colors[~covered] = gts['image'].to(colors.device)[~covered][:, :3] * 255.
-        return colors.cpu().numpy().astype(np.uint8), None, None, defMeshVs
+        return colors.cpu().numpy().astype(np.uint8), imgs, def1imgs, defMeshVs
+
+    def _shaded_previews(self, TmpVs, Tmpfs, ratio, frame_ids, defV, frags, gts):
+        """imgs / def1imgs of the reference's infer (network.py:306-337): HardPhongShader with pytorch3d 0.4.0's defaults (ops.shade_phong).
+        imgs: the posed template `defV` as the frame cameras rasterised it into `frags`, light at (0, 1, 0); with `gts`: RGB only, and
+        the background taken from gts['image'] swapped from the dataset's BGR.  def1imgs: the template plus the non-rigid offset (the
+        translator defs[0] alone) seen by a camera with the dataset's intrinsics, R = diag(-1, 1, -1) and T = the mean translation,
+        light at (0, 1, T_z).  Both uint8 of clamp(255 x, 0, 255)."""
+        device = frame_ids.device
+        N = frame_ids.numel()
+        cameras, H, W = self._cameras(N, device)
+        hit = getattr(self, '_preview_adjacency', None)              # (one template serves every batch of an infer loop)
+        if hit is None or hit[0] is not Tmpfs or hit[1] != (Tmpfs._version, TmpVs.shape[0]):
+            hit = self._preview_adjacency = (Tmpfs, (Tmpfs._version, TmpVs.shape[0]), vertex_adjacency(Tmpfs, TmpVs.shape[0]))
+        adj = hit[2]
+        with torch.no_grad():
+            imgs = shade_phong(defV, vertex_normals(defV, Tmpfs, adj), Tmpfs, frags, cameras.cam_pos().detach(), (0., 1., 0.))
+            if gts:
+                imgs = imgs[..., :3]
+                if 'image' in gts:
+                    bg = frags.pix_to_face[..., 0] < 0
+                    imgs[bg] = gts['image'].to(device)[bg][:, [2, 1, 0]]
+            imgs = torch.clamp(imgs * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
+            d_cond = self.dataset.get_grad_parameters(frame_ids, device)[2].detach()
+            canVs = self.deformer.defs[0](TmpVs[None, :, :].expand(N, -1, 3), d_cond, ratio=ratio)
+            focals, princeple_ps = [t.detach() for t in self.dataset.get_camera_parameters(N, device)[:2]]
+            newT = self.dataset.trans.detach().mean(0).to(device)
+            R = torch.tensor([[-1., 0., 0.], [0., 1., 0.], [0., 0., -1.]], device=device)
+            front = RectifiedPerspectiveCameras(focals, princeple_ps, R.expand(N, 3, 3), newT.expand(N, 3), image_size=[(W, H)])
+            xy, z = front.project_ndc(canVs)
+            light = torch.stack([newT.new_zeros(()), newT.new_ones(()), newT[2]])
+            def1imgs = shade_phong(canVs, vertex_normals(canVs, Tmpfs, adj), Tmpfs, rasterize_meshes(xy, z, Tmpfs, H, W), front.cam_pos(), light)
+            def1imgs = torch.clamp(def1imgs * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
+        return imgs, def1imgs
 
     def _cameras(self, N, device):
         # fixed cameras (no learnable parameter) are built once: quaternion -> R and friends are ~40 tiny launches per call

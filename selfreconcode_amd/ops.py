@@ -1,4 +1,7 @@
-"""Autograd faces of the small HIP ops used by the training step."""
+"""Autograd faces of the small HIP ops used by the training step, and the no-grad renderers of infer."""
+import ctypes
+from collections import namedtuple
+
 import torch
 from torch.autograd import Function
 from . import _lib
@@ -100,3 +103,83 @@ def rasterize_meshes(xy_ndc, z, faces, H, W):
         _lib.call("sr_rasterize_meshes", _lib.ptr(xy), _lib.ptr(z), _lib.ptr(faces), N, V, faces.shape[0], H, W, _lib.ptr(zbuf), _lib.ptr(p2f),
                   _lib.ptr(bary), _lib.ptr(zo), _lib.stream_of(xy))
     return Fragments(p2f.unsqueeze(-1), bary.unsqueeze(3), zo.unsqueeze(-1))
+
+
+# ------------------------------------------------------------------ shaded previews of infer (csrc/shade.hip)
+# pytorch3d 0.4.0 defaults of the HardPhongShader the reference's infer.py installs: PointLights (ambient 0.5, diffuse 0.3, specular 0.2
+# per channel; location (0, 1, 0)), Materials (all colours 1, shininess 64), BlendParams (background (1, 1, 1)).  Restated, unpinned.
+PHONG_AMBIENT, PHONG_DIFFUSE, PHONG_SPECULAR, PHONG_SHININESS = (0.5,) * 3, (0.3,) * 3, (0.2,) * 3, 64.
+PHONG_BACKGROUND = (1., 1., 1.)
+PHONG_LIGHT = (0., 1., 0.)
+
+VertexAdjacency = namedtuple("VertexAdjacency", "offsets nbr V F")
+
+
+def _faces(faces):
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"faces [F,3] expected, got {tuple(faces.shape)}")
+    return faces.long().contiguous()                 # (the kernels read int64 rows)
+
+
+def _verts(verts):
+    if verts.dim() != 3 or verts.shape[2] != 3:
+        raise ValueError(f"verts [N,V,3] expected, got {tuple(verts.shape)}")
+    return verts.detach().contiguous().float()
+
+
+def vertex_adjacency(faces, V):
+    """The vertex -> (face, corner) lists of a template (sr_vertex_adjacency), built once and reused for every batch of deformed
+    copies: `vertex_normals(verts, faces, adjacency)`."""
+    _lib.require_gpu(faces)
+    faces = _faces(faces)
+    F, dev = faces.shape[0], faces.device
+    offsets = torch.empty((V + 1,), dtype=torch.int64, device=dev)
+    nbr = torch.empty((3 * F, 2), dtype=torch.int32, device=dev)
+    cursor = torch.empty((V,), dtype=torch.int32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("sr_vertex_adjacency", _lib.ptr(faces), V, F, _lib.ptr(offsets), _lib.ptr(cursor), _lib.ptr(nbr), _lib.stream_of(faces))
+    return VertexAdjacency(offsets, nbr, V, F)
+
+
+def vertex_normals(verts, faces, adjacency=None):
+    """Unit vertex normals [N,V,3] of N deformed copies verts [N,V,3] of the template `faces` -- pytorch3d's
+    Meshes.verts_normals_packed (faces with a -1 skipped), summed in a fixed order: bit-reproducible.  No autograd."""
+    _lib.require_gpu(verts)
+    v = _verts(verts)
+    N, V = v.shape[0], v.shape[1]
+    adj = adjacency if adjacency is not None else vertex_adjacency(faces, V)
+    if adj.V != V or adj.F != faces.shape[0]:
+        raise ValueError(f"vertex_normals: adjacency of a {adj.V}-vertex / {adj.F}-face template for {V} vertices / {faces.shape[0]} faces")
+    out = torch.empty_like(v)
+    with _lib.on_device(v.device):
+        _lib.call("sr_vertex_normals", _lib.ptr(v), N, V, _lib.ptr(adj.offsets), _lib.ptr(adj.nbr), _lib.ptr(out), _lib.stream_of(v))
+    return out
+
+
+def _per_image(x, N, dev):
+    return torch.as_tensor(x, dtype=torch.float32).to(dev).reshape(-1, 3).expand(N, 3).contiguous()
+
+
+def shade_phong(verts, normals, faces, frags, cam_pos, light_loc=PHONG_LIGHT, ambient=PHONG_AMBIENT, diffuse=PHONG_DIFFUSE,
+                specular=PHONG_SPECULAR, shininess=PHONG_SHININESS, background=PHONG_BACKGROUND):
+    """RGBA [N,H,W,4] of pytorch3d 0.4.0's HardPhongShader (phong_shading + hard_rgb_blend, TexturesVertex of ones) on the fragments
+    of `rasterize_meshes` (verts, normals [N,V,3]; cam_pos, light_loc [3] or [N,3], world space).  Colours are the light's times the
+    material's.  Alpha is 1 (unpinned, see sr_shade_phong).  No autograd."""
+    _lib.require_gpu(verts)
+    p2f = frags.pix_to_face[..., 0].long().contiguous()
+    bary = frags.bary_coords[..., 0, :].contiguous().float()
+    N, H, W = p2f.shape
+    if bary.shape != (N, H, W, 3):
+        raise ValueError(f"shade_phong: bary_coords {tuple(frags.bary_coords.shape)} for pix_to_face {tuple(frags.pix_to_face.shape)}")
+    _require_square(H, W, "shade_phong")
+    v = _verts(verts); n = normals.detach().contiguous().float(); faces = _faces(faces)
+    if v.shape[0] != N or n.shape != v.shape:
+        raise ValueError(f"shade_phong: verts {tuple(v.shape)} / normals {tuple(n.shape)} for {N} images")
+    dev = v.device
+    cam, light = _per_image(cam_pos, N, dev), _per_image(light_loc, N, dev)
+    coeffs = (ctypes.c_float * 13)(*[float(c) for c in (*ambient, *diffuse, *specular, shininess, *background)])
+    rgba = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("sr_shade_phong", _lib.ptr(v), _lib.ptr(n), _lib.ptr(faces), N, v.shape[1], faces.shape[0], H, W, _lib.ptr(p2f), _lib.ptr(bary),
+                  _lib.ptr(cam), _lib.ptr(light), coeffs, _lib.ptr(rgba), _lib.stream_of(v))
+    return rgba
