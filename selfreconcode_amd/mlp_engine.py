@@ -17,8 +17,10 @@ all the derivative orders the reference reaches through autograd:
     over a 1-tangent forward).  Cotangents on dW/db (third-party code differentiating parameter
     gradients) are not supported -- the reference never does that.
 """
-import math
+import collections
+import contextlib
 import ctypes
+import math
 import os
 import weakref
 import torch
@@ -27,6 +29,34 @@ from . import _lib
 
 ACT_NONE, ACT_SOFTPLUS100, ACT_RELU = 0, 1, 2
 EPI_FWD, EPI_BWD = 0, 1
+
+# Weight-gradient GEMMs on a stream of their own.  In a reverse sweep dW_l = Zbar_l^T X_{l-1} and the backward-data GEMM
+# Zbar_{l-1} = (Zbar_l W_l) . act' depend on the same Zbar_l and on nothing of each other; on one stream they alternate, every launch
+# drains the machine before the next one fills it (the last partial wave of 128x128 tiles of an 85k-row batch leaves ~5 % of a launch
+# idle, plus the launch gap).  With the weight gradients on a second stream the backward-data chain is the critical path and the
+# weight-gradient workgroups fill its tails.  Only in deferred mode (the results land in the per-layer buffers, nobody reads them
+# before flush_param_grads, which joins the stream); all weight-gradient launches share ONE stream, so the accumulation order into
+# a buffer is the program order -- results are bit-identical to the one-stream schedule.
+TN_SIDE_STREAM = True          # (module attribute: tests compare the one- and two-stream schedules bit for bit)
+GROUP_TN_BELOW = 16384         # rows: the weight gradients of a reverse sweep on fewer rows than this go out as ONE grouped launch (0 = never)
+DEBUG_TN_DELAY_MS = int(os.environ.get("SR_DEBUG_TN_DELAY_MS", "0"))      # race amplifier: hold the weight-gradient stream before every launch
+_TN_STREAMS = {}               # device -> the weight-gradient stream
+_TN_PENDING = set()            # devices whose weight-gradient stream has launches nobody has waited for yet
+_DELAY_FLAG = {}
+
+# Deferred parameter gradients (opt-in, used by the training step): every weight-gradient GEMM adds
+# into ONE persistent buffer per layer instead of returning a tensor that autograd then pushes through
+# a weight-norm backward and an AccumulateGrad add for each of the ~30 network uses per iteration.
+# `flush_param_grads()` runs the weight-norm backward once per layer and adds into the parameters'
+# .grad; OptimNetwork.propagateTmpPsGrad (the last gradient producer of a step) calls it.
+DEFERRED_PARAM_GRADS = False
+
+# The pack registry: one `_Pack` per weight parameter, found by the parameter and by the pointer of the packed weight.
+# Only _pack_entry (registration, replacement) and _drop_entry (removal) edit the two maps.
+_PACK_CACHE = {}               # id(weight_v or weight) -> _Pack
+_ENTRY_BY_PTR = {}             # data_ptr of a packed W -> the same _Pack
+
+_INPUT_GRADS_ONLY = False
 
 
 def pad4(n):
@@ -72,24 +102,27 @@ class MLPSpec:
         return MLPSpec(layers, K0)
 
 
+# ------------------------------------------------------------------------------------------------
+# Launch helpers and the optional timing of every layer-GEMM launch.
+_GemmRecord = collections.namedtuple("_GemmRecord", "e0 e1 flop rows overlap N K mode group")
+
+
 class _GemmProfile:
     """Optional HIP-event timing of every layer-GEMM launch on the launching stream (bench.py's roofline
     leg): achieved = sum(2 M N K) / sum(event time).  Off by default: zero overhead in the product path."""
 
     def __init__(self):
-        self.enabled = False
-        self.records = []
-        self.pool = []
         self.overlap = False      # set by OptimNetwork.forward while two streams feed the GPU: an event pair then brackets a kernel
                                   # that shares the machine with the other stream's kernels, not a kernel's own duration
+        self.reset(enabled=False)
 
     def reset(self, enabled, reserve=0):
         """`reserve` event pairs are created (and recorded once, which is what allocates the HIP event) ahead of time, so that
         inside the measured region a pair costs two hipEventRecord calls and nothing else."""
         self.enabled = enabled
-        self.records = []
-        self.chains = []          # persistent layer-chain launches of the refiner: ([(e0, e1, phase, flop per row)], live counts, overlap flag)
-        self.pool = []
+        # records: a _GemmRecord per timed launch; chains: the persistent layer-chain launches of the refiner, one
+        # ([(e0, e1, phase, flop per row)], live counts, overlap flag) per refiner call; pool: event pairs ready for use
+        self.records, self.chains, self.pool = [], [], []
         for _ in range(reserve if enabled else 0):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(); e1.record()
@@ -98,6 +131,22 @@ class _GemmProfile:
     def pair(self):
         return self.pool.pop() if self.pool else (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
 
+    def launch(self, name, args, stream, timed=True, what=None, marks=None):
+        """The ABI call `name(&args, stream)`; when enabled and `timed`, between an event pair that goes into a record of `what` = (rows, N,
+        K, mode, group) -- or, with `what` as it is, into the list `marks`: a launch whose row count only the device knows (see `chains`)."""
+        if not (timed and self.enabled):
+            _lib.call(name, ctypes.byref(args), stream)
+            return
+        e0, e1 = self.pair()
+        e0.record()
+        _lib.call(name, ctypes.byref(args), stream)
+        e1.record()
+        if marks is not None:
+            marks.append((e0, e1) + what)
+        else:
+            rows, N, K, mode, group = what
+            self.records.append(_GemmRecord(e0, e1, 2.0 * rows * N * K, rows, self.overlap, N, K, mode, group))
+
     def summary(self):
         if not self.records:
             return {"tflops": 0.0, "launches": 0, "avg_us": 0.0, "avg_flop": 0.0}
@@ -105,25 +154,25 @@ class _GemmProfile:
         for marks, live, overlap in self.chains:          # fold the chain launches in as records: FLOPs from the device-side row counts
             lv = live.tolist()
             for e0, e1, phase, fpr in marks:
-                self.records.append((e0, e1, fpr * lv[phase], lv[phase], overlap, (0, 0, "chain", 1)))
+                self.records.append(_GemmRecord(e0, e1, fpr * lv[phase], lv[phase], overlap, 0, 0, "chain", 1))
         self.chains = []
-        times = [r[0].elapsed_time(r[1]) for r in self.records]
+        times = [r.e0.elapsed_time(r.e1) for r in self.records]
 
         def rate(sel):
-            f = sum(r[2] for r, t, k in zip(self.records, times, sel) if k)
+            f = sum(r.flop for r, t, k in zip(self.records, times, sel) if k)
             ms = sum(t for t, k in zip(times, sel) if k)
             n = sum(1 for k in sel if k)
             return (f / (ms * 1e-3) / 1e12 if ms > 0 else 0.0), n, (ms * 1e3 / n if n else 0.0), (f / n if n else 0.0)
 
-        nt = [r[5][2] != "tn" for r in self.records]                  # the NT tile code (forward / backward-data GEMMs, refiner chains)
-        alone = [k and not r[4] for k, r in zip(nt, self.records)]
+        nt = [r.mode != "tn" for r in self.records]                   # the NT tile code (forward / backward-data GEMMs, refiner chains)
+        alone = [k and not r.overlap for k, r in zip(nt, self.records)]
         tf, n, us, fl = rate(alone)                                   # launches that had the GPU to themselves
         tf_all, n_all, us_all, _ = rate(nt)
-        tf_big, n_big, _, _ = rate([a and r[3] >= 65536 for a, r in zip(alone, self.records)])
+        tf_big, n_big, _, _ = rate([a and r.rows >= 65536 for a, r in zip(alone, self.records)])
         tf_tn, n_tn, us_tn, _ = rate([not k for k in nt])             # the weight-gradient (TN) kernel + slab reduction
         self._times = times
-        f_nt = float(sum(r[2] for r, k in zip(self.records, nt) if k))
-        f_tn = float(sum(r[2] for r, k in zip(self.records, nt) if not k))
+        f_nt = float(sum(r.flop for r, k in zip(self.records, nt) if k))
+        f_tn = float(sum(r.flop for r, k in zip(self.records, nt) if not k))
         return {"tflops": round(tf, 3), "launches": n, "avg_us": round(us, 3), "avg_flop": round(fl, 1), "tflops_large": round(tf_big, 3),
                 "launches_large": n_big, "tflops_all": round(tf_all, 3), "launches_all": n_all, "avg_us_all": round(us_all, 3),
                 "avg_flop_all": round(f_nt / max(n_all, 1), 1), "flops_total": f_nt, "flops_total_tn": f_tn,
@@ -134,12 +183,11 @@ class _GemmProfile:
         the roofline figure reproducible next to the rocprof kernel trace (tools/summarize_profile.py joins the two)."""
         if not self.records:
             return []
-        times = getattr(self, "_times", None) or [r[0].elapsed_time(r[1]) for r in self.records]
+        times = getattr(self, "_times", None) or [r.e0.elapsed_time(r.e1) for r in self.records]
         acc = {}
         for r, t in zip(self.records, times):
-            key = (r[3],) + tuple(r[5]) + (bool(r[4]),)
-            a = acc.setdefault(key, [0, 0.0, 0.0])
-            a[0] += 1; a[1] += r[2]; a[2] += t
+            a = acc.setdefault((r.rows, r.N, r.K, r.mode, r.group, bool(r.overlap)), [0, 0.0, 0.0])
+            a[0] += 1; a[1] += r.flop; a[2] += t
         rows = [{"M": k[0], "N": k[1], "K": k[2], "mode": k[3], "group": k[4], "overlap": k[5], "launches": v[0], "flop": v[1], "ms": round(v[2], 4),
                  "tflops": round(v[1] / (v[2] * 1e-3) / 1e12, 2) if v[2] > 0 else 0.0} for k, v in acc.items()]
         rows.sort(key=lambda r: -r["ms"])
@@ -148,49 +196,55 @@ class _GemmProfile:
 
 PROFILE = _GemmProfile()
 
-def _gemm_nt(A, lda, B, ldb, C, ldc, M, N, K, bias, group, act, mode, out_scale=1.0, aux=None, ldaux=0, naux_fwd=0,
-             nact_bwd=0, aux_scale=1.0):
-    a = _lib.SrGemmArgs()
-    a.A, a.lda, a.B, a.ldb, a.C, a.ldc = _lib.ptr(A), lda, _lib.ptr(B), ldb, _lib.ptr(C), ldc
+
+def set_gemm_args(a, A, B, C, M, N, K, bias, group, act, mode, out_scale=1.0, aux=None, naux_fwd=0, nact_bwd=0, aux_scale=1.0, pitches=None):
+    """Fills the SrGemmArgs `a`.  `pitches` = (lda, ldb, ldc, ldaux) where the caller states them (_gemm_nt), else the row strides of the
+    matrices.  M = 0: the row count comes from the device (the refiner's layer chains)."""
+    lda, ldb, ldc, ldaux = pitches or (A.stride(0), B.stride(0), C.stride(0), 0 if aux is None else aux.stride(0))
+    a.A, a.lda, a.B, a.ldb, a.C, a.ldc = A.data_ptr(), lda, B.data_ptr(), ldb, C.data_ptr(), ldc
     a.M, a.N, a.K = M, N, K
     a.bias = _lib.ptr(bias)
     a.group, a.act, a.mode, a.out_scale = group, act, mode, out_scale
     a.aux, a.ldaux, a.naux_fwd, a.nact_bwd, a.aux_scale = _lib.ptr(aux), ldaux, naux_fwd, nact_bwd, aux_scale
-    if PROFILE.enabled and M >= 128 and N > 32:      # the 128x128-tile kernel only
-        e0, e1 = PROFILE.pair()
-        e0.record()
-        _lib.call("sr_mlp_gemm_nt", ctypes.byref(a), _lib.stream_of(C))
-        e1.record()
-        PROFILE.records.append((e0, e1, 2.0 * M * N * K, M, PROFILE.overlap, (N, K, mode, group)))
-        return
-    _lib.call("sr_mlp_gemm_nt", ctypes.byref(a), _lib.stream_of(C))
+
+
+def _gemm_nt(A, lda, B, ldb, C, ldc, M, N, K, bias, group, act, mode, out_scale=1.0, aux=None, ldaux=0, naux_fwd=0,
+             nact_bwd=0, aux_scale=1.0):
+    a = _lib.SrGemmArgs()
+    set_gemm_args(a, A, B, C, M, N, K, bias, group, act, mode, out_scale, aux, naux_fwd, nact_bwd, aux_scale, (lda, ldb, ldc, ldaux))
+    PROFILE.launch("sr_mlp_gemm_nt", a, _lib.stream_of(C), M >= 128 and N > 32, (M, N, K, mode, group))     # (timed: the 128x128-tile kernel only)
+
+
+# One weight-gradient problem: dW [N, lddw] (+)= Z[:, :N]^T A[:, :K], db [N] (+)= sum of the primal rows of Z.
+_TnProblem = collections.namedtuple("_TnProblem", "Z ldz A lda R N K lddw group dW db accumulate")
+
+
+def _tn_workspace(R, N, lddw):
+    """-> (floats of the partial dW slabs, at least 1; row splits).  A problem's workspace is that many floats + splits * N for db."""
+    splits = ctypes.c_int32(0)
+    ws = _lib.raw("sr_mlp_gemm_tn_workspace_floats")(R, N, lddw, ctypes.byref(splits))
+    return max(int(ws), 1), splits.value
+
+
+def _set_tn_args(a, Z, ldz, A, lda, R, N, K, lddw, group, dW, db, accumulate, partial, ws, splits):
+    """Fills the SrGemmTnArgs `a` from the fields of a _TnProblem and its workspace: `partial` = address of ws + splits * N floats."""
+    a.Z, a.ldz, a.A, a.lda, a.dW, a.lddw, a.partial = Z.data_ptr(), ldz, A.data_ptr(), lda, dW.data_ptr(), lddw, partial
+    a.R, a.N, a.K, a.splits, a.accumulate = R, N, K, splits, 1 if accumulate else 0
+    a.db, a.db_partial, a.group = db.data_ptr(), partial + 4 * ws, group
 
 
 def _gemm_tn(Z, ldz, A, lda, R, N, K, lddw, group=1, dW=None, db=None, accumulate=False):
     """dW [N, lddw] (+)= Z[:, :N]^T A[:, :K] and db [N] (+)= sum of the primal rows of Z (deterministic slab reductions)."""
-    splits = ctypes.c_int32(0)
-    ws = _lib.raw("sr_mlp_gemm_tn_workspace_floats")(R, N, lddw, ctypes.byref(splits))
+    ws, splits = _tn_workspace(R, N, lddw)
     if dW is None:
         dW = torch.empty((N, lddw), dtype=torch.float32, device=Z.device)
-    partial = torch.empty((max(int(ws), 1) + splits.value * N,), dtype=torch.float32, device=Z.device)
+    partial = torch.empty((ws + splits * N,), dtype=torch.float32, device=Z.device)
     if db is None:
         db = torch.empty((N,), dtype=torch.float32, device=Z.device)
     a = _lib.SrGemmTnArgs()
-    a.Z, a.ldz, a.A, a.lda, a.dW, a.lddw, a.partial = _lib.ptr(Z), ldz, _lib.ptr(A), lda, _lib.ptr(dW), lddw, _lib.ptr(partial)
-    a.R, a.N, a.K, a.splits, a.accumulate = R, N, K, splits.value, 1 if accumulate else 0
-    a.db, a.db_partial, a.group = _lib.ptr(db), _lib.ptr(partial) + 4 * max(int(ws), 1), group
-    if PROFILE.enabled and R >= 128 and N > 32:        # weight-gradient GEMM + its slab reduction, as one interval
-        e0, e1 = PROFILE.pair()
-        e0.record()
-        _lib.call("sr_mlp_gemm_tn", ctypes.byref(a), _lib.stream_of(Z))
-        e1.record()
-        PROFILE.records.append((e0, e1, 2.0 * R * N * K, R, PROFILE.overlap, (N, K, "tn", group)))
-        return dW, db
-    _lib.call("sr_mlp_gemm_tn", ctypes.byref(a), _lib.stream_of(Z))
+    _set_tn_args(a, Z, ldz, A, lda, R, N, K, lddw, group, dW, db, accumulate, partial.data_ptr(), ws, splits)
+    PROFILE.launch("sr_mlp_gemm_tn", a, _lib.stream_of(Z), R >= 128 and N > 32, (R, N, K, "tn", group))     # (timed with its slab reduction, as one interval)
     return dW, db
-
-
-GROUP_TN_BELOW = 16384     # rows: the weight gradients of a reverse sweep on fewer rows than this go out as ONE grouped launch (0 = never)
 
 
 def _tn_is_narrow(N, lddw):
@@ -201,32 +255,79 @@ def _gemm_tn_group(problems):
     """`problems`: list of (Z, ldz, A, lda, R, N, K, lddw, group, dW, db, accumulate) with distinct dW / db -- the weight gradients of
     one reverse sweep.  One launch for all tiles and slabs + one for all slab reductions (sr_mlp_gemm_tn_group); each problem is computed
     exactly as `_gemm_tn` would compute it alone: same splits, same slab order, bit-identical results."""
+    problems = [_TnProblem(*p) for p in problems]
     g = _lib.SrGemmTnGroupArgs()
     g.n = len(problems)
     sizes, total = [], 0
-    for (Z, ldz, A, lda, R, N, K, lddw, group, dW, db, accumulate) in problems:
-        splits = ctypes.c_int32(0)
-        ws = max(int(_lib.raw("sr_mlp_gemm_tn_workspace_floats")(R, N, lddw, ctypes.byref(splits))), 1)
-        sizes.append((ws, splits.value, total))
-        total += (ws + splits.value * N + 3) // 4 * 4                     # (every problem's partial block stays 16-byte aligned)
-    partial = torch.empty((total,), dtype=torch.float32, device=problems[0][0].device)
-    for a, (Z, ldz, A, lda, R, N, K, lddw, group, dW, db, accumulate), (ws, splits, off) in zip(g.p, problems, sizes):
-        a.Z, a.ldz, a.A, a.lda, a.dW, a.lddw, a.partial = _lib.ptr(Z), ldz, _lib.ptr(A), lda, _lib.ptr(dW), lddw, _lib.ptr(partial) + 4 * off
-        a.R, a.N, a.K, a.splits, a.accumulate = R, N, K, splits, 1 if accumulate else 0
-        a.db, a.db_partial, a.group = _lib.ptr(db), _lib.ptr(partial) + 4 * (off + ws), group
+    for p in problems:
+        ws, splits = _tn_workspace(p.R, p.N, p.lddw)
+        sizes.append((ws, splits, total))
+        total += (ws + splits * p.N + 3) // 4 * 4                         # (every problem's partial block stays 16-byte aligned)
+    partial = torch.empty((total,), dtype=torch.float32, device=problems[0].Z.device)
+    for a, p, (ws, splits, off) in zip(g.p, problems, sizes):
+        _set_tn_args(a, *p, partial.data_ptr() + 4 * off, ws, splits)
     _lib.call("sr_mlp_gemm_tn_group", ctypes.byref(g), _lib.stream_of(partial))
 
 
-def _colsum(Z, ldz, R, N, group):
-    out = torch.zeros((N,), dtype=torch.float32, device=Z.device)
-    _lib.call("sr_colsum_rows", _lib.ptr(Z), ldz, R, N, group, _lib.ptr(out), _lib.stream_of(Z))
-    return out
+def _debug_delay(device, ms):
+    f = _DELAY_FLAG.get(str(device))
+    if f is None:
+        f = _DELAY_FLAG[str(device)] = torch.zeros(2, dtype=torch.int32, device=device)
+    _lib.call('sr_stream_flag_wait', f.data_ptr(), 0x40000000, 0, ms, torch.cuda.current_stream(device).cuda_stream)
 
 
+def _tn_stream(device):
+    key = str(device)
+    st = _TN_STREAMS.get(key)
+    if st is None:
+        st = _TN_STREAMS[key] = torch.cuda.Stream(device=device)
+    return st
+
+
+def _launch_on_tn_stream(device, problems):
+    """ONE launch for `problems` (_TnProblem, distinct dW / db) on the weight-gradient stream of `device`, which first waits for what the
+    current stream has enqueued: every Zbar of the problems (and, for a partial first use, the zeroed buffers) is final there."""
+    main, side = torch.cuda.current_stream(device), _tn_stream(device)
+    ready = torch.cuda.Event()
+    ready.record(main)
+    side.wait_event(ready)
+    with torch.cuda.stream(side):
+        if DEBUG_TN_DELAY_MS:
+            _debug_delay(device, DEBUG_TN_DELAY_MS)
+        if len(problems) == 1:                                 # (the group of one goes out as the plain kernel)
+            p = problems[0]
+            _gemm_tn(*p[:9], dW=p.dW, db=p.db, accumulate=p.accumulate)
+        else:
+            _gemm_tn_group(problems)
+    for p in problems:
+        p.Z.record_stream(side); p.A.record_stream(side)      # both may be freed by the main stream's owner before the side stream has read them
+    _TN_PENDING.add(str(device))
+
+
+def join_weight_gradient_stream():
+    """The current stream of every device with outstanding weight-gradient launches waits for them."""
+    for key in list(_TN_PENDING):
+        st = _TN_STREAMS[key]
+        torch.cuda.current_stream(st.device).wait_stream(st)
+    _TN_PENDING.clear()
+
+
+# ------------------------------------------------------------------------------------------------
+# The layer loops.
 def _check_mat(t, name):
     if t.dtype != torch.float32 or not t.is_cuda or t.dim() != 2 or t.stride(1) != 1 or (t.stride(0) % 4) or (t.data_ptr() % 16):
         raise RuntimeError(f"mlp_engine: {name} must be a GPU fp32 matrix with unit column stride, row pitch % 4 == 0 "
                            f"and 16-byte alignment (got {tuple(t.shape)}, strides {t.stride()}, {t.dtype}, {t.device})")
+
+
+def _bias_segments(b0, R, group):
+    """-> (S, rows per segment) when the first-layer bias is a matrix [S, N_0] (row segment s of the batch uses bias row s), else None."""
+    if b0 is None or b0.dim() != 2:
+        return None
+    S = b0.shape[0]
+    if S < 1 or R % S or (R // S) % group or b0.stride(1) != 1:
+        raise RuntimeError(f"mlp_engine: segmented first-layer bias {tuple(b0.shape)} does not divide {R} rows of group {group}")
+    return S, R // S
 
 
 def forward(spec, A0, Ws, bs, group):
@@ -257,55 +358,31 @@ def forward(spec, A0, Ws, bs, group):
     return acts
 
 
-def _bias_segments(b0, R, group):
-    """-> (S, rows per segment) when the first-layer bias is a matrix [S, N_0] (row segment s of the batch uses bias row s), else None."""
-    if b0 is None or b0.dim() != 2:
-        return None
-    S = b0.shape[0]
-    if S < 1 or R % S or (R // S) % group or b0.stride(1) != 1:
-        raise RuntimeError(f"mlp_engine: segmented first-layer bias {tuple(b0.shape)} does not divide {R} rows of group {group}")
-    return S, R // S
+# Where the weight gradient of one layer of a reverse sweep goes.
+_DW_GROUPED, _DW_SIDE, _DW_SINK, _DW_SEGMENTED, _DW_AUTOGRAD = range(5)
 
 
-# Weight-gradient GEMMs on a stream of their own.  In a reverse sweep dW_l = Zbar_l^T X_{l-1} and the backward-data GEMM
-# Zbar_{l-1} = (Zbar_l W_l) . act' depend on the same Zbar_l and on nothing of each other; on one stream they alternate, every launch
-# drains the machine before the next one fills it (the last partial wave of 128x128 tiles of an 85k-row batch leaves ~5 % of a launch
-# idle, plus the launch gap).  With the weight gradients on a second stream the backward-data chain is the critical path and the
-# weight-gradient workgroups fill its tails.  Only in deferred mode (the results land in the per-layer buffers, nobody reads them
-# before flush_param_grads, which joins the stream); all weight-gradient launches share ONE stream, so the accumulation order into
-# a buffer is the program order -- results are bit-identical to the one-stream schedule.
-TN_SIDE_STREAM = True          # (module attribute: tests compare the one- and two-stream schedules bit for bit)
-# (Row slabs of the deferred weight-gradient launches: all of them, two workgroups per CU -- since round 5 the weight-gradient stream is
-# what the tail of the big backward waits for; rounds 3-4 ran half the count.)
-_TN_STREAMS = {}
-_TN_PENDING = set()
-
-
-DEBUG_TN_DELAY_MS = int(os.environ.get("SR_DEBUG_TN_DELAY_MS", "0"))      # race amplifier: hold the weight-gradient stream before every launch
-_DELAY_FLAG = {}
-
-
-def _debug_delay(device, ms):
-    f = _DELAY_FLAG.get(str(device))
-    if f is None:
-        f = _DELAY_FLAG[str(device)] = torch.zeros(2, dtype=torch.int32, device=device)
-    _lib.call('sr_stream_flag_wait', f.data_ptr(), 0x40000000, 0, ms, torch.cuda.current_stream(device).cuda_stream)
-
-
-def _tn_stream(device):
-    key = str(device)
-    st = _TN_STREAMS.get(key)
-    if st is None:
-        st = _TN_STREAMS[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-def join_weight_gradient_stream():
-    """The current stream of every device with outstanding weight-gradient launches waits for them."""
-    for key in list(_TN_PENDING):
-        st = _TN_STREAMS[key]
-        torch.cuda.current_stream(st.device).wait_stream(st)
-    _TN_PENDING.clear()
+def _weight_gradient_route(l, L, Ws, bs, seg, grouped):
+    """-> (route, sink) for layer `l`.  With a `sink` = (dW buffer, db buffer, accumulate) of deferred mode the gradient is added there: in one
+    launch with the sweep's other small problems (collected in `grouped`) or alone on the weight-gradient stream, or on the current stream.
+    Without one it is returned to autograd; a first layer with one bias row per row segment then takes one launch per segment."""
+    segmented = l == 0 and seg is not None
+    sink = None
+    if DEFERRED_PARAM_GRADS and Ws is not None:
+        if not segmented:
+            sink = _deferred_sink(Ws[l], bs[l])
+        if sink is None and not Ws[l].requires_grad:
+            e = _ENTRY_BY_PTR.get(Ws[l].data_ptr())
+            if e is not None and any(r() is not None and r().requires_grad for r in e.src):
+                raise RuntimeError("mlp_engine: a packed weight handed out without autograd node (deferred mode) met a layer call "
+                                   "that has no deferred sink (bias that is not the layer's own leaf parameter?): its gradient would be lost")
+    if sink is None:
+        return (_DW_SEGMENTED if segmented else _DW_AUTOGRAD), None
+    if grouped is not None and not _tn_is_narrow(L.N, pad4(L.K)) and len(grouped) < _lib.SR_TN_GROUP_MAX:
+        return _DW_GROUPED, sink
+    if TN_SIDE_STREAM and not PROFILE.enabled:
+        return _DW_SIDE, sink
+    return _DW_SINK, sink
 
 
 def reverse(spec, A0, WTs, acts, Ybar, group, need_input_grad=True, need_param_grad=True, Ws=None, bs=None):
@@ -320,37 +397,25 @@ def reverse(spec, A0, WTs, acts, Ybar, group, need_input_grad=True, need_param_g
     A0bar = None
     seg = _bias_segments(bs[0], R, group) if bs is not None else None
     # weight gradients of a SMALL sweep (deferred mode, their own stream): collected here and launched as one group after the last layer --
-    # each is < 100 workgroups that end before the next starts (26 launches per iteration at 27 TFLOP/s in round 5)
+    # each is < 100 workgroups that end before the next starts (26 launches per iteration at 27 TFLOP/s when launched one by one)
     grouped = [] if (0 < R < GROUP_TN_BELOW and TN_SIDE_STREAM and not PROFILE.enabled) else None
     with _lib.on_device(A0.device):
         for l in range(nl - 1, -1, -1):
             L = spec.layers[l]
             X = A0 if l == 0 else acts[l - 1]
             if need_param_grad:
-                sink = _deferred_sink(Ws[l], bs[l]) if (DEFERRED_PARAM_GRADS and Ws is not None and not (l == 0 and seg is not None)) else None
-                if sink is None and DEFERRED_PARAM_GRADS and Ws is not None and not Ws[l].requires_grad:
-                    e = _ENTRY_BY_PTR.get(Ws[l].data_ptr())
-                    if e is not None and any(r() is not None and r().requires_grad for r in e.get("src", ())):
-                        raise RuntimeError("mlp_engine: a packed weight handed out without autograd node (deferred mode) met a layer call "
-                                           "that has no deferred sink (bias that is not the layer's own leaf parameter?): its gradient would be lost")
-                if sink is not None and grouped is not None and not _tn_is_narrow(L.N, pad4(L.K)) and len(grouped) < _lib.SR_TN_GROUP_MAX:
-                    grouped.append((Zbar, Zbar.stride(0), X, X.stride(0), R, L.N, L.K, pad4(L.K), group, sink[0], sink[1], sink[2]))
-                elif sink is not None and TN_SIDE_STREAM and not PROFILE.enabled:
-                    main, side = torch.cuda.current_stream(A0.device), _tn_stream(A0.device)
-                    ready = torch.cuda.Event()
-                    ready.record(main)                                   # Zbar (and, for a partial first use, the zeroed buffers) are final here
-                    side.wait_event(ready)
-                    with torch.cuda.stream(side):
-                        if DEBUG_TN_DELAY_MS:
-                            _debug_delay(A0.device, DEBUG_TN_DELAY_MS)
-                        _gemm_tn(Zbar, Zbar.stride(0), X, X.stride(0), R, L.N, L.K, pad4(L.K), group, dW=sink[0], db=sink[1], accumulate=sink[2])
-                    Zbar.record_stream(side); X.record_stream(side)      # both may be freed by the main stream's owner before the side stream has read them
-                    _TN_PENDING.add(str(A0.device))
-                elif sink is not None:        # accumulate straight into the per-step gradient buffers (no autograd traffic)
-                    _gemm_tn(Zbar, Zbar.stride(0), X, X.stride(0), R, L.N, L.K, pad4(L.K), group, dW=sink[0], db=sink[1], accumulate=sink[2])
-                elif l == 0 and seg is not None:
-                    # segmented first-layer bias: the weight gradient is the sum over the segments (accumulated launch by launch, in
-                    # segment order), the bias gradient one row per segment
+                route, sink = _weight_gradient_route(l, L, Ws, bs, seg, grouped)
+                if sink is not None:
+                    p = _TnProblem(Zbar, Zbar.stride(0), X, X.stride(0), R, L.N, L.K, pad4(L.K), group, *sink)
+                    if route == _DW_GROUPED:
+                        grouped.append(p)
+                    elif route == _DW_SIDE:
+                        _launch_on_tn_stream(A0.device, [p])
+                    else:                     # accumulate straight into the per-step gradient buffers (no autograd traffic)
+                        _gemm_tn(*p[:9], dW=p.dW, db=p.db, accumulate=p.accumulate)
+                elif route == _DW_SEGMENTED:
+                    # the weight gradient is the sum over the segments (accumulated launch by launch, in segment order), the bias
+                    # gradient one row per segment
                     S, rs = seg
                     dWs[0] = torch.empty((L.N, pad4(L.K)), dtype=torch.float32, device=A0.device)
                     dbs[0] = torch.zeros((S, L.N), dtype=torch.float32, device=A0.device)
@@ -375,21 +440,7 @@ def reverse(spec, A0, WTs, acts, Ybar, group, need_input_grad=True, need_param_g
                 if A0bar_extra is not None:
                     A0bar[:, :A0bar_extra.shape[1]] += A0bar_extra
         if grouped:
-            main, side = torch.cuda.current_stream(A0.device), _tn_stream(A0.device)
-            ready = torch.cuda.Event()
-            ready.record(main)                                           # every Zbar of the sweep is final here
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                if DEBUG_TN_DELAY_MS:
-                    _debug_delay(A0.device, DEBUG_TN_DELAY_MS)
-                if len(grouped) == 1:
-                    p = grouped[0]
-                    _gemm_tn(*p[:9], dW=p[9], db=p[10], accumulate=p[11])
-                else:
-                    _gemm_tn_group(grouped)
-            for p in grouped:
-                p[0].record_stream(side); p[2].record_stream(side)
-            _TN_PENDING.add(str(A0.device))
+            _launch_on_tn_stream(A0.device, grouped)
     return A0bar, dWs, dbs
 
 
@@ -443,16 +494,8 @@ def rows_frame_sum(X, index, n):
     return out
 
 
-def interleave(rows):
-    """[R,K] x g -> [g*R, K] with sample-major interleaving (primal, tangent_1, ...)."""
-    return torch.stack(rows, dim=1).reshape(rows[0].shape[0] * len(rows), rows[0].shape[1])
-
-
-import contextlib
-
-_INPUT_GRADS_ONLY = False
-
-
+# ------------------------------------------------------------------------------------------------
+# The autograd Functions.
 @contextlib.contextmanager
 def input_grads_only():
     """Wrap `torch.autograd.grad(outputs, points, ...)` calls that only want d/d(input) (normals, Jacobians):
@@ -546,43 +589,68 @@ class MLPCoreBackward(torch.autograd.Function):
         return (None, None, None, gA0, ydot.contiguous()) + tuple(dWs) + tuple(dbs) + (None,) * (nl - 1)
 
 
+def mlp_apply(spec, A0, Ws, bs):
+    return MLPCoreFunction.apply(spec, A0, *Ws, *bs)
+
+
 # ------------------------------------------------------------------------------------------------
 # Effective-weight packing with a per-parameter-version cache.  The reference recomputes
 # W = g v/|v| in a forward pre-hook at EVERY module call (~30 calls per iteration); here the padded weight
 # and its transpose are built once per optimizer step and handed out as aliases (no kernel launch on a hit),
 # while each use still back-propagates into (g, v) through its own autograd node.
-_PACK_CACHE = {}     # key: id(param) -> dict(sig=..., W=..., WT=..., norms=...)
-_WT_BY_PTR = {}      # data_ptr of a packed W -> its transposed copy
+class _Pack:
+    """The packed form of one layer's weight and what deferred mode keeps with it."""
+    # W, WT, norms  padded effective weight [N, pad4(K)], its transpose [K, pad4(N)], |v| per row (weight norm) or None
+    # sig, src      _sig of the parameters W was made from; weak references to them, (v, g) or (w,): an entry must not keep them alive
+    # bias_param    the layer's bias parameter, as pack_linear last saw it
+    # dW, db, bias  deferred gradient buffers (made by the first _deferred_sink) and the bias parameter that db belongs to
+    # fresh, dirty  the next weight-gradient GEMM overwrites the buffers; they hold gradients flush_param_grads has not delivered yet
+    __slots__ = ("W", "WT", "norms", "sig", "src", "bias_param", "dW", "db", "bias", "fresh", "dirty")
+
+    def __init__(self, W, WT, norms):
+        self.W, self.WT, self.norms, self.sig, self.src = W, WT, norms, None, ()
+        self.dW = self.db = self.bias = self.bias_param = None
+        self.fresh, self.dirty = True, False
 
 
 def _sig(*ts):
     return tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in ts)
 
 
+def _lin_params(lin):
+    """(v, g) of an nn.Linear: (weight_v, weight_g) under weight norm, (weight, None) without."""
+    return (lin.weight_v, lin.weight_g) if hasattr(lin, "weight_g") else (lin.weight, None)
+
+
+def _lin_sig(v, g):
+    return _sig(v) if g is None else _sig(v, g)
+
+
+def _raise_if_dirty(e):
+    if e.dirty:
+        raise RuntimeError("mlp_engine: parameters changed while deferred gradients were pending; call flush_param_grads() "
+                           "before the optimizer step")
+
+
 def _drop_entry(key):
     e = _PACK_CACHE.pop(key, None)
     if e is not None:
-        _WT_BY_PTR.pop(e["W"].data_ptr(), None)
-        _ENTRY_BY_PTR.pop(e["W"].data_ptr(), None)
+        _ENTRY_BY_PTR.pop(e.W.data_ptr(), None)
 
 
 def _pack_entry(key, sig, build, owner=None):
+    """The entry under `key`, made by `build()` (-> _Pack) when there is none or its signature is not `sig`."""
     e = _PACK_CACHE.get(key)
     if e is None and owner is not None:
         weakref.finalize(owner, _drop_entry, key)      # the entry (packed weights, gradient buffers) goes when its parameter does
-    if e is None or e["sig"] != sig:
+    if e is None or e.sig != sig:
         if e is not None:
-            _WT_BY_PTR.pop(e["W"].data_ptr(), None)
-        if e is not None and e.get("dirty"):
-            raise RuntimeError("mlp_engine: parameters changed while deferred gradients were pending; call flush_param_grads() "
-                               "before the optimizer step")
-        if e is not None:
-            _ENTRY_BY_PTR.pop(e["W"].data_ptr(), None)
+            _raise_if_dirty(e)
+            _drop_entry(key)
         e = build()
-        e["sig"] = sig
+        e.sig = sig
         _PACK_CACHE[key] = e
-        _WT_BY_PTR[e["W"].data_ptr()] = e["WT"]
-        _ENTRY_BY_PTR[e["W"].data_ptr()] = e
+        _ENTRY_BY_PTR[e.W.data_ptr()] = e
     return e
 
 
@@ -595,12 +663,12 @@ class PackWeightNorm(torch.autograd.Function):
             with torch.no_grad():
                 w, norms = torch._weight_norm_interface(v, g, 0)
                 W = pad_cols(w, pad4(K)).contiguous()
-                return {"W": W, "WT": transpose_padded(W, K), "norms": norms}
+                return _Pack(W, transpose_padded(W, K), norms)
         e = _pack_entry(id(v), _sig(v, g), build, owner=v)
-        e["src"] = (weakref.ref(v), weakref.ref(g))
-        ctx.save_for_backward(v, g, e["norms"])
+        e.src = (weakref.ref(v), weakref.ref(g))
+        ctx.save_for_backward(v, g, e.norms)
         ctx.set_materialize_grads(False)      # deferred mode hands back None for every use: no zero tensor, no weight-norm backward of zeros
-        return e["W"].detach()
+        return e.W.detach()
 
     @staticmethod
     def backward(ctx, gW):
@@ -621,46 +689,37 @@ class PackPlain(torch.autograd.Function):
                 W = pad_cols(w, pad4(K)).contiguous()
                 if W.data_ptr() == w.data_ptr():
                     W = W.clone()
-                return {"W": W, "WT": transpose_padded(W, K), "norms": None}
+                return _Pack(W, transpose_padded(W, K), None)
         e = _pack_entry(id(w), _sig(w), build, owner=w)
-        e["src"] = (weakref.ref(w),)
+        e.src = (weakref.ref(w),)
         ctx.K = K
         ctx.set_materialize_grads(False)
-        return e["W"].detach()
+        return e.W.detach()
 
     @staticmethod
     def backward(ctx, gW):
         return None if gW is None else gW[:, :ctx.K]
 
 
-FUSED_PACK = True       # refresh all stale packs of a network with ONE launch (sr_pack_weights) instead of ~5 torch launches per layer
-
-
 def refresh_packs(lins):
     """Brings the pack entries of `lins` (the nn.Linear layers of one network) up to date with their parameters: entries that exist
-    and are stale (the optimizer stepped) are re-filled IN PLACE by one launch; entries that do not exist yet are left to the
-    per-layer torch path of pack_linear (first call only).  In-place refresh keeps every pointer (W, WT, gradient buffers)
-    stable across optimizer steps.  A graph built on the old values must be back-propagated before the optimizer step that
-    precedes this refresh -- as every training loop does; one that is not gets autograd's in-place error (the version counters of
-    the refreshed buffers are bumped after the kernel), never stale weights."""
-    if not FUSED_PACK or not lins:
-        return
-    first = lins[0].weight_v if hasattr(lins[0], "weight_g") else lins[0].weight
-    if not first.is_cuda:
+    and are stale (the optimizer stepped) are re-filled IN PLACE by ONE launch (sr_pack_weights) instead of ~5 torch launches per layer;
+    entries that do not exist yet are left to the per-layer torch path of pack_linear (first call only).  In-place refresh keeps every
+    pointer (W, WT, gradient buffers) stable across optimizer steps.  A graph built on the old values must be back-propagated before the
+    optimizer step that precedes this refresh -- as every training loop does; one that is not gets autograd's in-place error (the
+    version counters of the refreshed buffers are bumped after the kernel), never stale weights."""
+    if not lins or not _lin_params(lins[0])[0].is_cuda:
         return
     stale = []
     for lin in lins:
-        wn = hasattr(lin, "weight_g")
-        v, g = (lin.weight_v, lin.weight_g) if wn else (lin.weight, None)
+        v, g = _lin_params(lin)
         e = _PACK_CACHE.get(id(v))
         if e is None:
             continue
-        sig = _sig(v, g) if wn else _sig(v)
-        if e["sig"] != sig:
-            if e.get("dirty"):
-                raise RuntimeError("mlp_engine: parameters changed while deferred gradients were pending; call flush_param_grads() "
-                                   "before the optimizer step")
-            if e["W"].shape != (v.shape[0], pad4(v.shape[1])):
+        sig = _lin_sig(v, g)
+        if e.sig != sig:
+            _raise_if_dirty(e)
+            if e.W.shape != (v.shape[0], pad4(v.shape[1])):
                 continue                                   # shape changed: let pack_linear rebuild it
             stale.append((e, v, g, sig))
     for i in range(0, len(stale), _lib.SR_PACK_MAX_LAYERS):
@@ -673,45 +732,37 @@ def refresh_packs(lins):
             if not vv.is_contiguous():
                 vv = vv.contiguous()
             L.v, L.g = _lib.ptr(vv), (0 if g is None else _lib.ptr(g.detach().contiguous()))
-            L.W, L.WT, L.norms = _lib.ptr(e["W"]), _lib.ptr(e["WT"]), (0 if g is None else _lib.ptr(e["norms"]))
-            L.N, L.K, L.ldw, L.ldwt = v.shape[0], v.shape[1], e["W"].stride(0), e["WT"].stride(0)
+            L.W, L.WT, L.norms = _lib.ptr(e.W), _lib.ptr(e.WT), (0 if g is None else _lib.ptr(e.norms))
+            L.N, L.K, L.ldw, L.ldwt = v.shape[0], v.shape[1], e.W.stride(0), e.WT.stride(0)
         with _lib.on_device(chunk[0][1].device), torch.no_grad():
             _lib.call("sr_pack_weights", ctypes.byref(t), _lib.stream_of(chunk[0][1]))
         for e, v, g, sig in chunk:
-            e["sig"] = sig
+            e.sig = sig
         # The kernel wrote W / WT / norms behind torch's version counters.  Bump them (host-only, no launch): a graph that saved the
         # OLD values -- a retained graph, gradient accumulation over two forwards with an optimizer step in between, a delayed
         # backward -- now raises autograd's "modified by an inplace operation" error instead of silently back-propagating with
         # the new weights.
-        torch.autograd.graph.increment_version([t for e, _, _, _ in chunk for t in (e["W"], e["WT"], e["norms"]) if t is not None])
-
-
-PLAIN_PACKS = True
+        torch.autograd.graph.increment_version([t for e, _, _, _ in chunk for t in (e.W, e.WT, e.norms) if t is not None])
 
 
 def pack_linear(lin):
     """Padded effective weight of an nn.Linear, weight-normed (network.py:65-66) or plain."""
-    if DEFERRED_PARAM_GRADS and PLAIN_PACKS:
+    v, g = _lin_params(lin)
+    if DEFERRED_PARAM_GRADS:
         # Deferred mode: the weight gradients of every use go into the entry's buffers and reach (v, g) through flush_param_grads,
         # so an up-to-date pack is handed out as a plain tensor -- no autograd node per layer and call (~12 us of host time each,
         # ~250 of them per iteration).  reverse() refuses to drop a gradient silently if such a weight ever comes without a sink.
-        wn = hasattr(lin, "weight_g")
-        v = lin.weight_v if wn else lin.weight
         e = _PACK_CACHE.get(id(v))
         b = lin.bias
         # (a layer whose bias is frozen or not a leaf has no deferred sink -- _deferred_sink keys the buffers on the bias -- so its
         # weight must keep an autograd node, or its gradient would be dropped without an error: take the autograd pack below)
-        if (e is not None and e["sig"] == (_sig(v, lin.weight_g) if wn else _sig(v)) and "src" in e
-                and b is not None and b.is_leaf and b.requires_grad):
-            e["bias_param"] = b
-            return e["W"]
-    if hasattr(lin, "weight_g"):
-        W = PackWeightNorm.apply(lin.weight_v, lin.weight_g)
-    else:
-        W = PackPlain.apply(lin.weight)
+        if e is not None and e.sig == _lin_sig(v, g) and e.src and b is not None and b.is_leaf and b.requires_grad:
+            e.bias_param = b
+            return e.W
+    W = PackPlain.apply(v) if g is None else PackWeightNorm.apply(v, g)
     e = _ENTRY_BY_PTR.get(W.data_ptr())
     if e is not None:
-        e["bias_param"] = lin.bias
+        e.bias_param = lin.bias
     return W
 
 
@@ -733,13 +784,13 @@ def packed_weights_of(module, nlayers):
         b = P.get('bias')
         if b is not None:
             params.append(b)
-    key = (DEFERRED_PARAM_GRADS, PLAIN_PACKS) + tuple((id(p), p.data_ptr(), p._version, p.requires_grad) for p in params)
+    key = (DEFERRED_PARAM_GRADS,) + tuple((id(p), p.data_ptr(), p._version, p.requires_grad) for p in params)
     hit = d.get('_sr_packs')
     if hit is not None and hit[0] == key:
         return list(hit[1]), list(hit[2])
     refresh_packs(lins)
     Ws, bs = [pack_linear(lin) for lin in lins], [lin.bias for lin in lins]
-    if DEFERRED_PARAM_GRADS and PLAIN_PACKS and all(W.grad_fn is None and not W.requires_grad and W.data_ptr() in _ENTRY_BY_PTR for W in Ws):
+    if DEFERRED_PARAM_GRADS and all(W.grad_fn is None and not W.requires_grad and W.data_ptr() in _ENTRY_BY_PTR for W in Ws):
         d['_sr_packs'] = (key, list(Ws), list(bs))
     else:
         d.pop('_sr_packs', None)
@@ -750,27 +801,18 @@ def transposed_of(W, K):
     """W^T for the backward-data GEMM: the packed transpose, or -- for a leading block of a packed weight (the first K input columns
     of a first layer whose per-frame code was hoisted out, the first row of the sdf-only last layer) -- the matching block of it
     (same row pitch; the GEMM masks the contraction tail, so the columns past N inside the 16-byte pad are never used)."""
-    WT = _WT_BY_PTR.get(W.data_ptr())
-    if WT is not None:
+    e = _ENTRY_BY_PTR.get(W.data_ptr())
+    if e is not None:
+        WT = e.WT
         if WT.shape == (K, pad4(W.shape[0])):
             return WT
-        e = _ENTRY_BY_PTR.get(W.data_ptr())
-        if (e is not None and e["WT"] is WT and W.stride(0) == e["W"].stride(0) and W.shape[0] <= e["W"].shape[0]
-                and K <= WT.shape[0] and pad4(W.shape[0]) <= WT.shape[1]):
+        if W.stride(0) == e.W.stride(0) and W.shape[0] <= e.W.shape[0] and K <= WT.shape[0] and pad4(W.shape[0]) <= WT.shape[1]:
             return WT[:K, :pad4(W.shape[0])]
     return transpose_padded(W, K)
 
 
 # ------------------------------------------------------------------------------------------------
-# Deferred parameter gradients (opt-in, used by the training step): every weight-gradient GEMM adds
-# into ONE persistent buffer per layer instead of returning a tensor that autograd then pushes through
-# a weight-norm backward and an AccumulateGrad add for each of the ~30 network uses per iteration.
-# `flush_param_grads()` runs the weight-norm backward once per layer and adds into the parameters'
-# .grad; OptimNetwork.propagateTmpPsGrad (the last gradient producer of a step) calls it.
-DEFERRED_PARAM_GRADS = False
-_ENTRY_BY_PTR = {}
-
-
+# Deferred parameter gradients (see DEFERRED_PARAM_GRADS at the top).
 def set_deferred_param_grads(flag):
     global DEFERRED_PARAM_GRADS
     flush_param_grads()
@@ -781,37 +823,37 @@ def _deferred_sink(W, b):
     """-> (dW buffer, db buffer, accumulate) or None.  Both buffers are private to the pack entry; the first weight-gradient GEMM
     after a flush OVERWRITES them (no zero fill), later ones add."""
     e = _ENTRY_BY_PTR.get(W.data_ptr())
-    if e is None or b is None or not b.requires_grad or W.shape[0] > e["W"].shape[0] or W.stride(0) != e["W"].stride(0):
+    if e is None or b is None or not b.requires_grad or W.shape[0] > e.W.shape[0] or W.stride(0) != e.W.stride(0):
         return None
-    n, full = W.shape[0], W.shape[0] == e["W"].shape[0]
+    n, full = W.shape[0], W.shape[0] == e.W.shape[0]
     if full:
         if not b.is_leaf:
             return None
     else:
         # the leading rows of a layer (the sdf-only evaluation uses row 0 of the last SDF layer, with bias[:1]): same buffers, first
         # rows.  `b` must then be the head of the layer's own bias parameter (registered by pack_linear).
-        base = e.get("bias_param")
+        base = e.bias_param
         if base is None or not base.is_leaf or not base.requires_grad or b.data_ptr() != base.data_ptr():
             return None
         b = base
-    if e.get("dW") is None:
-        e["dW"] = torch.empty_like(e["W"])
-        e["db"] = torch.empty((e["W"].shape[0],), dtype=torch.float32, device=e["W"].device)
-        e["fresh"] = True
-    if e["fresh"] and not full:                 # a partial first use: the rows it does not touch must read as zero at the flush
-        e["dW"].zero_(); e["db"].zero_()
-        e["fresh"] = False
-    accumulate = not e["fresh"]
-    e["fresh"] = False
-    e["dirty"] = True
-    e["bias"] = b
-    return e["dW"][:n], e["db"][:n], accumulate
+    if e.dW is None:
+        e.dW = torch.empty_like(e.W)
+        e.db = torch.empty((e.W.shape[0],), dtype=torch.float32, device=e.W.device)
+        e.fresh = True
+    if e.fresh and not full:                    # a partial first use: the rows it does not touch must read as zero at the flush
+        e.dW.zero_(); e.db.zero_()
+        e.fresh = False
+    accumulate = not e.fresh
+    e.fresh = False
+    e.dirty = True
+    e.bias = b
+    return e.dW[:n], e.db[:n], accumulate
 
 
 def flush_param_grads(only=None):
     """`only`: ids of parameter tensors (weight_v / weight) whose layers are flushed now; the rest stays pending.
     All pending layers are turned into parameter gradients by ONE launch (sr_unpack_grads: weight-norm backward / plain copy)."""
-    todo = [e for e in _PACK_CACHE.values() if e.get("dirty") and (only is None or id(e["src"][0]()) in only)]
+    todo = [e for e in _PACK_CACHE.values() if e.dirty and (only is None or id(e.src[0]()) in only)]
     if not todo:
         return
     join_weight_gradient_stream()
@@ -822,7 +864,7 @@ def flush_param_grads(only=None):
         outs = []
         for j, e in enumerate(chunk):
             L = t.layer[j]
-            src = tuple(r() for r in e["src"])          # (weak references: an entry must not keep its parameters alive)
+            src = tuple(r() for r in e.src)
             v = src[0]
             g = src[1] if len(src) == 2 else None
             acc = v.grad is not None and (g is None or g.grad is not None)
@@ -837,34 +879,28 @@ def flush_param_grads(only=None):
             vd = v.detach()
             if not vd.is_contiguous():
                 vd = vd.contiguous()
-            L.dW, L.lddw = _lib.ptr(e["dW"]), e["dW"].stride(0)
-            L.v, L.g, L.norms = _lib.ptr(vd), (0 if g is None else _lib.ptr(g.detach().contiguous())), (0 if g is None else _lib.ptr(e["norms"]))
+            L.dW, L.lddw = _lib.ptr(e.dW), e.dW.stride(0)
+            L.v, L.g, L.norms = _lib.ptr(vd), (0 if g is None else _lib.ptr(g.detach().contiguous())), (0 if g is None else _lib.ptr(e.norms))
             L.gv, L.gg, L.N, L.K, L.accumulate = _lib.ptr(gv), _lib.ptr(gg), v.shape[0], v.shape[1], 1 if acc else 0
-            b = e["bias"]
+            b = e.bias
             fold_bias = b.grad is not None and b.grad.is_contiguous() and b.grad.dtype == torch.float32       # else: the buffer is handed over below
-            L.db, L.gb = (_lib.ptr(e["db"]), _lib.ptr(b.grad)) if fold_bias else (0, 0)
+            L.db, L.gb = (_lib.ptr(e.db), _lib.ptr(b.grad)) if fold_bias else (0, 0)
             outs.append((e, v, g, gv, gg, acc, vd, fold_bias))
-        dev = chunk[0]["W"].device
+        dev = chunk[0].W.device
         with _lib.on_device(dev), torch.no_grad():
             _lib.call("sr_unpack_grads", ctypes.byref(t), torch.cuda.current_stream(dev).cuda_stream)
         for e, v, g, gv, gg, acc, _, fold_bias in outs:
-            if acc:
-                pass                                         # added in place
-            else:
+            if not acc:                                      # (else: added in place)
                 v.grad = gv if v.grad is None else v.grad.add_(gv)
                 if g is not None:
                     g.grad = gg if g.grad is None else g.grad.add_(gg)
-            b = e["bias"]
+            b = e.bias
             if fold_bias:
                 torch.autograd.graph.increment_version(b.grad)   # added in place by the launch above
             elif b.grad is None:                               # hand the buffer over instead of copying it; a new one is made on demand
-                b.grad = e["db"]
-                e["db"] = torch.empty_like(e["db"])
+                b.grad = e.db
+                e.db = torch.empty_like(e.db)
             else:
-                b.grad.add_(e["db"])
-            e["fresh"] = True                                  # the next GEMM overwrites the buffers
-            e["dirty"] = False
-
-
-def mlp_apply(spec, A0, Ws, bs):
-    return MLPCoreFunction.apply(spec, A0, *Ws, *bs)
+                b.grad.add_(e.db)
+            e.fresh = True                                     # the next GEMM overwrites the buffers
+            e.dirty = False

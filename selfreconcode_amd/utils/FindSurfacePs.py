@@ -185,13 +185,6 @@ class _RefinerWorkspace:
         self.a0bar, self.a0dbar = f(cap, me.pad4(ev.sdf_spec.K0)), f(cap, me.pad4(ev.tr.spec.K0))
 
 
-def _fill_gemm(g, A, B, C, N, K, bias, act, mode, out_scale=1.0, aux=None, naux_fwd=0, nact_bwd=0, aux_scale=1.0):
-    g.A, g.lda, g.B, g.ldb, g.C, g.ldc = _lib.ptr(A), A.stride(0), _lib.ptr(B), B.stride(0), _lib.ptr(C), C.stride(0)
-    g.M, g.N, g.K, g.bias = 0, N, K, _lib.ptr(bias)
-    g.group, g.act, g.mode, g.out_scale = 1, act, mode, out_scale
-    g.aux, g.ldaux, g.naux_fwd, g.nact_bwd, g.aux_scale = _lib.ptr(aux), 0 if aux is None else aux.stride(0), naux_fwd, nact_bwd, aux_scale
-
-
 def _forward_chain(ws, ev):
     c = _lib.SrChainArgs()
     nets = ((ev.sdf_spec, ev.sdf_W, ev.sdf_b, ws.a0, ws.sdf_act), (ev.tr.spec, ev.def_W, ev.def_b, ws.a0d, ws.def_act))
@@ -202,8 +195,8 @@ def _forward_chain(ws, ev):
             if l >= len(spec.layers):
                 continue
             L = spec.layers[l]
-            _fill_gemm(c.g[l][k], a0 if l == 0 else acts[l - 1], W[l], acts[l], L.N, L.K, b[l], L.act, me.EPI_FWD, out_scale=L.out_scale,
-                       aux=a0 if L.nfill else None, naux_fwd=L.nfill)
+            me.set_gemm_args(c.g[l][k], a0 if l == 0 else acts[l - 1], W[l], acts[l], 0, L.N, L.K, b[l], 1, L.act, me.EPI_FWD,
+                             out_scale=L.out_scale, aux=a0 if L.nfill else None, naux_fwd=L.nfill)
             k += 1
         c.nprob[l] = k
     return c
@@ -226,10 +219,10 @@ def _reverse_chain(ws, ev):
             src = ybar if l == nl - 1 else zbar[l + 1]
             if l > 0:
                 Pv = spec.layers[l - 1]
-                _fill_gemm(c.g[r][k], src, WT[l], zbar[l], L.K, L.N, None, Pv.act, me.EPI_BWD, out_scale=Pv.out_scale, aux=acts[l - 1], nact_bwd=Pv.N,
-                           aux_scale=Pv.out_scale)
+                me.set_gemm_args(c.g[r][k], src, WT[l], zbar[l], 0, L.K, L.N, None, 1, Pv.act, me.EPI_BWD, out_scale=Pv.out_scale, aux=acts[l - 1],
+                                 nact_bwd=Pv.N, aux_scale=Pv.out_scale)
             else:
-                _fill_gemm(c.g[r][k], src, WT[0], a0bar, L.K, L.N, None, me.ACT_NONE, me.EPI_FWD)
+                me.set_gemm_args(c.g[r][k], src, WT[0], a0bar, 0, L.K, L.N, None, 1, me.ACT_NONE, me.EPI_FWD)
             k += 1
         c.nprob[r] = k
     return c
@@ -289,20 +282,13 @@ def _optimize_device_driven(ev, cam, rays, initTmpPs, batch_inds, dthreshold, at
         ra = ctypes.byref(a)
         _lib.call("sr_refine_init", ra, st)
 
-        prof = me.PROFILE if me.PROFILE.enabled else None
         fwd_flop = sum(2.0 * g.N * g.K for l in range(fwd.nlayers) for g in fwd.g[l][:fwd.nprob[l]])
         rev_flop = sum(2.0 * g.N * g.K for l in range(rev.nlayers) for g in rev.g[l][:rev.nprob[l]])
         marks = []
 
-        def chain(c, phase, flop_per_row):
+        def chain(c, phase, flop_per_row):                 # (bench.py's roofline leg: the chain's FLOPs are live[phase] x (sum over its layers))
             c.m_dev = ws.live.data_ptr() + 4 * phase
-            if prof is not None:                           # bench.py's roofline leg: the chain's FLOPs are live[phase] x (sum over its layers)
-                e0, e1 = prof.pair()
-                e0.record()
-            _lib.call("sr_mlp_chain", ctypes.byref(c), st)
-            if prof is not None:
-                e1.record()
-                marks.append((e0, e1, phase, flop_per_row))
+            me.PROFILE.launch("sr_mlp_chain", c, st, what=(phase, flop_per_row), marks=marks)
 
         def evaluate(phase):                               # the first-layer inputs were written by whoever enqueued the rays
             chain(fwd, phase, fwd_flop)
@@ -319,8 +305,8 @@ def _optimize_device_driven(ev, cam, rays, initTmpPs, batch_inds, dthreshold, at
             if watch is not None: watch(a, ws, k + 1, st)
         evaluate(times + 1)
         _lib.call("sr_refine_mid", ra, times + 1, 2, st)
-        if prof is not None:
-            prof.chains.append((marks, ws.live[:times + 2].clone(), me.PROFILE.overlap))
+        if me.PROFILE.enabled:
+            me.PROFILE.chains.append((marks, ws.live[:times + 2].clone(), me.PROFILE.overlap))
     x0.record_stream(torch.cuda.current_stream(dev)); bi.record_stream(torch.cuda.current_stream(dev))
     initTmpPs.copy_(p_out)
     return initTmpPs.detach(), conv_out.bool(), ws

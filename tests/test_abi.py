@@ -87,15 +87,17 @@ def test_pack_cache_entries_die_with_their_parameters():
     import torch
     from selfreconcode_amd import mlp_engine as me
 
-    class Stub:                       # what _pack_entry needs of an entry, without a GPU
-        pass
     lin = torch.nn.Linear(8, 4)
     key = id(lin.weight)
-    W = torch.zeros(4, 8)
-    e = me._pack_entry(key, ("sig",), lambda: {"W": W, "WT": W.t().contiguous(), "norms": None}, owner=lin.weight)
-    assert key in me._PACK_CACHE and me._ENTRY_BY_PTR[W.data_ptr()] is e
+    W = torch.zeros(4, 8)                                 # (a CPU tensor: the registry needs no GPU)
+    e = me._pack_entry(key, ("sig",), lambda: me._Pack(W, W.t().contiguous(), None), owner=lin.weight)
+    assert me._PACK_CACHE[key] is e and me._ENTRY_BY_PTR[W.data_ptr()] is e
     import weakref
-    e["src"] = (weakref.ref(lin.weight),)
+    e.src = (weakref.ref(lin.weight),)
     del lin
     gc.collect()
-    assert key not in me._PACK_CACHE and W.data_ptr() not in me._ENTRY_BY_PTR and W.data_ptr() not in me._WT_BY_PTR
+    assert key not in me._PACK_CACHE and W.data_ptr() not in me._ENTRY_BY_PTR
+    for name, reg in vars(me).items():                    # no registry of the engine holds the entry or the pointer
+        if isinstance(reg, (dict, set)) and not name.startswith("__"):
+            held = list(reg) + (list(reg.values()) if isinstance(reg, dict) else [])
+            assert not any(x is e or (isinstance(x, int) and x == W.data_ptr()) for x in held), name

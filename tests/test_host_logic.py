@@ -120,6 +120,7 @@ def test_pack_cache_follows_parameter_changes():
             net.lin1.weight.mul_(2.0)
         W3, _ = me.packed_weights_of(net, 2)
         assert torch.allclose(W3[1][:, :12], net.lin1.weight)
+        assert W2[1].data_ptr() not in me._ENTRY_BY_PTR and W3[1].data_ptr() in me._ENTRY_BY_PTR      # the replaced entry left the registry
         net.lin1.bias = nn.Parameter(torch.full((3,), 0.25))          # a replaced parameter
         _, b4 = me.packed_weights_of(net, 2)
         assert b4[1] is net.lin1.bias

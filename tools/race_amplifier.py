@@ -43,8 +43,9 @@ for mode in ("f32",):
     for name, env in configs:
         out = f"/tmp/race_{len(name)}.pt"
         r = subprocess.run([sys.executable, "-c", CHILD, out], env=dict(os.environ, **env), capture_output=True, text=True, timeout=600)
-        if r.returncode != 0:
-            print(name, "FAILED TO RUN", r.stderr[-800:]); continue
+        if r.returncode != 0:               # nothing more is started on a GPU that a child has just faulted, aborted or hung on
+            print(name, "FAILED TO RUN", r.stderr[-800:], flush=True)
+            sys.exit(1)
         a, b = torch.load(out)
         rep = [k for k in a if a[k].shape != b[k].shape or not torch.equal(a[k], b[k])]
         if base is None:
