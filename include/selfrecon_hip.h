@@ -125,6 +125,10 @@ typedef struct {
   float aux_scale;        /* BWD: scale the stored activations carry */
 } sr_gemm_args;
 int sr_mlp_gemm_nt(const sr_gemm_args* host_args, void* stream);
+/* Tile shape (rows x columns of C per workgroup) sr_mlp_gemm_nt launches for M rows and ncols = N (+ naux_fwd in SR_EPI_FWD) output
+ * columns: one of 32x32, 64x32, 256x32 (ncols <= 32), 64x64, 64x128, 128x128.  Host only, needs no device.  A tile takes the
+ * straight-line epilogue when it lies inside the M rows and inside the first N (SR_EPI_FWD) / min(N, nact_bwd) (SR_EPI_BWD) columns. */
+int sr_mlp_gemm_nt_tile(int32_t M, int32_t ncols, int32_t* bm_out, int32_t* bn_out);
 
 /* Layer chain: up to SR_CHAIN_MAX_LAYERS consecutive layer GEMMs of one or two independent networks (layer l of both side
  * by side in one grid) on a row count read from DEVICE memory: rows = *m_dev * m_mul <= m_cap * m_mul (every g[l][p].M is
@@ -169,8 +173,6 @@ typedef struct {
   sr_gemm_tn_args p[SR_TN_GROUP_MAX];
 } sr_gemm_tn_group_args;
 int sr_mlp_gemm_tn_group(const sr_gemm_tn_group_args* host_args, void* stream);
-/* Bias gradient: out[n] += sum_{r % group == 0} Z[r][n]  (out must be zero-filled or hold the running sum). */
-int sr_colsum_rows(const float* Z, int64_t ldz, int32_t R, int32_t N, int32_t group, float* out, void* stream);
 
 /* Positional encoding (a1) fused with the first-layer input assembly: replaces the 13 elementwise
  * launches + torch.cat of model/Embedder.py:34-41 and the conds[batch_inds] concat of

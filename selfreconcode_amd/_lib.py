@@ -160,6 +160,7 @@ SIGNATURES = {
     "sr_gridsample3d_dbwd_f32": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp, _vp],
     "sr_gridsample3d_dbwd_f64": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp, _vp],
     "sr_mlp_gemm_nt": [_vp, _vp],
+    "sr_mlp_gemm_nt_tile": [ctypes.c_int32, ctypes.c_int32, _vp, _vp],
     "sr_mlp_chain": [_vp, _vp],
     "sr_refine_init": [_vp, _vp],
     "sr_refine_embed": [_vp, ctypes.c_int32, _vp],
@@ -168,7 +169,6 @@ SIGNATURES = {
     "sr_mlp_gemm_tn_workspace_floats": [ctypes.c_int32, ctypes.c_int32, _i64, _vp],
     "sr_mlp_gemm_tn": [_vp, _vp],
     "sr_mlp_gemm_tn_group": [_vp, _vp],
-    "sr_colsum_rows": [_vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
     "sr_lbs_chain_fwd": [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_lbs_chain_bwd": [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_lbs_fwd": [_vp, _vp],

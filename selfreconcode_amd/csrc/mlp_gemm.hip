@@ -800,24 +800,36 @@ __global__ __launch_bounds__(256) void slab_reduce_group_kernel(TnGroup G) {
   slab_reduce_body(g.partial, g.dW, g.N, g.K, g.lddw, g.R > 0 ? g.splits : 0, g.accumulate, g.db_partial, g.db, bid, G.blocks[i]);
 }
 
-// out[n] = sum over primal rows (r % group == 0) of Z[r][n]; one workgroup per 64 columns x row-slice,
-// finished by atomics into a zeroed `out` only when more than one slice exists.
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ Z, int64_t ldz, int R, int N, int group,
-                                                      float* __restrict__ out, int rows_per_block) {
-  __shared__ float red[4][64];
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  const int sub = threadIdx.x >> 6;
-  const int r_begin = blockIdx.y * rows_per_block;
-  const int r_end = min(R, r_begin + rows_per_block);
-  float s = 0.f;
-  if (c < N)
-    for (int r = r_begin + sub * group; r < r_end; r += 4 * group) s += Z[(int64_t)r * ldz + c];
-  red[sub][threadIdx.x & 63] = s;
-  __syncthreads();
-  if (sub == 0 && c < N) atomicAdd(out + c, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
-}
-
 }  // namespace
+
+// Tile shape of an NT launch on M rows and `ncols` output columns, by a cost model.  The one place that decides it: sr_mlp_gemm_nt
+// launches what this returns and sr_mlp_gemm_nt_tile reports it.
+static void nt_tile_choice(int M, int ncols, int* bm, int* bn) {
+  auto cost = [&](int tm, int tn, double eff) {
+    const int64_t wgs = sr_cdiv(M, tm) * sr_cdiv(ncols, tn);
+    return (double)sr_cdiv(wgs, 256) * tm * tn / eff;
+  };
+  if (ncols <= 32) {
+    // narrow outputs (the 3-wide deformer / render heads, the sdf-only last layer): 256x32 tiles for the template-sized batches,
+    // 64x32 / 32x32 for the refiner's few thousand rows (6k rows are only 24 tiles of 256 rows on 256 CUs)
+    const double c[3] = {cost(32, 32, 0.6), cost(64, 32, 0.8), cost(256, 32, 1.0)};
+    *bn = 32;
+    if (c[0] < c[1] && c[0] < c[2]) *bm = 32;
+    else if (c[1] < c[2]) *bm = 64;
+    else *bm = 256;
+  } else {
+    // The workgroups resident on a CU share its four MFMA pipes, so a CU's time is (tiles it receives) x (tile work):
+    // cost = ceil(workgroups / 256) * bm * bn / eff, eff = measured large-M rate of the configuration relative to 128x128.
+    // (M = 6144, N = 512: 64x64 gives 3 tiles/CU = 12.3k, 64x128 2 tiles/CU = 16.4k, 128x128 1 tile on 192 CUs = 16.4k;
+    // measured 31.5 / 39.9 / 45 us.)
+    // (256x128 and 128x256 tiles with 8 waves were measured in rounds 3-4 and lose: one workgroup per CU.)
+    const double c[3] = {cost(64, 64, 0.92), cost(64, 128, 0.94), cost(128, 128, 1.0)};
+    int pick = 1;
+    for (int i = 1; i < 3; ++i) if (c[i] < c[pick - 1]) pick = i + 1;
+    *bm = pick == 3 ? 128 : 64;
+    *bn = pick == 1 ? 64 : 128;
+  }
+}
 
 extern "C" {
 int sr_mlp_gemm_nt(const sr_gemm_args* a, void* stream) {
@@ -834,11 +846,6 @@ int sr_mlp_gemm_nt(const sr_gemm_args* a, void* stream) {
   const int ncols = a->N + (a->mode == SR_EPI_FWD ? a->naux_fwd : 0);
   sr_gemm_args g = *a;
   if (g.mode != SR_EPI_FWD) g.naux_fwd = 0;
-  // Tile choice by a cost model, see below.
-  auto cost = [&](int bm, int bn, double eff) {
-    const int64_t wgs = sr_cdiv(g.M, bm) * sr_cdiv(ncols, bn);
-    return (double)sr_cdiv(wgs, 256) * bm * bn / eff;
-  };
 #define SR_NT_LAUNCH(WM, WN, TM, TN)                                                                                        \
   do {                                                                                                                      \
     using C_ = Cfg<WM, WN, TM, TN>;                                                                                         \
@@ -850,30 +857,24 @@ int sr_mlp_gemm_nt(const sr_gemm_args* a, void* stream) {
       hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, false>), dim3(nwg), dim3(C_::kThreads), C_::kLdsFloats * sizeof(float), \
                          (hipStream_t)stream, g);                                                                           \
   } while (0)
-  if (ncols <= 32) {
-    // narrow outputs (the 3-wide deformer / render heads, the sdf-only last layer): 256x32 tiles for the template-sized batches,
-    // 64x32 / 32x32 for the refiner's few thousand rows (6k rows are only 24 tiles of 256 rows on 256 CUs)
-    const double c[3] = {cost(32, 32, 0.6), cost(64, 32, 0.8), cost(256, 32, 1.0)};
-    if (c[0] < c[1] && c[0] < c[2]) SR_NT_LAUNCH(1, 1, 1, 1);
-    else if (c[1] < c[2]) SR_NT_LAUNCH(2, 1, 1, 1);
-    else SR_NT_LAUNCH(4, 1, 2, 1);
-  } else {
-    // The workgroups resident on a CU share its four MFMA pipes, so a CU's time is (tiles it receives) x (tile work):
-    // cost = ceil(workgroups / 256) * bm * bn / eff, eff = measured large-M rate of the configuration relative to 128x128.
-    // (M = 6144, N = 512: 64x64 gives 3 tiles/CU = 12.3k, 64x128 2 tiles/CU = 16.4k, 128x128 1 tile on 192 CUs = 16.4k;
-    // measured 31.5 / 39.9 / 45 us.)
-    // (256x128 and 128x256 tiles with 8 waves were measured in rounds 3-4 and lose: one workgroup per CU.)
-    const double c[3] = {cost(64, 64, 0.92), cost(64, 128, 0.94), cost(128, 128, 1.0)};
-    int pick = 1;
-    for (int i = 1; i < 3; ++i) if (c[i] < c[pick - 1]) pick = i + 1;
-    switch (pick) {
-      case 1: SR_NT_LAUNCH(2, 2, 1, 1); break;
-      case 2: SR_NT_LAUNCH(2, 2, 1, 2); break;
-      default: SR_NT_LAUNCH(2, 2, 2, 2); break;
-    }
+  int bm = 0, bn = 0;
+  nt_tile_choice(g.M, ncols, &bm, &bn);
+  switch (bm * 1024 + bn) {
+    case 32 * 1024 + 32: SR_NT_LAUNCH(1, 1, 1, 1); break;
+    case 64 * 1024 + 32: SR_NT_LAUNCH(2, 1, 1, 1); break;
+    case 256 * 1024 + 32: SR_NT_LAUNCH(4, 1, 2, 1); break;
+    case 64 * 1024 + 64: SR_NT_LAUNCH(2, 2, 1, 1); break;
+    case 64 * 1024 + 128: SR_NT_LAUNCH(2, 2, 1, 2); break;
+    default: SR_NT_LAUNCH(2, 2, 2, 2); break;
   }
 #undef SR_NT_LAUNCH
   return sr_launch_status();
+}
+
+int sr_mlp_gemm_nt_tile(int32_t M, int32_t ncols, int32_t* bm, int32_t* bn) {
+  if (M <= 0 || ncols <= 0 || !bm || !bn) return SR_EINVAL;
+  nt_tile_choice(M, ncols, bm, bn);
+  return SR_OK;
 }
 
 // The same layer pair as ONE ordinary launch: grid sized for the capacity row count, workgroups past the tiles of the LIVE row count
@@ -996,19 +997,6 @@ int sr_mlp_gemm_tn_group(const sr_gemm_tn_group_args* a, void* stream) {
   if (any_rows && nb > 0)
     hipLaunchKernelGGL(gemm_tn_group_kernel, dim3(nb), dim3(256), Square::kLdsFloats * sizeof(float), (hipStream_t)stream, G);
   hipLaunchKernelGGL(slab_reduce_group_kernel, dim3(nr), dim3(256), 0, (hipStream_t)stream, Rd);
-  return sr_launch_status();
-}
-
-int sr_colsum_rows(const float* Z, int64_t ldz, int32_t R, int32_t N, int32_t group, float* out, void* stream) {
-  if (!out || R < 0 || N <= 0 || group < 1) return SR_EINVAL;
-  if (R == 0) return SR_OK;
-  if (!Z) return SR_EINVAL;
-  int slices = (int)sr_cdiv(R, 4096);
-  if (slices > 256) slices = 256;
-  int rows_per_block = (int)sr_cdiv(R, slices);
-  rows_per_block = (int)(sr_cdiv(rows_per_block, 4 * group) * 4 * group);
-  slices = (int)sr_cdiv(R, rows_per_block);
-  hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)sr_cdiv(N, 64), slices), dim3(256), 0, (hipStream_t)stream, Z, ldz, R, N, group, out, rows_per_block);
   return sr_launch_status();
 }
 }

@@ -211,6 +211,63 @@ def test_gemm_kernels_ragged_shapes_vs_float64(M, N, K):
     assert torch.isfinite(dW).all()                                # padding columns [K, pad4(K)) are written as zeros
 
 
+TN_CASES = [  # (R, N, K, group, accumulate): row counts around the 384-row split floor and the 32-row step, no rows at all, both tile shapes
+    (0, 130, 96, 1, False), (0, 130, 96, 2, True), (0, 256, 39, 4, True), (4, 3, 512, 4, False), (383, 512, 167, 1, True), (384, 257, 289, 2, False),
+    (385, 512, 512, 1, False), (388, 473, 512, 4, True), (12289, 512, 473, 1, True), (12290, 130, 96, 2, False), (12292, 512, 512, 4, False),
+    (382, 256, 39, 2, True), (384, 300, 64, 4, False), (385, 256, 41, 1, True), (12292, 512, 39, 4, True), (12289, 257, 7, 1, False)]
+
+
+def _tn_problem(R, N, K, group, seed):
+    from selfreconcode_amd import mlp_engine as me
+    g = torch.Generator().manual_seed(seed)
+    ldz, lda, lddw = me.pad4(N) + 8, me.pad4(K) + 4, me.pad4(K)
+    Z = torch.full((max(R, 1), ldz), float("nan")); Z[:R, :N] = torch.randn(R, N, generator=g)
+    A = torch.full((max(R, 1), lda), float("nan")); A[:R, :K] = torch.randn(R, K, generator=g)
+    dW0 = torch.randn(N, lddw, generator=g) * 3.0
+    db0 = torch.randn(N, generator=g) * 3.0
+    return Z, ldz, A, lda, lddw, dW0, db0
+
+
+def _tn_check(dW, db, Z, A, R, N, K, group, dW0, db0, acc, what):
+    from oracle import gemm_epilogue_ref as ger
+    rdW, rdb = ger.tn_ref(Z[:R, :N], A[:R, :K], group, dW0[:, :K], db0, acc)
+    tol = 2e-5 * max(1.0, R ** 0.5)
+    torch.testing.assert_close(dW[:, :K].cpu().double(), rdW, rtol=2e-5, atol=tol, msg=lambda m: f"dW {what}: {m}")
+    torch.testing.assert_close(db.cpu().double(), rdb, rtol=2e-5, atol=tol, msg=lambda m: f"db {what}: {m}")
+    pad = dW[:, K:].cpu()
+    assert torch.equal(pad, dW0[:, K:] if acc else torch.zeros_like(pad)), what          # the header: padding columns are written as 0 (added to when accumulating)
+
+
+@pytest.mark.parametrize("R,N,K,group,acc", TN_CASES)
+def test_weight_gradient_groups_and_accumulate_vs_float64(R, N, K, group, acc):
+    """sr_mlp_gemm_tn against float64 (oracle/gemm_epilogue_ref.py::tn_ref): dW over all rows, db over the primal rows of group 2 / 4
+    only, accumulate onto non-zero dW / db, no rows at all, row counts at the 384-row split floor and the 32-row step, both tile
+    shapes (256 x 64 for K <= 64 and N >= 256); NaN in the operand padding.  Bounds as in the ragged test above."""
+    from selfreconcode_amd import mlp_engine as me
+    assert R % group == 0
+    Z, ldz, A, lda, lddw, dW0, db0 = _tn_problem(R, N, K, group, R * 31 + N * 7 + K + group)
+    dW, db = dW0.to(DEV), db0.to(DEV)
+    me._gemm_tn(Z.to(DEV), ldz, A.to(DEV), lda, R, N, K, lddw, group, dW=dW, db=db, accumulate=acc)
+    _tn_check(dW, db, Z, A, R, N, K, group, dW0, db0, acc, (R, N, K, group, acc))
+
+
+def test_grouped_weight_gradients_vs_float64():
+    """sr_mlp_gemm_tn_group against the truth (the test below compares it with the single launches only)."""
+    from selfreconcode_amd import mlp_engine as me
+    shapes = [c for c in TN_CASES if not me._tn_is_narrow(c[1], me.pad4(c[2]))][:me._lib.SR_TN_GROUP_MAX]
+    assert len(shapes) >= 8 and {c[3] for c in shapes} == {1, 2, 4} and any(c[0] == 0 for c in shapes)
+    probs, keep = [], []
+    for i, (R, N, K, group, acc) in enumerate(shapes):
+        Z, ldz, A, lda, lddw, dW0, db0 = _tn_problem(R, N, K, group, 9000 + i)
+        dW, db = dW0.to(DEV), db0.to(DEV)
+        probs.append((Z.to(DEV), ldz, A.to(DEV), lda, R, N, K, lddw, group, dW, db, acc))
+        keep.append((Z, A, dW0, db0))
+    me._gemm_tn_group(probs)
+    torch.cuda.synchronize()
+    for p, (Z, A, dW0, db0), s in zip(probs, keep, shapes):
+        _tn_check(p[9], p[10], Z, A, *s[:4], dW0, db0, s[4], ("grouped",) + s)
+
+
 def test_pe_embed_kernel_vs_reference_golden(golden):
     """a1: the fused embed kernel itself against the reference's Embedder run (tests/golden/pe.npz): ratio None (all ones),
     annealed 0.35 / 1.0 and the <= 0 switch (all PE weights zero, used by initializeTmpSDF with ratio -1)."""
