@@ -504,6 +504,42 @@ int sr_mask_iou_loss_bwd(const float* masks, const float* gt, int N, int64_t hw,
 int sr_implicit_solve(const float* grad_f, const float* J, const float* v, const float* grad_l, int64_t n, float* cot_f, float* rhs_tail, float* temp,
                       uint8_t* ok, void* stream);
 
+/* Texture baking (csrc/texture.hip): the reference's texture_mesh_extract.py on the GPU.  opendr's visibility / VideoAvatar's Isomapper
+ * are third-party code outside the reference repository; their semantics are restated, parity unpinned.
+ *   sr_uv_rasterize: vt [Vt,2] in [0,1]^2, ft [F,3] -> face [R,R] int32 (-1: none) and bary [R,R,3].  Texel (r, c) has centre
+ *     u = (c + 0.5) / R, v = 1 - (r + 0.5) / R and belongs to the lowest-indexed non-degenerate UV triangle that contains it (edge
+ *     functions >= 0 for either winding; |twice the area| <= 1e-14 or an index outside [0, Vt): owns nothing).  Integer atomics only.
+ *   sr_face_visibility: visible [N,F] uint8 = the face owns a pixel of pix_to_face [N,H,W] (packed indices n F + f, as
+ *     sr_rasterize_meshes writes them) and its three vertices are in the mask: rint of xy_pix [N,V,2] inside the viewport and
+ *     mask [N,H,W] (uint8) set there.
+ *   sr_view_alpha: alpha [N,V] = max(0, dot(normalize(verts - cam_pos[n]), -normals)).
+ *   sr_texture_accumulate: for the T covered texels (tface [T], tbary [T,3]) and the N views in order: cosv = UV-barycentric blend of
+ *     alpha (0 on a face that is not visible); where cosv > the minimum over the texel's agg_num slots, the first slot holding the
+ *     minimum takes (cosv, bilinear sample of images [N,H,W,3] at the blend of the vertices' pixel positions, fids[n]).  Slots are
+ *     slot-major: slot_cos / slot_view [agg_num,T], slot_rgb [agg_num,3,T]; count / min_cos / min_idx [T] carry the fill count and the
+ *     running minimum between calls.  The caller initialises slot_cos = cosv0 (>= 0), slot_view = -1, slot_rgb = count = min_idx = 0,
+ *     min_cos = cosv0.
+ *   sr_texture_resolve: per covered texel (texel [T]: its index r R + c) into the [R,R] images: count = slots > cosv0, mask_final =
+ *     count >= check_num, view_id = view of the first slot with the maximum (-1 outside mask_final), tex_median [R,R,3] = per-channel
+ *     median of the filled slots (even count: mean of the two middle values; 0 outside mask_final).
+ *   sr_texture_fill: texture [R,R,3] = tex_median on mask_final, a push-pull fill (known texels averaged down a 2x pyramid to 1 x 1,
+ *     then bilinearly pulled back into unknown cells only) on the square dilation of tex_mask by `dilate` texels (cv2.dilate's window
+ *     i - k/2 .. i - k/2 + k - 1) minus mask_final, 0 elsewhere.  workspace: sr_texture_fill_workspace_bytes(R) bytes, 16-byte aligned. */
+int sr_uv_rasterize(const float* vt, const int64_t* ft, int64_t Vt, int64_t F, int32_t R, int32_t* face, float* bary, void* stream);
+int sr_face_visibility(const int64_t* pix_to_face, const int64_t* faces, int64_t N, int64_t V, int64_t F, const float* xy_pix, const uint8_t* mask,
+                       int32_t H, int32_t W, uint8_t* visible, void* stream);
+int sr_view_alpha(const float* verts, const float* normals, const float* cam_pos, int64_t N, int64_t V, float* alpha, void* stream);
+int sr_texture_accumulate(int64_t T, const int32_t* tface, const float* tbary, const int64_t* faces, int64_t F, int64_t V, int32_t N,
+                          const uint8_t* visible, const float* alpha, const float* xy_pix, const float* images, int32_t H, int32_t W,
+                          const int32_t* fids, int32_t agg_num, float cosv0, float* slot_cos, float* slot_rgb, int32_t* slot_view, int32_t* count,
+                          float* min_cos, int32_t* min_idx, void* stream);
+int sr_texture_resolve(int64_t T, const int32_t* texel, int32_t agg_num, float cosv0, int32_t check_num, const float* slot_cos,
+                       const float* slot_rgb, const int32_t* slot_view, int32_t* count, uint8_t* mask_final, int32_t* view_id, float* tex_median,
+                       void* stream);
+int64_t sr_texture_fill_workspace_bytes(int32_t R);
+int sr_texture_fill(const float* tex_median, const uint8_t* mask_final, const uint8_t* tex_mask, int32_t R, int32_t dilate, float* texture,
+                    void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,10 +224,19 @@ SIGNATURES = {
     "sr_vertex_adjacency": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "sr_vertex_normals": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "sr_shade_phong": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sr_uv_rasterize": [_vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_face_visibility": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
+    "sr_view_alpha": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "sr_texture_accumulate": [_i64, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32,
+                              ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sr_texture_resolve": [_i64, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sr_texture_fill_workspace_bytes": [ctypes.c_int32],
+    "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
     "sr_pe_embed_bwd": [_vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp],
     "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
 }
-_RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64}
+_RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64,
+            "sr_texture_fill_workspace_bytes": _i64}
 
 _fn = {}
 for _name, _args in SIGNATURES.items():

@@ -309,6 +309,11 @@ class OptimNetwork(nn.Module):
             colors[~covered] = gts['image'].to(colors.device)[~covered][:, :3] * 255.
         return colors.cpu().numpy().astype(np.uint8), imgs, def1imgs, defMeshVs
 
+    def bake_texture(self, verts, faces, vt, ft, views, ratio=None, **kwargs):
+        """The texture stage (texture_mesh_prepare.py + texture_mesh_extract.py) for a UV-mapped template: see texture.bake_texture."""
+        from ..texture import bake_texture
+        return bake_texture(self, verts, faces, vt, ft, views, ratio, **kwargs)
+
     def _shaded_previews(self, TmpVs, Tmpfs, ratio, frame_ids, defV, frags, gts):
         """imgs / def1imgs of the reference's infer (network.py:306-337): HardPhongShader with pytorch3d 0.4.0's defaults (ops.shade_phong).
         imgs: the posed template `defV` as the frame cameras rasterised it into `frags`, light at (0, 1, 0); with `gts`: RGB only, and

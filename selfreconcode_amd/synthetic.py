@@ -192,6 +192,26 @@ def cube_sphere(n):
     return torch.from_numpy(dirs).float(), torch.from_numpy(faces.astype(np.int64))
 
 
+def per_face_atlas(F, resolution=1680, margin=0.5):
+    """A UV atlas for templates that carry none (marching cubes gives no UVs, and the reference leaves unwrapping to the user): face i
+    gets one half of cell i // 2 of an n x n grid over [0,1]^2, n = ceil(sqrt(F / 2)), each triangle inset by `margin` texels of a
+    `resolution`^2 texture so that no texel centre is claimed by two faces.  Returns vt [3 F, 2] float32 and ft [F, 3] int64
+    (ft = arange(3 F)).  A test and measurement aid, NOT a parameterisation to ship: no two faces share an edge in UV space, every seam
+    is visible, and half of the atlas is margin at the full-size template."""
+    F = int(F)
+    n = max(int(np.ceil(np.sqrt(F / 2.0))), 1)
+    s, m = 1.0 / n, float(margin) / float(resolution)
+    if not s > 3.0 * m:
+        raise ValueError(f"per_face_atlas: {F} faces leave cells of {s * resolution:.2f} texels, too small for a margin of {margin}")
+    i = np.arange(F)
+    cell, half = i // 2, i % 2
+    x0, y0 = (cell % n) * s, (cell // n) * s
+    lower = np.stack([np.stack([x0 + m, y0 + m], -1), np.stack([x0 + s - 2 * m, y0 + m], -1), np.stack([x0 + m, y0 + s - 2 * m], -1)], 1)
+    upper = np.stack([np.stack([x0 + s - m, y0 + s - m], -1), np.stack([x0 + 2 * m, y0 + s - m], -1), np.stack([x0 + s - m, y0 + 2 * m], -1)], 1)
+    vt = np.where((half == 0)[:, None, None], lower, upper).reshape(-1, 2)
+    return torch.from_numpy(vt.astype(np.float32)), torch.arange(3 * F, dtype=torch.long).view(F, 3)
+
+
 # ------------------------------------------------------------------------------------------------
 # Synthetic sequence + scene builder (SURVEY.md 8(d) cfg2/cfg3): the tensor contract of
 # dataset/dataset.py (poses / trans / per-frame codes as dense learnable tensors, one camera),

@@ -1,0 +1,171 @@
+"""Texture baking: the third stage of the reference pipeline (train, infer, texture) -- texture_mesh_prepare.py +
+texture_mesh_extract.py -- for a UV-mapped template, on the GPU.
+
+The reference's scripts hand the unwrap and the per-view partial textures to opendr and VideoAvatar's Isomapper and the final fill to
+cv2; none of them is part of the reference repository.  What the script computes with them is restated here (restated,
+unpinned):
+
+  1. frames      fids = ceil(arange(num) frame_num / num); per frame the posed vertices deformer(verts, [d_cond, [poses, trans]]).
+  2. texel map   texel (r, c), centre u = (c + 0.5) / R, v = 1 - (r + 0.5) / R, belongs to the lowest-indexed UV triangle containing it.
+  3. visible[f]  the face owns a pixel of the rasterised posed mesh and its three vertices round onto set mask pixels.
+  4. alpha[v]    max(0, dot(normalize(p_v - cam_pos), -n_v)).
+  5. per texel   cosv = UV-barycentric blend of alpha (0 on a hidden face); colour = bilinear sample of the image at the (affine) blend
+                 of the vertices' pixel positions.
+  6. slots       agg_num per texel, starting at cos(normal_ang); cosv > min(slots): the first slot holding the minimum takes the view.
+  7. resolve     count, mask_final = count >= check_num, view_id of the best slot, tex_median = per-channel median of the filled slots.
+  8. fill        push-pull into dilate(tex_mask, int(0.1 R)) - mask_final.  The reference inpaints that region with cv2.INPAINT_TELEA;
+                 this is a different, documented algorithm (texture_ops.fill), not Telea's pixels.
+
+Files written by `export_texture`, as texture_mesh_extract.py names them: tex_mask.png, mask_final.png, tex_median.png, texture.png
+(uint8(x 255)), view_id.npy and tex_predata.npz (vt, ft, tmpvs, fs, defVs, fids; the opendr camera entries are not written).
+UV unwrapping of the marching-cubes template is left to the user, as in the reference (template/uvmap.obj).
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from .infer_export import write_png
+from .ops import rasterize_meshes, vertex_adjacency, vertex_normals
+from .texture_ops import TextureAccumulator, face_visibility, fill, uv_texel_map, view_alpha
+
+FULL_RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
+
+BakedTexture = namedtuple("BakedTexture", "tex_mask mask_final count view_id tex_median texture fids def_verts")
+
+
+def texture_frames(frame_num, num=120):
+    """The frame ids texture_mesh_prepare.py:81 bakes from: `num` ids spread over `frame_num` frames."""
+    return np.ceil(np.arange(int(num)) * int(frame_num) * 1. / int(num)).astype(np.int64)
+
+
+def _obj_index(tok, n, what, line):
+    i = int(tok)
+    i = i - 1 if i > 0 else n + i
+    if not 0 <= i < n:
+        raise ValueError(f"{what} index {tok} out of range in '{line}'")
+    return i
+
+
+def read_obj_uv(path):
+    """(verts [V,3] float32, faces [F,3] int64, vt [Vt,2] float32, ft [F,3] int64) of a Wavefront OBJ with `v`, `vt` and triangular
+    `f a/b[/c]` lines (what template/uvmap.obj holds).  Faces with more than three corners or without texture indices raise."""
+    v, vt, f, ft = [], [], [], []
+    with open(path) as fh:
+        lines = [ln.strip() for ln in fh]
+    for ln in lines:
+        tok = ln.split()
+        if not tok or tok[0] not in ("v", "vt", "f"):
+            continue
+        if tok[0] == "v":
+            v.append([float(x) for x in tok[1:4]])
+        elif tok[0] == "vt":
+            vt.append([float(x) for x in tok[1:3]])
+    for ln in lines:
+        tok = ln.split()
+        if not tok or tok[0] != "f":
+            continue
+        if len(tok) != 4:
+            raise ValueError(f"{path}: only triangles are supported, got '{ln}'")
+        a, b = [], []
+        for corner in tok[1:]:
+            parts = corner.split("/")
+            if len(parts) < 2 or not parts[1]:
+                raise ValueError(f"{path}: face corner without a texture index in '{ln}'")
+            a.append(_obj_index(parts[0], len(v), "vertex", ln)); b.append(_obj_index(parts[1], len(vt), "texture", ln))
+        f.append(a); ft.append(b)
+    if not v or not f or not vt:
+        raise ValueError(f"{path}: no vertices, texture coordinates or faces")
+    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3), np.asarray(vt, np.float32).reshape(-1, 2),
+            np.asarray(ft, np.int64).reshape(-1, 3))
+
+
+def write_obj_uv(path, verts, faces, vt, ft):
+    """The OBJ `read_obj_uv` reads: `v x y z`, `vt u v`, `f a/ta b/tb c/tc` (1-based)."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3); t = np.asarray(vt, np.float32).reshape(-1, 2)
+    f = np.asarray(faces, np.int64).reshape(-1, 3); g = np.asarray(ft, np.int64).reshape(-1, 3)
+    if f.shape != g.shape:
+        raise ValueError(f"faces {f.shape} and ft {g.shape} must correspond one to one")
+    with open(path, "w") as fh:
+        fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+        fh.writelines("vt %.9g %.9g\n" % tuple(p) for p in t.tolist())
+        fh.writelines("f %d/%d %d/%d %d/%d\n" % (a[0] + 1, b[0] + 1, a[1] + 1, b[1] + 1, a[2] + 1, b[2] + 1) for a, b in zip(f.tolist(), g.tolist()))
+
+
+def _bake_batch(net, acc, adj, verts, faces, ratio, batch):
+    device = verts.device
+    fids = torch.tensor([int(b[0]) for b in batch], dtype=torch.long, device=device)
+    images = torch.stack([torch.as_tensor(b[1]).to(device=device, dtype=torch.float32) for b in batch])
+    masks = torch.stack([torch.as_tensor(b[2]).to(device) != 0 for b in batch])
+    N = fids.numel()
+    cameras, H, W = net._cameras(N, device)
+    if tuple(images.shape) != (N, H, W, 3) or tuple(masks.shape) != (N, H, W):
+        raise ValueError(f"bake_texture: images {tuple(images.shape)} / masks {tuple(masks.shape)} for the dataset's {H} x {W} camera")
+    with torch.no_grad():
+        poses, trans, d_cond, _ = [t.detach() for t in net.dataset.get_grad_parameters(fids, device)]
+        defV = net.deformer(verts[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio).detach().contiguous()
+        xy_ndc, z = cameras.project_ndc(defV)
+        frags = rasterize_meshes(xy_ndc, z, faces, H, W)
+        xy_pix, _ = cameras.project(defV)
+        alpha = view_alpha(defV, vertex_normals(defV, faces, adj), cameras.cam_pos().detach())
+        visible = face_visibility(frags.pix_to_face[..., 0], faces, xy_pix, masks)
+        acc.accumulate(fids, visible, alpha, xy_pix, images)
+    return defV
+
+
+def bake_texture(net, verts, faces, vt, ft, views, ratio=None, resolution=1680, agg_num=50, normal_ang=68., check_num=5, batch=8):
+    """Bakes the texture of the UV-mapped template (verts [V,3], faces [F,3], vt [Vt,2], ft [F,3]; GPU tensors) from `views`, an iterable
+    of (frame_id, image [H,W,3] float in [0,1], mask [H,W] bool) in frame order -- the channel order of the images is carried through
+    untouched.  Each view poses the template with the trained deformer (all ratios 1 unless `ratio` is given), rasterises it under the
+    dataset's camera and feeds the accumulator; `batch` views share one set of launches.  Returns BakedTexture of numpy arrays: tex_mask,
+    mask_final [R,R] bool, count, view_id [R,R] int32, tex_median, texture [R,R,3] float32, fids [K], def_verts [K,V,3]."""
+    from . import _lib
+    _lib.require_gpu(verts, faces, vt, ft)
+    ratio = ratio or FULL_RATIO
+    verts = verts.detach().contiguous().float()
+    faces = faces.long().contiguous()
+    if tuple(ft.shape) != tuple(faces.shape):
+        raise ValueError(f"bake_texture: ft {tuple(ft.shape)} and faces {tuple(faces.shape)} must correspond one to one")
+    tmap = uv_texel_map(vt, ft, resolution)
+    acc = TextureAccumulator(tmap, faces, agg_num, normal_ang)
+    adj = vertex_adjacency(faces, verts.shape[0])
+    fids, defVs, pending = [], [], []
+    for view in views:
+        pending.append(view)
+        if len(pending) == int(batch):
+            defVs.append(_bake_batch(net, acc, adj, verts, faces, ratio, pending).cpu())
+            fids += [int(b[0]) for b in pending]
+            pending = []
+    if pending:
+        defVs.append(_bake_batch(net, acc, adj, verts, faces, ratio, pending).cpu())
+        fids += [int(b[0]) for b in pending]
+    if not fids:
+        raise ValueError("bake_texture: no views")
+    res = acc.resolve(check_num)
+    tex_mask = tmap.face >= 0
+    texture = fill(res.tex_median, res.mask_final, tex_mask)
+    return BakedTexture(tex_mask.cpu().numpy(), res.mask_final.cpu().numpy(), res.count.cpu().numpy(), res.view_id.cpu().numpy(),
+                        res.tex_median.cpu().numpy(), texture.cpu().numpy(), np.asarray(fids, np.int64), torch.cat(defVs).numpy())
+
+
+def _u8(x):
+    return np.uint8(np.clip(np.asarray(x, np.float32), 0., 1.) * 255)
+
+
+def export_texture(net, obj_path, views, out_root, ratio=None, resolution=1680, agg_num=50, normal_ang=68., check_num=5, device=None):
+    """texture_mesh_prepare.py + texture_mesh_extract.py: reads the UV-mapped template `obj_path` (template/uvmap.obj), bakes it from
+    `views` (see bake_texture) and writes tex_mask.png, mask_final.png, tex_median.png, texture.png, view_id.npy and tex_predata.npz under
+    `out_root`.  Returns the BakedTexture."""
+    v, f, vt, ft = read_obj_uv(obj_path)
+    device = device or net.dataset.device
+    baked = bake_texture(net, torch.from_numpy(v).to(device), torch.from_numpy(f).to(device), torch.from_numpy(vt).to(device),
+                         torch.from_numpy(ft).to(device), views, ratio, resolution, agg_num, normal_ang, check_num)
+    os.makedirs(out_root, exist_ok=True)
+    write_png(os.path.join(out_root, "tex_mask.png"), _u8(baked.tex_mask))
+    write_png(os.path.join(out_root, "mask_final.png"), _u8(baked.mask_final))
+    write_png(os.path.join(out_root, "tex_median.png"), _u8(baked.tex_median))
+    write_png(os.path.join(out_root, "texture.png"), _u8(baked.texture))
+    np.save(os.path.join(out_root, "view_id.npy"), baked.view_id)
+    np.savez(os.path.join(out_root, "tex_predata.npz"), vt=vt, ft=ft, tmpvs=v, fs=f, defVs=baked.def_verts, fids=baked.fids)
+    return baked
