@@ -540,6 +540,22 @@ int64_t sr_texture_fill_workspace_bytes(int32_t R);
 int sr_texture_fill(const float* tex_median, const uint8_t* mask_final, const uint8_t* tex_mask, int32_t R, int32_t dilate, float* texture,
                     void* workspace, void* stream);
 
+/* Skinning-weight field of a body mesh (csrc/lbsw.hip): compute_lbswField + smooth_weights of model/Deformer.py:235-284.
+ *   sr_lbsw_knn_blend: field [nj,D,H,W] (channel-major, W fastest) over the box [bmin, bmax] (host float[3] each).  Voxel (w, h, d) has
+ *     centre ((w + 1/2) / W) (bmax - bmin) + bmin per axis, or (w / (W - 1)) ... with align_corners (every size >= 2 then).  Its value
+ *     is the blend of the rows of vert_ws [nv,nj] of the k nearest of verts [nv,3], weighted by 1 / clamp(distance, 1e-4, 1) and
+ *     normalised over the k.  "Nearest" orders the vertices by (squared float32 distance to the float32 centre, vertex index): of
+ *     equal distances the LOWER VERTEX INDEX wins (torch.topk, which the reference calls, promises no order among ties).  The
+ *     selected distances are re-evaluated in double for the weights.  1 <= k <= min(SR_LBSW_MAX_K, nv), else SR_EINVAL.
+ *   sr_lbsw_smooth: one Jacobi step src -> dst (distinct buffers, both [nj,D,H,W]): interior voxels become mean6 + 0.7 (w - mean6) of
+ *     the OLD field, then every voxel, border included, is divided by its sum over the channels.  A grid without interior (a size
+ *     < 3) is only renormalised.  No truncation of small weights (Deformer.py:243 has it commented out).
+ * Neither uses atomics: two calls give identical bits. */
+#define SR_LBSW_MAX_K 32
+int sr_lbsw_knn_blend(const float* verts, const float* vert_ws, int64_t nv, int32_t nj, int32_t k, int32_t W, int32_t H, int32_t D,
+                      const float* bmin, const float* bmax, int32_t align_corners, float* field, void* stream);
+int sr_lbsw_smooth(const float* src, float* dst, int32_t nj, int32_t W, int32_t H, int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,8 @@ SIGNATURES = {
     "sr_texture_resolve": [_i64, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_texture_fill_workspace_bytes": [ctypes.c_int32],
     "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_lbsw_knn_blend": [_vp, _vp, _i64] + [ctypes.c_int32] * 5 + [_vp, _vp, ctypes.c_int32, _vp, _vp],
+    "sr_lbsw_smooth": [_vp, _vp] + [ctypes.c_int32] * 4 + [_vp],
     "sr_pe_embed_bwd": [_vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp],
     "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
 }

@@ -575,3 +575,54 @@ def translator_value_jacobian(tr, ps, conds, batch_inds, ratio):
             ds_.append(d_f); Js_.append(J_f)
         return torch.stack(ds_, 0), torch.cat(Js_, 0)
     return TranslatorValueJacobian.apply(tr, r, ps, conds, index, seg, None, *Ws, *bs)
+
+
+# ------------------------------------------------------------------------------------------------
+# The skinning-weight volume of a body mesh (model/Deformer.py:235-295), on csrc/lbsw.hip
+def smooth_weights(weights, times=3):
+    """`times` Jacobi steps on weights [1,nj,D,H,W]: interior voxels move to mean6 + 0.7 (w - mean6) of the old field, then every
+    voxel is divided by its channel sum (Deformer.py:235-244; no truncation of small weights).  Returns a new tensor and leaves the
+    argument as it was (the reference overwrites the interior of its argument during the first step); times = 0 returns it."""
+    from .. import ops
+    _lib.require_gpu(weights)
+    if weights.dim() != 5 or weights.shape[0] != 1:
+        raise ValueError(f"smooth_weights: weights [1,nj,D,H,W] expected, got {tuple(weights.shape)}")
+    if int(times) <= 0:
+        return weights
+    return ops.lbsw_smooth(weights.detach()[0].contiguous().float(), times).unsqueeze(0)
+
+
+def _three(v):
+    if torch.is_tensor(v):
+        v = v.detach().cpu().numpy()
+    return [float(x) for x in np.asarray(v, dtype=np.float32).reshape(3)]
+
+
+def compute_lbswField(bmins, bmaxs, resolutions, smpl_verts, smpl_ws, align_corners=False, mean_neighbor=5, smooth_times=30):
+    """ws [1,nj,D,H,W] of the box [bmins, bmaxs] sampled at resolutions = (W, H, D): per voxel centre the inverse-distance blend of
+    the skinning weights smpl_ws [nv,nj] of the mean_neighbor (<= 32) nearest of smpl_verts [nv,3], then smooth_times Jacobi steps
+    (Deformer.py:246-284).  Among equally distant vertices the lower index wins."""
+    from .. import ops
+    _lib.require_gpu(smpl_verts, smpl_ws)
+    field = ops.lbsw_knn_blend(smpl_verts, smpl_ws, _three(bmins), _three(bmaxs), resolutions, mean_neighbor, align_corners)
+    return ops.lbsw_smooth(field, smooth_times, consume=True).unsqueeze(0)
+
+
+LBS_BOX_MARGIN = (0.15, 0.15, 0.20)
+
+
+def initial_lbs_skinner(verts, skin_weights, Js, parents, init_pose, resolution, bmins=None, bmaxs=None):
+    """The reference's initialLBSkinner (Deformer.py:286-295) without the SMPL evaluation, which is the caller's: verts [nv,3] are the
+    body's vertices in the pose `init_pose` [24,3], skin_weights [nv,24] their skinning weights, Js [24,3] the rest joints.  Without a
+    box the adaptive one is used (min/max of the vertices -/+ LBS_BOX_MARGIN).  The field is built with 30 neighbours and 30 smoothing
+    steps at resolution = (W, H, D); returns the LBSkinner on the device of `verts`."""
+    _lib.require_gpu(verts, skin_weights)
+    if bmins is None or bmaxs is None:
+        margin = np.array(LBS_BOX_MARGIN, dtype=np.float32)
+        bmins = (verts.min(0)[0].cpu().numpy() - margin).tolist()
+        bmaxs = (verts.max(0)[0].cpu().numpy() + margin).tolist()
+    ws = compute_lbswField(bmins, bmaxs, resolution, verts, skin_weights, align_corners=False, mean_neighbor=30, smooth_times=30)
+    pose = torch.from_numpy(init_pose.astype(np.float32)) if isinstance(init_pose, np.ndarray) else init_pose.detach().float().cpu()
+    skinner = LBSkinner(ws, _three(bmins), _three(bmaxs), torch.as_tensor(Js).detach().float().cpu(), np.asarray(parents), init_pose=pose,
+                        align_corners=False)
+    return skinner.to(verts.device)

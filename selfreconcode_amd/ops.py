@@ -183,3 +183,45 @@ def shade_phong(verts, normals, faces, frags, cam_pos, light_loc=PHONG_LIGHT, am
         _lib.call("sr_shade_phong", _lib.ptr(v), _lib.ptr(n), _lib.ptr(faces), N, v.shape[1], faces.shape[0], H, W, _lib.ptr(p2f), _lib.ptr(bary),
                   _lib.ptr(cam), _lib.ptr(light), coeffs, _lib.ptr(rgba), _lib.stream_of(v))
     return rgba
+
+
+# ------------------------------------------------------------------ skinning-weight field of a body mesh (csrc/lbsw.hip)
+LBSW_MAX_K = 32
+
+
+def lbsw_knn_blend(verts, vert_ws, bmin, bmax, resolutions, k, align_corners=False):
+    """field [nj,D,H,W] float32 (sr_lbsw_knn_blend): per voxel centre of the (W, H, D) = `resolutions` grid over [bmin, bmax] (three
+    floats each) the inverse-distance blend of the rows of vert_ws [nv,nj] of the k nearest of verts [nv,3]; of equal distances the
+    lower vertex index wins.  Two calls give identical bits."""
+    _lib.require_gpu(verts, vert_ws)
+    if verts.dim() != 2 or verts.shape[1] != 3 or vert_ws.dim() != 2 or vert_ws.shape[0] != verts.shape[0]:
+        raise ValueError(f"lbsw_knn_blend: verts [nv,3] and vert_ws [nv,nj] expected, got {tuple(verts.shape)} / {tuple(vert_ws.shape)}")
+    W, H, D = (int(r) for r in resolutions)
+    v = verts.detach().contiguous().float(); ws = vert_ws.detach().to(v.device).contiguous().float()
+    nv, nj = ws.shape
+    if not 1 <= int(k) <= min(LBSW_MAX_K, nv):
+        raise ValueError(f"lbsw_knn_blend: k = {k} neighbours of {nv} vertices (1 <= k <= min({LBSW_MAX_K}, nv))")
+    lo = (ctypes.c_float * 3)(*[float(x) for x in bmin]); hi = (ctypes.c_float * 3)(*[float(x) for x in bmax])
+    field = torch.empty((nj, D, H, W), dtype=torch.float32, device=v.device)
+    with _lib.on_device(v.device):
+        _lib.call("sr_lbsw_knn_blend", _lib.ptr(v), _lib.ptr(ws), nv, nj, int(k), W, H, D, lo, hi, int(bool(align_corners)), _lib.ptr(field),
+                  _lib.stream_of(v))
+    return field
+
+
+def lbsw_smooth(field, times, consume=False):
+    """`times` Jacobi steps of sr_lbsw_smooth on field [nj,D,H,W] (float32, contiguous), ping-pong between two buffers; `consume`
+    lets the input be one of them.  times = 0 returns the input."""
+    _lib.require_gpu(field)
+    if field.dim() != 4 or field.dtype != torch.float32 or not field.is_contiguous():
+        raise ValueError(f"lbsw_smooth: contiguous float32 field [nj,D,H,W] expected, got {tuple(field.shape)} {field.dtype}")
+    nj, D, H, W = field.shape
+    src, pool = field, [None, field if consume else None]            # the two destinations, taken in turn
+    with _lib.on_device(field.device):
+        for t in range(int(times)):
+            if pool[t % 2] is None:
+                pool[t % 2] = torch.empty_like(field)
+            dst = pool[t % 2]
+            _lib.call("sr_lbsw_smooth", _lib.ptr(src), _lib.ptr(dst), nj, W, H, D, _lib.stream_of(field))
+            src = dst
+    return src

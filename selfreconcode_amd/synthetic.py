@@ -104,6 +104,33 @@ def synthetic_lbs_volume(shape_dhw=(65, 225, 129), device="cpu", chunk=1 << 20):
     return w.t().reshape(1, 24, D, H, W).contiguous()
 
 
+def synthetic_body(nv=6890, seed=0):
+    """A deterministic stand-in for a posed SMPL body (no SMPL mesh ships here): verts [nv,3] on capsules of radius 0.05-0.09 around
+    the 23 bones of synthetic_joints(), and skinning weights [nv,24] = exp(-|v - J_j|^2 / 0.08^2) with the entries below 1e-3 of the
+    row maximum zeroed and the rows normalised.  A test and timing aid for the skinning-field builder, not a body model."""
+    J = synthetic_joints().numpy().astype(np.float64)
+    u = det_array((nv, 6), 700 + seed, 1.0, np.float64)
+    bone = np.arange(nv) % 23
+    child, parent = bone + 1, np.array(SMPL_PARENTS)[bone + 1]
+    a, b = J[parent], J[child]
+    axis = (b - a) / np.linalg.norm(b - a, axis=1, keepdims=True)
+    radius = (0.05 + 0.04 * bone / 22.0)[:, None]
+    n = u[:, :3] + 1e-3
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    along = (n * axis).sum(1, keepdims=True)
+    side = n - along * axis
+    side /= np.maximum(np.linalg.norm(side, axis=1, keepdims=True), 1e-9)
+    t = (0.5 * (u[:, 3:4] + 1.0))
+    on_side = a + t * (b - a) + radius * side                                  # the cylinder
+    on_cap = np.where(along >= 0, b, a) + radius * n                           # the two half spheres
+    verts = np.where(u[:, 4:5] < 0.6, on_side, on_cap).astype(np.float32)
+    d2 = ((verts.astype(np.float64)[:, None, :] - J[None]) ** 2).sum(-1)
+    w = np.exp(-d2 / 0.08 ** 2)
+    w[w < 1e-3 * w.max(1, keepdims=True)] = 0.0
+    w /= w.sum(1, keepdims=True)
+    return torch.from_numpy(verts), torch.from_numpy(w.astype(np.float32))
+
+
 def det_normal(shape, seed, std=1.0, mean=0.0):
     """Approximately normal (Irwin-Hall, 4 uniforms): adds/muls only, so bit-reproducible."""
     s = sum(det_array(shape, seed * 4 + k, 1.0, np.float64) for k in range(4)) * (np.sqrt(3.0) / 2.0)

@@ -52,3 +52,26 @@ def set_hierarchical_config(conf, name, optNet, dataloader, resolutions):
                                   align_corners=False, balance_value=0.0,
                                   use_cuda_impl=getattr(optNet.engine, 'use_cuda_impl', True)).to(optNet.engine.b_min.device)
     return optNet, dataloader
+
+
+INITIAL_SKINNER_KEYS = ('ws', 'bmins', 'bmaxs', 'Js', 'parents', 'init_pose', 'tmpBodyVs', 'tmpBodyFs')
+
+
+def save_initial_skinner(path, skinner, tmpBodyVs=None, tmpBodyFs=None):
+    """The cache file `initial_skinner_<pose_type>.pth` of getOptNet (model/network.py:851-854), same keys: the skinner's volume, box,
+    joints, parents (a numpy array, as smpl.parents is) and inverse rest chain, plus the body mesh the reference keeps beside them
+    (None when the caller has none).  Tensors are stored on the CPU in plain NCDHW layout."""
+    import numpy as np
+    def cpu(t):
+        return None if t is None else t.detach().cpu().contiguous()
+    torch.save({'ws': cpu(skinner.ws), 'bmins': cpu(skinner.b_min), 'bmaxs': cpu(skinner.b_max), 'Js': cpu(skinner.Js),
+                'parents': np.asarray(skinner.parents), 'init_pose': cpu(skinner.init_pose), 'tmpBodyVs': cpu(tmpBodyVs),
+                'tmpBodyFs': cpu(tmpBodyFs)}, path)
+
+
+def load_initial_skinner(path):
+    """(skinner, tmpBodyVs, tmpBodyFs) from a cache file written by save_initial_skinner or by the reference (network.py:843-846)."""
+    from ..model.Deformer import LBSkinner
+    data = torch.load(path, map_location='cpu', weights_only=False)
+    skinner = LBSkinner(data['ws'], data['bmins'], data['bmaxs'], data['Js'], data['parents'], init_pose=data['init_pose'], align_corners=False)
+    return skinner, data['tmpBodyVs'], data['tmpBodyFs']
