@@ -556,6 +556,27 @@ int sr_lbsw_knn_blend(const float* verts, const float* vert_ws, int64_t nv, int3
                       const float* bmin, const float* bmax, int32_t align_corners, float* field, void* stream);
 int sr_lbsw_smooth(const float* src, float* dst, int32_t nj, int32_t W, int32_t H, int32_t D, void* stream);
 
+/* Mesh regularisers of the template step (csrc/mesh_reg.hip): mesh_laplacian_smoothing(method='uniform'), mesh_edge_loss and
+ * mesh_normal_consistency of pytorch3d 0.4.0 as model/network.py:655-670 calls them, restated, on one mesh of V vertices.
+ * Topology, int32, built once per remesh by mesh_losses.MeshTopology: nbr_row [V+1] / nbr [2E] the neighbour CSR (ascending per row),
+ * pairs [P,4] = (v0, v1, a, b) one row per pair of faces at an edge, pair_row [V+1] / pair_ent [4P] the CSR of the entries
+ * pair * 4 + slot per vertex (ascending per row).  `terms` is a set of SR_MESHREG_* bits; a term that is off is neither computed nor read.
+ *   sr_meshreg_fwd: out[3] = (lap, edge, nc), 0 for a term that is off.  lap_q [V,3] (lap), edge_g [V,3] (edge) and pair_g [P,4,3]
+ *     (normal; may be null when no gradient is wanted) receive what the backward gathers; workspace: sr_meshreg_workspace_bytes(V, P)
+ *     bytes, 8-byte aligned, not zeroed.  At most three launches.
+ *   sr_meshreg_bwd: grad [V,3] = g_lap d lap + g_edge d edge + g_nc d nc, the three cotangents read from DEVICE memory (one float each);
+ *     a null cotangent or a null buffer leaves that term out.  One launch, one thread per vertex, gathers only.
+ * No atomics: all sums run in a fixed order, two calls give identical bits. */
+#define SR_MESHREG_LAP 1
+#define SR_MESHREG_EDGE 2
+#define SR_MESHREG_NORMAL 4
+int64_t sr_meshreg_workspace_bytes(int64_t V, int64_t P);
+int sr_meshreg_fwd(const float* verts, int64_t V, const int32_t* nbr_row, const int32_t* nbr, int64_t E, const int32_t* pairs, int64_t P,
+                   int32_t terms, float target_length, float* lap_q, float* edge_g, float* pair_g, void* workspace, float* out, void* stream);
+int sr_meshreg_bwd(int64_t V, const int32_t* nbr_row, const int32_t* nbr, int64_t E, const int32_t* pair_row, const int32_t* pair_ent, int64_t P,
+                   const float* lap_q, const float* edge_g, const float* pair_g, const float* g_lap, const float* g_edge, const float* g_nc,
+                   float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,3 +10,13 @@ if _os.environ.get("SR_AUTOGRAD_CALLER_THREAD", "0") == "1":
     # (tests/test_trajectory_full_gpu.py) are pinned to the default order.
     import torch as _torch
     _torch.autograd.set_multithreading_enabled(False)
+
+# Public surface of the mesh regularisers (mesh_losses.py), resolved on first use: importing the package must not load the HIP library.
+_MESH_LOSSES = ("MeshTopology", "mesh_regularisers", "mesh_laplacian_smoothing", "mesh_edge_loss", "mesh_normal_consistency")
+
+
+def __getattr__(name):
+    if name in _MESH_LOSSES:
+        from . import mesh_losses
+        return getattr(mesh_losses, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

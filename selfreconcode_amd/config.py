@@ -95,10 +95,10 @@ def load_config(path):
         return parse_hocon(fh.read())
 
 
-def _loss(color, dct, pc_w, lap, defc_w, def_regu_w=0.1, sample_pix=None):
+def _loss(color, dct, pc_w, lap, defc_w, def_regu_w=0.1, sample_pix=None, edge=-10., norm=-0.001):
     d = Conf(color_weight=color, normal_weight=0.1, weighted_normal=True, grad_weight=1., offset_weight=0.,
              def_regu=Conf(weight=def_regu_w, c=0.5), dct_weight=dct,
-             pc_weight=Conf(weight=pc_w, laplacian_weight=lap, edge_weight=-10., norm_weight=-0.001,
+             pc_weight=Conf(weight=pc_w, laplacian_weight=lap, edge_weight=edge, norm_weight=norm,
                             def_consistent=Conf(weight=defc_w, c=0.01)))
     if sample_pix is not None:
         d['sample_pix_num'] = sample_pix

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 
 from .. import dist as srdist
 from .. import hostsync
+from .. import mesh_losses
 from .. import mlp_engine
 from .. import step_ops
 from ..ext import MCGpu
@@ -110,6 +111,7 @@ class OptimNetwork(nn.Module):
         self.angThred = None
         self.TmpVs = None
         self.Tmpfs = None
+        self._mesh_topo = None                # (Tmpfs, key, mesh_losses.MeshTopology) of the regularisers: see _mesh_topology
         self.forward_time = 0
         self.host_marks = None        # diagnostics (tools/host_profile.py): a list that receives (label, host time, event on the main stream)
         self.remesh_intersect = 30
@@ -232,6 +234,7 @@ class OptimNetwork(nn.Module):
         N = frame_ids.numel()
         if TmpVs is None:
             if self.TmpVs is None:
+                self._mesh_topo = None
                 self.TmpVs, self.Tmpfs = self.discretizeSDF(ratio, None, -self.sdfShrinkRadius)
                 self.TmpVs.requires_grad = True
                 self.TmpOptimizer = torch.optim.SGD([self.TmpVs], lr=0.05, momentum=0.9)
@@ -481,6 +484,17 @@ class OptimNetwork(nn.Module):
         self._mark('forward issued')
         return total_loss
 
+    def _mesh_topology(self):
+        """The template's MeshTopology, built on first use after every remesh.  Every place that replaces Tmpfs drops the cache; the
+        key (the faces tensor itself, its storage address, version and shape, the vertex count) guards callers that assign Tmpfs directly."""
+        f = self.Tmpfs
+        key = (f.data_ptr(), f._version, tuple(f.shape), self.TmpVs.shape[0])
+        hit = self._mesh_topo
+        if hit is None or hit[0] is not f or hit[1] != key:
+            # (faces that hold a -1 -- marching cubes writes them where the surface leaves the volume -- are padding to pytorch3d's Meshes)
+            hit = self._mesh_topo = (f, key, mesh_losses.MeshTopology.from_faces(f[(f >= 0).all(1)], self.TmpVs.shape[0]))
+        return hit[2]
+
     def _remesh_if_due(self, ratio, device):
         """On the main stream, every `remesh_intersect` calls: a pending stage switch, marching cubes (`remesh_events`), a new template."""
         if self.TmpVs is not None and self.Tmpfs is not None and self.forward_time % self.remesh_intersect != 0:
@@ -490,6 +504,7 @@ class OptimNetwork(nn.Module):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         self.update_hierarchical_config(device)          # a pending stage switch takes effect with this remesh (network.py:464)
+        self._mesh_topo = None                           # (the regularisers' topology belongs to the old faces)
         self.TmpVs, self.Tmpfs = self.discretizeSDF(ratio, None, -self.sdfShrinkRadius)
         if ev is not None:
             e1.record(); ev.append((e0, e1))
@@ -925,9 +940,17 @@ class OptimNetwork(nn.Module):
             mask_loss = (1. - (masks * gtMs).view(N, -1).sum(1) / (masks + gtMs - masks * gtMs).abs().view(N, -1).sum(1)).mean()
         self.info['pc_loss']['mask_loss'] = mask_loss.detach()
         loss = mask_loss * (self.conf.get_float('pc_weight.mask_weight') if 'pc_weight.mask_weight' in self.conf else 1.)
-        for name in ('laplacian_weight', 'edge_weight', 'norm_weight'):
-            if 'pc_weight' in self.conf and self.conf.get_float('pc_weight.' + name) > 0.:
-                raise NotImplementedError("pytorch3d mesh regularisers are disabled (negative weights) in every shipped config")
+        # mesh regularisers of the template (network.py:655-670; mesh_losses.py, restated -- DESIGN 3.12): only with a positive weight.
+        # With all three <= 0 (every shipped config) nothing below runs: no topology, no launch, no allocation.
+        regs = [self.conf.get_float('pc_weight.' + name) if 'pc_weight' in self.conf else -1. for name in ('laplacian_weight', 'edge_weight', 'norm_weight')]
+        if any(w > 0. for w in regs):
+            # (srdist: TmpVs and Tmpfs are bit-identical replicas, the kernels are deterministic, so this gradient is the same on every
+            # rank and the all_reduce_mean_ of TmpVs.grad below leaves it as it is)
+            terms = mesh_losses.mesh_regularisers(self.TmpVs, self._mesh_topology(), regs[0], regs[1], regs[2], target_length=0.)
+            for key, w, term in zip(('lap_loss', 'edge_loss', 'norm_loss'), regs, terms):
+                if w > 0.:
+                    self.info['pc_loss'][key] = term.detach()
+                    loss = loss + w * term
         cw = self.conf.get_float('pc_weight.def_consistent.weight') if 'pc_weight.def_consistent' in self.conf else -1.
         if cw > 0.:
             offset2 = defTmpVs - self.deformer.defs[1](self.TmpVs.view(1, -1, 3).expand(N, -1, 3), defconds[1])

@@ -225,3 +225,53 @@ def lbsw_smooth(field, times, consume=False):
             _lib.call("sr_lbsw_smooth", _lib.ptr(src), _lib.ptr(dst), nj, W, H, D, _lib.stream_of(field))
             src = dst
     return src
+
+
+# ------------------------------------------------------------------ mesh regularisers of the template step (csrc/mesh_reg.hip)
+MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = 1, 2, 4
+
+
+def _meshreg_i32(t, numel, name):
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"meshreg: {name} must be contiguous int32 with {numel} elements, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def meshreg_fwd(verts, nbr_row, nbr, pairs, terms, target_length=0., stage_grad=True):
+    """sr_meshreg_fwd on verts [V,3] float32 and the int32 topology of mesh_losses.MeshTopology (neighbour CSR nbr_row [V+1] / nbr [2E],
+    pair rows pairs [P,4]): -> (out [3] = (lap, edge, nc), saved) where `saved` = (lap_q, edge_g, pair_g) is what meshreg_bwd gathers
+    (None for a term that is off; pair_g also None without stage_grad).  `terms`: MESHREG_* bits; at most three launches, no host read."""
+    _lib.require_gpu(verts, nbr_row, nbr, pairs)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.dtype != torch.float32 or not verts.is_contiguous() or verts.shape[0] < 1:
+        raise ValueError(f"meshreg_fwd: contiguous float32 verts [V,3] expected, got {verts.dtype} {tuple(verts.shape)}")
+    V, E, P, terms = verts.shape[0], nbr.numel() // 2, pairs.shape[0], int(terms)
+    _meshreg_i32(nbr_row, V + 1, "nbr_row"); _meshreg_i32(nbr, 2 * E, "nbr"); _meshreg_i32(pairs, 4 * P, "pairs")
+    if not 0 < terms < 8 or not float(target_length) >= 0.:
+        raise ValueError(f"meshreg_fwd: terms = {terms} (a non-empty set of MESHREG_* bits), target_length = {target_length} (>= 0)")
+    dev = verts.device
+    lap_q = torch.empty_like(verts) if terms & MESHREG_LAP else None
+    edge_g = torch.empty_like(verts) if terms & MESHREG_EDGE else None
+    pair_g = torch.empty((P, 4, 3), dtype=torch.float32, device=dev) if terms & MESHREG_NORMAL and stage_grad and P > 0 else None
+    ws = torch.empty((max(1, _lib.raw("sr_meshreg_workspace_bytes")(V, P) // 8),), dtype=torch.float64, device=dev)
+    out = torch.empty((3,), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("sr_meshreg_fwd", _lib.ptr(verts), V, _lib.ptr(nbr_row), _lib.ptr(nbr), E, _lib.ptr(pairs), P, terms, float(target_length),
+                  _lib.ptr(lap_q), _lib.ptr(edge_g), _lib.ptr(pair_g), _lib.ptr(ws), _lib.ptr(out), _lib.stream_of(verts))
+    return out, (lap_q, edge_g, pair_g)
+
+
+def meshreg_bwd(saved, nbr_row, nbr, pair_row, pair_ent, num_verts, g_lap, g_edge, g_nc):
+    """grad [V,3] float32 (sr_meshreg_bwd) of g_lap lap + g_edge edge + g_nc nc from the buffers meshreg_fwd saved; the cotangents are
+    float32 DEVICE tensors of one element (or None: that term is left out) and are read by the kernel.  One launch, gathers only."""
+    lap_q, edge_g, pair_g = saved
+    _lib.require_gpu(nbr_row, nbr, pair_row, pair_ent, lap_q, edge_g, pair_g, g_lap, g_edge, g_nc)
+    V, E, P = int(num_verts), nbr.numel() // 2, pair_ent.numel() // 4
+    _meshreg_i32(nbr_row, V + 1, "nbr_row"); _meshreg_i32(nbr, 2 * E, "nbr"); _meshreg_i32(pair_row, V + 1, "pair_row"); _meshreg_i32(pair_ent, 4 * P, "pair_ent")
+    for t, n, name in ((lap_q, 3 * V, "lap_q"), (edge_g, 3 * V, "edge_g"), (pair_g, 12 * P, "pair_g"), (g_lap, 1, "g_lap"), (g_edge, 1, "g_edge"), (g_nc, 1, "g_nc")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise ValueError(f"meshreg_bwd: {name} must be contiguous float32 with {n} elements, got {t.dtype} {tuple(t.shape)}")
+    grad = torch.empty((V, 3), dtype=torch.float32, device=nbr_row.device)
+    with _lib.on_device(grad.device):
+        _lib.call("sr_meshreg_bwd", V, _lib.ptr(nbr_row), _lib.ptr(nbr), E, _lib.ptr(pair_row), _lib.ptr(pair_ent), P, _lib.ptr(lap_q), _lib.ptr(edge_g),
+                  _lib.ptr(pair_g), _lib.ptr(g_lap), _lib.ptr(g_edge), _lib.ptr(g_nc), _lib.ptr(grad), _lib.stream_of(grad))
+    return grad
