@@ -5,6 +5,7 @@ import pytest
 import torch
 from oracle import mc as mco
 from oracle import fixtures as fx
+from _interp2x_ref import interp2x_loop as _interp2x_numpy
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -129,30 +130,6 @@ def test_discretize_sdf_mlp_extracts_a_closed_surface():
     verts, faces = MCGpu.mc_gpu(vol[0, 0].permute(2, 1, 0).contiguous(), eng.spacing_x, eng.spacing_y, eng.spacing_z, eng.bx, eng.by, eng.bz, 0.)
     r = verts.norm(dim=1)
     assert faces.min() >= 0 and 0.3 < float(r.min()) and float(r.max()) < 0.9
-
-
-def _interp2x_numpy(a, bal):
-    """restatement of interp2x_boundary3d_kernel.cu:11-151 in numpy (float32 parent sums, division in double)."""
-    d, h, w = a.shape
-    D, H, W = 2 * d - 1, 2 * h - 1, 2 * w - 1
-    out = np.zeros((D, H, W), np.float32); bnd = np.zeros((D, H, W), bool)
-    for z in range(D):
-        for y in range(H):
-            for x in range(W):
-                zs = [z // 2] if z % 2 == 0 else [(z - 1) // 2, (z + 1) // 2]
-                ys = [y // 2] if y % 2 == 0 else [(y - 1) // 2, (y + 1) // 2]
-                xs = [x // 2] if x % 2 == 0 else [(x - 1) // 2, (x + 1) // 2]
-                if len(zs) == 2 and len(ys) == 2 and len(xs) == 2: order = [(zz, yy, xx) for zz in zs for yy in ys for xx in xs]
-                elif len(zs) == 1: order = [(zs[0], yy, xx) for yy in ys for xx in xs]
-                elif len(xs) == 1: order = [(zz, yy, xs[0]) for yy in ys for zz in zs]
-                else: order = [(zz, ys[0], xx) for xx in xs for zz in zs]
-                vals = [a[p] for p in order]
-                s = np.float32(vals[0])
-                for v in vals[1:]:
-                    s = np.float32(s + v)
-                out[z, y, x] = s if len(vals) == 1 else np.float32(np.float64(s) / len(vals))
-                bnd[z, y, x] = len({bool(v > bal) for v in vals}) > 1
-    return out, bnd
 
 
 def test_interp2x_boundary3d_forward_backward():
