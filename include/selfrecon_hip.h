@@ -556,6 +556,33 @@ int sr_lbsw_knn_blend(const float* verts, const float* vert_ws, int64_t nv, int3
                       const float* bmin, const float* bmax, int32_t align_corners, float* field, void* stream);
 int sr_lbsw_smooth(const float* src, float* dst, int32_t nj, int32_t W, int32_t H, int32_t D, void* stream);
 
+/* SMPL body model, forward only, float32 (csrc/smpl.hip): SMPL.forward / skeleton / avatar of smpl_pytorch/SMPL.py:93-173 with
+ * batch_rodrigues / batch_global_rigid_transformation of smpl_pytorch/util.py:35-103.  24 joints; all pointers are device memory
+ * unless named host_*.  No atomics: two calls give identical bits.
+ *   sr_smpl_shape:   v_shaped [B,nv,3] = v_template [nv,3] + sum_k beta [B,nbeta] shapedirs [nbeta, nv*3].
+ *   sr_smpl_regress: out [B,nk,3] = sum_v reg [nv,nk] x [B,nv,3], 3 nk <= 128.  Partial sums of 128 vertices in ascending order go
+ *     to `partial` (sr_smpl_regress_workspace_floats floats), a second launch adds them in ascending order.
+ *   sr_smpl_pose:    theta [B,24,3] axis-angle -> Rs [B,24,3,3] by the reference's route (|theta + 1e-8|, half-angle quaternion,
+ *     normalise, quat2mat); theta NULL: Rs is an input.  feature [B,207] = (Rs[:,1:] - I); the chain over host_parents [24]
+ *     (host_parents[i] < i for i > 0, entry 0 ignored) from the rest joints J [B,24,3] gives J_transformed [B,24,3] and
+ *     A [B,24,4,4] = G - pad(G [J;0]).
+ *   sr_smpl_skin:    verts [B,nv,3] = (sum_j weights [nv,24] A[b,j]) [v_posed; 1] with v_posed = rest[b,v] + posedirs [207,nv,3] .
+ *     feature[b]; rest is read at rest + b * rest_batch_stride (floats; 0 shares one mesh among the batch).  posedirs and feature
+ *     both NULL: v_posed = rest (SMPL.avatar).  One workgroup serves SR_SMPL_BATCH_TILE batch items of 128 vertices, so posedirs
+ *     is read once per batch tile.
+ * Limits (SR_EINVAL beyond them): the batch index is a grid's second dimension, so B <= 65535 for sr_smpl_shape and sr_smpl_regress
+ * and B <= 65535 * SR_SMPL_BATCH_TILE for sr_smpl_skin (a longer sequence is evaluated in slices); nv <= INT32_MAX / 4; for
+ * sr_smpl_regress also nv * nk and 3 * B * nk <= INT32_MAX. */
+#define SR_SMPL_BATCH_TILE 8
+int sr_smpl_shape(const float* v_template, const float* shapedirs, const float* beta, int32_t B, int32_t nbeta, int64_t nv, float* v_shaped,
+                  void* stream);
+int64_t sr_smpl_regress_workspace_floats(int32_t B, int64_t nv, int32_t nk);
+int sr_smpl_regress(const float* x, const float* reg, int32_t B, int64_t nv, int32_t nk, float* partial, float* out, void* stream);
+int sr_smpl_pose(const float* theta, float* Rs, const float* J, const int32_t* host_parents, int32_t B, float* feature, float* J_transformed,
+                 float* A, void* stream);
+int sr_smpl_skin(const float* rest, int64_t rest_batch_stride, const float* posedirs, const float* feature, const float* weights, const float* A,
+                 int32_t B, int64_t nv, float* verts, void* stream);
+
 /* Mesh regularisers of the template step (csrc/mesh_reg.hip): mesh_laplacian_smoothing(method='uniform'), mesh_edge_loss and
  * mesh_normal_consistency of pytorch3d 0.4.0 as model/network.py:655-670 calls them, restated, on one mesh of V vertices.
  * Topology, int32, built once per remesh by mesh_losses.MeshTopology: nbr_row [V+1] / nbr [2E] the neighbour CSR (ascending per row),

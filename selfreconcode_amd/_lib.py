@@ -234,6 +234,11 @@ SIGNATURES = {
     "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
     "sr_lbsw_knn_blend": [_vp, _vp, _i64] + [ctypes.c_int32] * 5 + [_vp, _vp, ctypes.c_int32, _vp, _vp],
     "sr_lbsw_smooth": [_vp, _vp] + [ctypes.c_int32] * 4 + [_vp],
+    "sr_smpl_shape": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _vp],
+    "sr_smpl_regress_workspace_floats": [ctypes.c_int32, _i64, ctypes.c_int32],
+    "sr_smpl_regress": [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_smpl_pose": [_vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
+    "sr_smpl_skin": [_vp, _i64, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp],
     "sr_meshreg_workspace_bytes": [_i64, _i64],
     "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
     "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,
@@ -241,7 +246,7 @@ SIGNATURES = {
     "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
 }
 _RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64,
-            "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64}
+            "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64, "sr_smpl_regress_workspace_floats": _i64}
 
 _fn = {}
 for _name, _args in SIGNATURES.items():

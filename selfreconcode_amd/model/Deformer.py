@@ -611,8 +611,21 @@ def compute_lbswField(bmins, bmaxs, resolutions, smpl_verts, smpl_ws, align_corn
 LBS_BOX_MARGIN = (0.15, 0.15, 0.20)
 
 
+def initialLBSkinner(gender, shape, pose, resolution, bmins=None, bmaxs=None, smpl=None):
+    """(skinner, verts [nv,3], faces [nf,3]) -- the reference's initialLBSkinner (Deformer.py:286-295): the body model of `gender`
+    (smpl_pytorch.getSMPL; or `smpl`, a constructed SMPL, in its place) evaluated at `shape` [10] for its rest joints and in `pose`
+    [24,3] for the body the skinning field is sampled from, then initial_lbs_skinner.  shape and pose are GPU tensors."""
+    from ..smpl_pytorch import getSMPL
+    _lib.require_gpu(shape, pose)
+    smpl = (smpl if smpl is not None else getSMPL(gender)).to(shape.device)
+    Js = smpl.skeleton(shape.view(1, -1), True)[0]
+    verts = smpl(shape.view(1, -1), pose.view(1, 24, 3), True)[0][0]
+    skinner = initial_lbs_skinner(verts, smpl.weight[0], Js.view(24, 3), smpl.parents, pose.view(24, 3), resolution, bmins, bmaxs)
+    return skinner, verts, smpl.faces_tensor.to(verts.device)
+
+
 def initial_lbs_skinner(verts, skin_weights, Js, parents, init_pose, resolution, bmins=None, bmaxs=None):
-    """The reference's initialLBSkinner (Deformer.py:286-295) without the SMPL evaluation, which is the caller's: verts [nv,3] are the
+    """The skinner of initialLBSkinner (Deformer.py:290-295) from an already evaluated body: verts [nv,3] are the
     body's vertices in the pose `init_pose` [24,3], skin_weights [nv,24] their skinning weights, Js [24,3] the rest joints.  Without a
     box the adaptive one is used (min/max of the vertices -/+ LBS_BOX_MARGIN).  The field is built with 30 neighbours and 30 smoothing
     steps at resolution = (W, H, D); returns the LBSkinner on the device of `verts`."""

@@ -227,6 +227,84 @@ def lbsw_smooth(field, times, consume=False):
     return src
 
 
+# ------------------------------------------------------------------ SMPL body model, forward only (csrc/smpl.hip)
+SMPL_BATCH_TILE = 8              # SR_SMPL_BATCH_TILE: batch items per workgroup of the skin kernel
+SMPL_NJ, SMPL_NPOSE = 24, 207
+
+
+def _smpl_f32(t, shape, name):
+    if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"smpl: {name} must be contiguous float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def smpl_shape(v_template, shapedirs, beta):
+    """v_shaped [B,nv,3] = v_template [nv,3] + beta [B,nbeta] . shapedirs [nbeta, nv*3] (sr_smpl_shape)."""
+    _lib.require_gpu(v_template, shapedirs, beta)
+    nv, (B, nbeta) = v_template.shape[0], beta.shape
+    _smpl_f32(v_template, (nv, 3), "v_template"); _smpl_f32(shapedirs, (nbeta, 3 * nv), "shapedirs"); _smpl_f32(beta, (B, nbeta), "beta")
+    out = torch.empty((B, nv, 3), dtype=torch.float32, device=beta.device)
+    with _lib.on_device(beta.device):
+        _lib.call("sr_smpl_shape", _lib.ptr(v_template), _lib.ptr(shapedirs), _lib.ptr(beta), B, nbeta, nv, _lib.ptr(out), _lib.stream_of(beta))
+    return out
+
+
+def smpl_regress(x, reg):
+    """out [B,nk,3] = sum_v reg [nv,nk] x [B,nv,3] in a fixed order (sr_smpl_regress)."""
+    _lib.require_gpu(x, reg)
+    B, nv, nk = x.shape[0], x.shape[1], reg.shape[1]
+    _smpl_f32(x, (B, nv, 3), "x"); _smpl_f32(reg, (nv, nk), "regressor")
+    n = _lib.raw("sr_smpl_regress_workspace_floats")(B, nv, nk)
+    if n < 0:
+        raise _lib.SrError("sr_smpl_regress_workspace_floats: bad argument")
+    partial = torch.empty((int(n),), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, nk, 3), dtype=torch.float32, device=x.device)
+    with _lib.on_device(x.device):
+        _lib.call("sr_smpl_regress", _lib.ptr(x), _lib.ptr(reg), B, nv, nk, _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(x))
+    return out
+
+
+def smpl_pose(J, parents, theta=None, Rs=None):
+    """(Rs [B,24,3,3], feature [B,207], J_transformed [B,24,3], A [B,24,4,4]) of the rest joints J [B,24,3] and either theta [B,24,3]
+    (axis-angle, the reference's quaternion route) or the rotations Rs themselves (sr_smpl_pose); parents: 24 host ints."""
+    _lib.require_gpu(J, theta, Rs)
+    B, dev = J.shape[0], J.device
+    _smpl_f32(J, (B, SMPL_NJ, 3), "J")
+    if (theta is None) == (Rs is None):
+        raise ValueError("smpl_pose: exactly one of theta and Rs")
+    if theta is not None:
+        _smpl_f32(theta, (B, SMPL_NJ, 3), "theta")
+        Rs = torch.empty((B, SMPL_NJ, 3, 3), dtype=torch.float32, device=dev)
+    else:
+        _smpl_f32(Rs, (B, SMPL_NJ, 3, 3), "Rs")
+    pa = (ctypes.c_int32 * SMPL_NJ)(*[max(int(p), 0) for p in parents])
+    feature = torch.empty((B, SMPL_NPOSE), dtype=torch.float32, device=dev)
+    Jt = torch.empty((B, SMPL_NJ, 3), dtype=torch.float32, device=dev)
+    A = torch.empty((B, SMPL_NJ, 4, 4), dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.call("sr_smpl_pose", _lib.ptr(theta), _lib.ptr(Rs), _lib.ptr(J), pa, B, _lib.ptr(feature), _lib.ptr(Jt), _lib.ptr(A), _lib.stream_of(J))
+    return Rs, feature, Jt, A
+
+
+def smpl_skin(rest, weights, A, posedirs=None, feature=None):
+    """verts [B,nv,3] (sr_smpl_skin): rest [B,nv,3], or [nv,3] shared by the batch; weights [nv,24]; A [B,24,4,4]; with posedirs
+    [207, nv*3] and feature [B,207] the pose blend shapes are added to `rest` first."""
+    _lib.require_gpu(rest, weights, A, posedirs, feature)
+    B, nv = A.shape[0], weights.shape[0]
+    _smpl_f32(A, (B, SMPL_NJ, 4, 4), "A"); _smpl_f32(weights, (nv, SMPL_NJ), "weight")
+    if rest.dim() == 2:
+        _smpl_f32(rest, (nv, 3), "rest vertices"); stride = 0
+    else:
+        _smpl_f32(rest, (B, nv, 3), "rest vertices"); stride = 3 * nv
+    if posedirs is not None:
+        _smpl_f32(posedirs, (SMPL_NPOSE, 3 * nv), "posedirs"); _smpl_f32(feature, (B, SMPL_NPOSE), "pose feature")
+    verts = torch.empty((B, nv, 3), dtype=torch.float32, device=A.device)
+    with _lib.on_device(A.device):
+        _lib.call("sr_smpl_skin", _lib.ptr(rest), stride, _lib.ptr(posedirs), _lib.ptr(feature), _lib.ptr(weights), _lib.ptr(A), B, nv, _lib.ptr(verts),
+                  _lib.stream_of(A))
+    return verts
+
+
 # ------------------------------------------------------------------ mesh regularisers of the template step (csrc/mesh_reg.hip)
 MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = 1, 2, 4
 

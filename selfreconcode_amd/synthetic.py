@@ -131,6 +131,30 @@ def synthetic_body(nv=6890, seed=0):
     return torch.from_numpy(verts), torch.from_numpy(w.astype(np.float32))
 
 
+def synthetic_smpl_model(nv=200, seed=0):
+    """A deterministic stand-in for a body-model file (the licensed ones never ship here): the dict of arrays a
+    `<gender>_smpl_with_cocoplus_reg` file holds, for nv vertices, with the real kinematic tree.  v_template is synthetic_body();
+    weights [nv,24] are peaked (exp(-|v - J_j|^2 / 0.12^2), below 1e-3 of the row maximum zeroed, rows sum to 1); J_regressor [nv,24]
+    and cocoplus_regressor [nv,19] are non-negative with columns that sum to 1 (the first concentrated near its joint); shapedirs
+    [nv,3,10] are uniform in +-0.03, posedirs [nv,3,207] in +-0.01; f is a small face list [min(nv, 64) - 2, 3].  All float32 / int64."""
+    verts, _ = synthetic_body(nv, seed)
+    v = verts.numpy().astype(np.float64)
+    J = synthetic_joints().numpy().astype(np.float64)
+    d2 = ((v[:, None, :] - J[None]) ** 2).sum(-1)                              # [nv,24]
+    w = np.exp(-d2 / 0.12 ** 2)
+    w[w < 1e-3 * w.max(1, keepdims=True)] = 0.0
+    w /= w.sum(1, keepdims=True)
+    jr = np.exp(-d2 / 0.10 ** 2) + 1e-6 * (1.0 + det_array((nv, 24), 710 + seed, 1.0, np.float64))
+    jr /= jr.sum(0, keepdims=True)
+    cr = 1.0 + det_array((nv, 19), 711 + seed, 1.0, np.float64) + 20.0 * np.exp(-d2[:, :19] / 0.2 ** 2)
+    cr /= cr.sum(0, keepdims=True)
+    nf = max(min(nv, 64) - 2, 1)
+    faces = np.stack([np.zeros(nf, np.int64), np.arange(1, nf + 1), np.arange(2, nf + 2) % nv], 1)
+    return {'v_template': verts.numpy().copy(), 'shapedirs': det_array((nv, 3, 10), 712 + seed, 0.03), 'J_regressor': jr.astype(np.float32),
+            'posedirs': det_array((nv, 3, 207), 713 + seed, 0.01), 'kintree_table': np.stack([np.array(SMPL_PARENTS, np.int64), np.arange(24)]),
+            'cocoplus_regressor': cr.astype(np.float32), 'weights': w.astype(np.float32), 'f': faces}
+
+
 def det_normal(shape, seed, std=1.0, mean=0.0):
     """Approximately normal (Irwin-Hall, 4 uniforms): adds/muls only, so bit-reproducible."""
     s = sum(det_array(shape, seed * 4 + k, 1.0, np.float64) for k in range(4)) * (np.sqrt(3.0) / 2.0)
