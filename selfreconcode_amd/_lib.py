@@ -288,6 +288,59 @@ def ptr(t):
     return 0 if t is None else t.data_ptr()
 
 
+def device_args(on, args):
+    """The flat C arguments of a launch anchored on tensor `on`: a tensor goes as its address, None as a null pointer, anything else
+    (ints, floats, ctypes arrays, structs, byref objects) as it is.  A tensor on another device than `on` is refused here -- behind
+    whatever require_gpu() the operator did on its own arguments -- instead of becoming a GPU fault."""
+    dev, out = on.device, []
+    for a in args:
+        if isinstance(a, torch.Tensor):
+            if a.device != dev:
+                raise RuntimeError(f"selfreconcode_amd: HIP operator called with a tensor on {a.device} in a launch on {dev} "
+                                   "(there is deliberately no CPU fallback)")
+            out.append(a.data_ptr())
+        elif a is None:
+            out.append(0)
+        else:
+            out.append(a)
+    return out
+
+
+def launch(name, on, *args):
+    """call(name, *args, stream): THE way to run a stream-taking entry point with flat arguments (see device_args) -- on the device
+    of tensor `on` and on torch's current stream there, which every kernel entry point takes last."""
+    flat = device_args(on, args)
+    with on_device(on.device):
+        call(name, *flat, stream_of(on))
+
+
+def workspace(name, *args, device, dtype=torch.uint8):
+    """Scratch for a kernel whose size function is `name(*args)` (in elements of `dtype`; negative: an error code -> SrError): at
+    least one element, 256-byte aligned.  The result is a view into a slightly larger allocation and is itself what to pass and save."""
+    n = _fn[name](*args)
+    if n < 0:
+        raise SrError(f"{name} failed: {_CODES.get(n, n)}")
+    n, per = max(int(n), 1), 256 // dtype.itemsize
+    buf = torch.empty((n + per,), dtype=dtype, device=device)
+    off = (-buf.data_ptr()) % 256 // dtype.itemsize
+    return buf[off:off + n]
+
+
+def f32c(t):
+    """t.detach().contiguous().float() without the conversions that would be no-ops (each is a dispatcher round trip)."""
+    t = t.detach()
+    if t.dtype != torch.float32:
+        t = t.float()
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def i64c(t):
+    t = t.detach()
+    if t.dtype != torch.int64:
+        t = t.long()
+    return t if t.is_contiguous() else t.contiguous()
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

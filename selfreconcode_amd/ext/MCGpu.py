@@ -29,16 +29,13 @@ def mc_gpu(sdfs, xstep=1.0, ystep=1.0, zstep=1.0, xmin=0.0, ymin=0.0, zmin=0.0, 
     if nx <= 0 or ny <= 0 or nz <= 0:
         return []
     dev = sdfs.device
-    with _lib.on_device(dev):
-        st = _lib.stream_of(sdfs)
-        nbytes = _lib.raw("sr_mc_workspace_bytes")(nx, ny, nz)
-        ws = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
-        counts = torch.zeros((2,), dtype=torch.int32, device=dev)
-        _lib.call("sr_mc_count", _lib.ptr(sdfs), nx, ny, nz, float(fTargetValue), _lib.ptr(ws), _lib.ptr(counts), st)
-        nv, nf = counts.tolist()                       # the one host sync (the reference has the same one)
-        verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
-        if nv or nf:
-            _lib.call("sr_mc_emit", _lib.ptr(sdfs), nx, ny, nz, float(fTargetValue), _lib.ptr(ws), float(xstep), float(ystep),
-                      float(zstep), float(xmin), float(ymin), float(zmin), _lib.ptr(verts), _lib.ptr(faces), st)
+    ws = _lib.workspace("sr_mc_workspace_bytes", nx, ny, nz, device=dev)
+    counts = torch.zeros((2,), dtype=torch.int32, device=dev)
+    _lib.launch("sr_mc_count", sdfs, sdfs, nx, ny, nz, float(fTargetValue), ws, counts)
+    nv, nf = counts.tolist()                           # the one host sync (the reference has the same one)
+    verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
+    if nv or nf:
+        _lib.launch("sr_mc_emit", sdfs, sdfs, nx, ny, nz, float(fTargetValue), ws, float(xstep), float(ystep), float(zstep), float(xmin), float(ymin),
+                    float(zmin), verts, faces)
     return [verts, faces]

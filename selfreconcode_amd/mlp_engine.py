@@ -488,7 +488,7 @@ def rows_frame_sum(X, index, n):
         X = X.float().contiguous()
     index = index.contiguous()
     out = torch.empty((n, E), dtype=torch.float32, device=X.device)
-    part = torch.empty((max(int(_lib.raw("sr_rows_frame_sum_workspace_floats")(P, E, n)), 1),), dtype=torch.float32, device=X.device)
+    part = _lib.workspace("sr_rows_frame_sum_workspace_floats", P, E, n, device=X.device, dtype=torch.float32)
     with _lib.on_device(X.device):
         _lib.call("sr_rows_frame_sum", _lib.ptr(X), X.stride(0), P, E, _lib.ptr(index), n, _lib.ptr(part), _lib.ptr(out), _lib.stream_of(X))
     return out

@@ -264,29 +264,36 @@ class LBSkinner(nn.Module):
         assert poses.shape[0] == trans.shape[0]
         return self.posed_chain(poses)[0][:, :, :3, 3]
 
+    def fill_lbs_fields(self, a, A, trans):
+        """The skinning inputs every kernel that evaluates this skinner reads, set on a struct that has these fields (SrLbsArgs,
+        SrRefineArgs): posed transforms A [N,24,4,4] as their top three rows, translations trans [N,3] (contiguous, or None), the
+        weight volume in its channel-last view and the box.  Returns the tensors the struct now points into: the caller holds them
+        until its launch is enqueued."""
+        A12 = A[:, :, :3, :].contiguous()
+        vol = self.ws.permute(0, 2, 3, 4, 1)
+        assert vol.is_contiguous()
+        a.A, a.trans, a.nframes = _lib.ptr(A12), _lib.ptr(trans), A.shape[0]
+        a.vol, a.D, a.H, a.W = _lib.ptr(vol), vol.shape[1], vol.shape[2], vol.shape[3]
+        box = self._box_consts()
+        for i in range(3):
+            a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
+        return A12, vol
+
     def fused(self, ps, A, trans, batch_inds=None, with_jac=False, tps=None):
         """No-autograd fused kernel: y (and dy/dp) for flat points [P,3] (batch_inds) or [N,V,3]."""
         flat = ps.reshape(-1, 3).contiguous()
         P = flat.shape[0]
         a = _lib.SrLbsArgs()
-        A12 = A[:, :, :3, :].contiguous()
         tr = trans.contiguous()
+        keep = self.fill_lbs_fields(a, A, tr)                       # noqa: F841 (held until the launch below is enqueued)
         y = torch.empty_like(flat)
         jac = torch.empty((P, 3, 3), device=flat.device) if with_jac else None
         tp = None if tps is None else tps.reshape(-1, 3).contiguous()
-        vol = self.ws.permute(0, 2, 3, 4, 1)
-        assert vol.is_contiguous()
         a.p, a.tp, a.P = _lib.ptr(flat), _lib.ptr(tp), P
-        a.A, a.trans, a.nframes = _lib.ptr(A12), _lib.ptr(tr), A.shape[0]
         a.batch_inds = _lib.ptr(batch_inds)
         a.points_per_frame = 0 if batch_inds is not None else (ps.shape[1] if ps.dim() == 3 else P)
-        a.vol, a.D, a.H, a.W = _lib.ptr(vol), vol.shape[1], vol.shape[2], vol.shape[3]
-        box = self._box_consts()
-        for i in range(3):
-            a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
         a.y, a.jac = _lib.ptr(y), _lib.ptr(jac)
-        with _lib.on_device(flat.device):
-            _lib.call("sr_lbs_fwd", ctypes.byref(a), _lib.stream_of(flat))
+        _lib.launch("sr_lbs_fwd", flat, ctypes.byref(a))
         return y.view(ps.shape), jac
 
     def forward(self, ps, conds, batch_inds=None, **kwargs):
@@ -328,22 +335,15 @@ class LBSkinner(nn.Module):
     def fused_backward(self, flat, A, batch_inds, ppf, ybar, need_p, need_A, need_t):
         P = flat.shape[0]
         a = _lib.SrLbsArgs()
-        A12 = A[:, :, :3, :].contiguous()
-        vol = self.ws.permute(0, 2, 3, 4, 1)
+        keep = self.fill_lbs_fields(a, A, None)                     # noqa: F841 (the backward kernels do not read trans)
         a.p, a.tp, a.P = _lib.ptr(flat), 0, P
-        a.A, a.trans, a.nframes = _lib.ptr(A12), 0, A.shape[0]
         a.batch_inds, a.points_per_frame = _lib.ptr(batch_inds), ppf
-        a.vol, a.D, a.H, a.W = _lib.ptr(vol), vol.shape[1], vol.shape[2], vol.shape[3]
-        box = self._box_consts()
-        for i in range(3):
-            a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
         yb = ybar.contiguous().float()
         pbar = torch.empty_like(flat) if need_p else None
         Abar = torch.empty((A.shape[0], 24, 12), device=flat.device) if need_A else None            # written, not accumulated
         tbar = torch.empty((A.shape[0], 3), device=flat.device) if need_t else None
-        part = torch.empty((max(int(_lib.raw("sr_lbs_bwd_workspace_floats")(P, A.shape[0])), 1),), device=flat.device)
-        with _lib.on_device(flat.device):
-            _lib.call("sr_lbs_bwd", ctypes.byref(a), _lib.ptr(yb), _lib.ptr(pbar), _lib.ptr(Abar), _lib.ptr(tbar), _lib.ptr(part), _lib.stream_of(flat))
+        part = _lib.workspace("sr_lbs_bwd_workspace_floats", P, A.shape[0], device=flat.device, dtype=torch.float32)
+        _lib.launch("sr_lbs_bwd", flat, ctypes.byref(a), yb, pbar, Abar, tbar, part)
         return pbar, Abar, tbar
 
 
@@ -355,8 +355,7 @@ class _PosedChain(torch.autograd.Function):
         G = torch.empty((B, 24, 4, 4), dtype=torch.float32, device=p.device)
         A = torch.empty_like(G)
         js, pa, ip = skin._host_consts()
-        with _lib.on_device(p.device):
-            _lib.call("sr_lbs_chain_fwd", _lib.ptr(p), B, js, pa, ip, _lib.ptr(G), _lib.ptr(A), _lib.stream_of(p))
+        _lib.launch("sr_lbs_chain_fwd", p, p, B, js, pa, ip, G, A)
         ctx.skin = skin
         ctx.save_for_backward(p)
         ctx.pshape = poses.shape
@@ -372,8 +371,7 @@ class _PosedChain(torch.autograd.Function):
         out = torch.empty_like(p)
         gb = None if Gbar is None else Gbar.contiguous().float()
         ab = None if Abar is None else Abar.contiguous().float()
-        with _lib.on_device(p.device):
-            _lib.call("sr_lbs_chain_bwd", _lib.ptr(p), p.shape[0], js, pa, ip, _lib.ptr(ab), _lib.ptr(gb), _lib.ptr(out), _lib.stream_of(p))
+        _lib.launch("sr_lbs_chain_bwd", p, p, p.shape[0], js, pa, ip, ab, gb, out)
         return None, out.view(ctx.pshape)
 
 
@@ -430,24 +428,16 @@ class _LBSValueJacobian(torch.autograd.Function):
         need_q, need_A, need_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         P = flat.shape[0]
         a = _lib.SrLbsArgs()
-        A12 = A[:, :, :3, :].contiguous()
-        vol = skin.ws.permute(0, 2, 3, 4, 1)
+        keep = skin.fill_lbs_fields(a, A, None)                     # noqa: F841 (as in fused_backward)
         a.p, a.tp, a.P = _lib.ptr(flat), 0, P
-        a.A, a.trans, a.nframes = _lib.ptr(A12), 0, A.shape[0]
         a.batch_inds, a.points_per_frame = _lib.ptr(batch_inds), ctx.ppf
-        a.vol, a.D, a.H, a.W = _lib.ptr(vol), vol.shape[1], vol.shape[2], vol.shape[3]
-        box = skin._box_consts()
-        for i in range(3):
-            a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
         yb = None if ybar is None else ybar.contiguous().float()
         Jb = torch.zeros((P, 3, 3), device=flat.device) if Jbar is None else Jbar.contiguous().float()
         qbar = torch.empty_like(flat) if need_q else None
         Abar = torch.empty((A.shape[0], 24, 12), device=flat.device) if need_A else None            # written, not accumulated
         tbar = torch.empty((A.shape[0], 3), device=flat.device) if (need_t and yb is not None) else None
-        part = torch.empty((max(int(_lib.raw("sr_lbs_bwd_workspace_floats")(P, A.shape[0])), 1),), device=flat.device)
-        with _lib.on_device(flat.device):
-            _lib.call("sr_lbs_jac_bwd", ctypes.byref(a), _lib.ptr(yb), _lib.ptr(Jb), _lib.ptr(qbar), _lib.ptr(Abar), _lib.ptr(tbar), _lib.ptr(part),
-                      _lib.stream_of(flat))
+        part = _lib.workspace("sr_lbs_bwd_workspace_floats", P, A.shape[0], device=flat.device, dtype=torch.float32)
+        _lib.launch("sr_lbs_jac_bwd", flat, ctypes.byref(a), yb, Jb, qbar, Abar, tbar, part)
         if Abar is not None:
             Abar = torch.nn.functional.pad(Abar.view(A.shape[0], 24, 3, 4), (0, 0, 0, 1))
         return None, qbar, Abar, tbar, None, None
@@ -497,8 +487,7 @@ class TranslatorValueJacobian(torch.autograd.Function):
         A0 = torch.empty((P * 4, ldo), dtype=torch.float32, device=flat.device)
         cd = None if conds is None else conds.reshape(-1, E).contiguous().float()
         with _lib.on_device(flat.device):
-            _lib.call("sr_pe_embed", _lib.ptr(flat), P, tr.multires, _lib.ptr(wt), _lib.ptr(cd), 0 if cd is None else cd.stride(0), E,
-                      _lib.ptr(index), 4, _lib.ptr(A0), ldo, _lib.stream_of(flat))
+            _lib.launch("sr_pe_embed", flat, flat, P, tr.multires, wt, cd, 0 if cd is None else cd.stride(0), E, index, 4, A0, ldo)
             acts = me.forward(spec, A0, Ws, bs, 4)
         out = acts[-1].view(P, 4, -1)[:, :, :3]
         d = flat + out[:, 0]
@@ -538,9 +527,7 @@ class TranslatorValueJacobian(torch.autograd.Function):
         xbar = None
         if need_x:
             xbar = torch.empty_like(flat)
-            with _lib.on_device(flat.device):
-                _lib.call("sr_pe_embed_bwd", _lib.ptr(flat), P, tr.multires, _lib.ptr(ctx.wt), 4, _lib.ptr(A0bar), A0bar.stride(0),
-                          _lib.ptr(xbar), _lib.stream_of(flat))
+            _lib.launch("sr_pe_embed_bwd", flat, flat, P, tr.multires, ctx.wt, 4, A0bar, A0bar.stride(0), xbar)
             if dbar is not None:
                 xbar = xbar + dbar.reshape(-1, 3)
             xbar = xbar.view(ctx.xshape)

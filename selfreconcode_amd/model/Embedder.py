@@ -53,9 +53,7 @@ class PEFunction(torch.autograd.Function):
         ldo = pad4(3 + 6 * L + E)
         out = torch.empty((P, ldo), dtype=torch.float32, device=x.device)
         ex = None if extra is None else extra.contiguous().float()
-        with _lib.on_device(x.device):
-            _lib.call("sr_pe_embed", _lib.ptr(x), P, L, _lib.ptr(wt), _lib.ptr(ex), 0 if ex is None else ex.stride(0), E,
-                      _lib.ptr(extra_index), 1, _lib.ptr(out), ldo, _lib.stream_of(x))
+        _lib.launch("sr_pe_embed", x, x, P, L, wt, ex, 0 if ex is None else ex.stride(0), E, extra_index, 1, out, ldo)
         ctx.L, ctx.E, ctx.segment = L, E, segment
         ctx.n_extra = 0 if extra is None else extra.shape[0]
         ctx.wt = wt
@@ -72,8 +70,7 @@ class PEFunction(torch.autograd.Function):
             # create_graph=True, where the backward itself must be differentiable)
             g = g.contiguous()
             gx = torch.empty_like(x)
-            with _lib.on_device(x.device):
-                _lib.call("sr_pe_embed_bwd", _lib.ptr(x), P, L, _lib.ptr(ctx.wt), 1, _lib.ptr(g), g.stride(0), _lib.ptr(gx), _lib.stream_of(x))
+            _lib.launch("sr_pe_embed_bwd", x, x, P, L, ctx.wt, 1, g, g.stride(0), gx)
         elif not ctx.needs_input_grad[0]:
             gx = None
         else:

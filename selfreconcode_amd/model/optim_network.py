@@ -379,14 +379,14 @@ class OptimNetwork(nn.Module):
             from .. import _lib
             if getattr(self, '_delay_flag', None) is None:
                 self._delay_flag = torch.zeros(2, dtype=torch.int32, device=self.TmpVs.device)
-            _lib.call('sr_stream_flag_wait', self._delay_flag.data_ptr(), 0x40000000, 0, ms, torch.cuda.current_stream().cuda_stream)
+            _lib.launch('sr_stream_flag_wait', self._delay_flag, self._delay_flag, 0x40000000, None, ms)
 
     def _mark(self, label):
         """Diagnostics: host time + a device-clock stamp on the CURRENT stream (sr_stream_stamp; slot index into self.mark_stamps)."""
         if self.host_marks is not None:
             from .. import _lib
             i = len(self.host_marks)
-            _lib.call('sr_stream_stamp', self.mark_stamps.data_ptr() + 8 * i, torch.cuda.current_stream().cuda_stream)
+            _lib.launch('sr_stream_stamp', self.mark_stamps, self.mark_stamps.data_ptr() + 8 * i)
             self.host_marks.append((label, time.perf_counter(), i))
 
     def _side_stream(self, device, which=0):

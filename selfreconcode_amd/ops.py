@@ -14,12 +14,11 @@ class SingularValues3x3(Function):
     @staticmethod
     def forward(ctx, J):
         _lib.require_gpu(J)
-        A = J.detach().contiguous().float().view(-1, 3, 3)
+        A = _lib.f32c(J).view(-1, 3, 3)
         n = A.shape[0]
         U = torch.empty_like(A); V = torch.empty_like(A)
         S = torch.empty((n, 3), dtype=torch.float32, device=A.device)
-        with _lib.on_device(A.device):
-            _lib.call("sr_svd3x3", _lib.ptr(A), n, _lib.ptr(U), _lib.ptr(S), _lib.ptr(V), _lib.stream_of(A))
+        _lib.launch("sr_svd3x3", A, A, n, U, S, V)
         ctx.save_for_backward(U, V)
         return S
 
@@ -41,29 +40,21 @@ class PointsSilhouette(Function):
     @staticmethod
     def forward(ctx, xy_ndc, z, H, W, radius, K):
         _lib.require_gpu(xy_ndc)
-        xy = xy_ndc.detach().contiguous().float(); zz = z.detach().contiguous().float()
+        xy, zz = _lib.f32c(xy_ndc), _lib.f32c(z)
         N, V = xy.shape[0], xy.shape[1]
-        nbytes = _lib.raw("sr_points_silhouette_workspace_bytes")(N, V, H, W, float(radius))
-        if nbytes < 0:
-            raise _lib.SrError("sr_points_silhouette_workspace_bytes: bad argument")
-        ws = torch.empty((max(int(nbytes), 256) + 255,), dtype=torch.uint8, device=xy.device)
-        off = (-ws.data_ptr()) % 256
+        ws = _lib.workspace("sr_points_silhouette_workspace_bytes", N, V, H, W, float(radius), device=xy.device)
         mask = torch.empty((N, H, W), dtype=torch.float32, device=xy.device)
-        with _lib.on_device(xy.device):
-            _lib.call("sr_points_silhouette_fwd", _lib.ptr(xy), _lib.ptr(zz), N, V, H, W, float(radius), int(K), _lib.ptr(mask),
-                      ws.data_ptr() + off, _lib.stream_of(xy))
+        _lib.launch("sr_points_silhouette_fwd", xy, xy, zz, N, V, H, W, float(radius), int(K), mask, ws)
         ctx.save_for_backward(xy, zz, ws)
-        ctx.dims = (H, W, float(radius), off)
+        ctx.dims = (H, W, float(radius))
         return mask
 
     @staticmethod
     def backward(ctx, gmask):
         xy, zz, ws = ctx.saved_tensors
-        H, W, radius, off = ctx.dims
+        H, W, radius = ctx.dims
         gxy = torch.empty_like(xy)
-        with _lib.on_device(xy.device):
-            _lib.call("sr_points_silhouette_bwd", _lib.ptr(xy), _lib.ptr(zz), xy.shape[0], xy.shape[1], H, W, radius, ws.data_ptr() + off,
-                      _lib.ptr(gmask.contiguous().float()), _lib.ptr(gxy), _lib.stream_of(xy))
+        _lib.launch("sr_points_silhouette_bwd", xy, xy, zz, xy.shape[0], xy.shape[1], H, W, radius, ws, _lib.f32c(gmask), gxy)
         return gxy, None, None, None, None, None
 
 
@@ -92,16 +83,14 @@ def rasterize_meshes(xy_ndc, z, faces, H, W):
     settings (model/network.py:877-892; see sr_rasterize_meshes)."""
     _lib.require_gpu(xy_ndc)
     _require_square(H, W, "rasterize_meshes")
-    xy = xy_ndc.detach().contiguous().float(); z = z.detach().contiguous().float(); faces = faces.contiguous()
+    xy, z, faces = _lib.f32c(xy_ndc), _lib.f32c(z), faces.contiguous()
     N, V = xy.shape[0], xy.shape[1]
     dev = xy.device
     zbuf = torch.empty((N, H, W), dtype=torch.int64, device=dev)
     p2f = torch.empty((N, H, W), dtype=torch.int64, device=dev)
     bary = torch.empty((N, H, W, 3), dtype=torch.float32, device=dev)
     zo = torch.empty((N, H, W), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_rasterize_meshes", _lib.ptr(xy), _lib.ptr(z), _lib.ptr(faces), N, V, faces.shape[0], H, W, _lib.ptr(zbuf), _lib.ptr(p2f),
-                  _lib.ptr(bary), _lib.ptr(zo), _lib.stream_of(xy))
+    _lib.launch("sr_rasterize_meshes", xy, xy, z, faces, N, V, faces.shape[0], H, W, zbuf, p2f, bary, zo)
     return Fragments(p2f.unsqueeze(-1), bary.unsqueeze(3), zo.unsqueeze(-1))
 
 
@@ -118,13 +107,13 @@ VertexAdjacency = namedtuple("VertexAdjacency", "offsets nbr V F")
 def _faces(faces):
     if faces.dim() != 2 or faces.shape[1] != 3:
         raise ValueError(f"faces [F,3] expected, got {tuple(faces.shape)}")
-    return faces.long().contiguous()                 # (the kernels read int64 rows)
+    return _lib.i64c(faces)                          # (the kernels read int64 rows)
 
 
 def _verts(verts):
     if verts.dim() != 3 or verts.shape[2] != 3:
         raise ValueError(f"verts [N,V,3] expected, got {tuple(verts.shape)}")
-    return verts.detach().contiguous().float()
+    return _lib.f32c(verts)
 
 
 def vertex_adjacency(faces, V):
@@ -136,8 +125,7 @@ def vertex_adjacency(faces, V):
     offsets = torch.empty((V + 1,), dtype=torch.int64, device=dev)
     nbr = torch.empty((3 * F, 2), dtype=torch.int32, device=dev)
     cursor = torch.empty((V,), dtype=torch.int32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_vertex_adjacency", _lib.ptr(faces), V, F, _lib.ptr(offsets), _lib.ptr(cursor), _lib.ptr(nbr), _lib.stream_of(faces))
+    _lib.launch("sr_vertex_adjacency", faces, faces, V, F, offsets, cursor, nbr)
     return VertexAdjacency(offsets, nbr, V, F)
 
 
@@ -151,8 +139,7 @@ def vertex_normals(verts, faces, adjacency=None):
     if adj.V != V or adj.F != faces.shape[0]:
         raise ValueError(f"vertex_normals: adjacency of a {adj.V}-vertex / {adj.F}-face template for {V} vertices / {faces.shape[0]} faces")
     out = torch.empty_like(v)
-    with _lib.on_device(v.device):
-        _lib.call("sr_vertex_normals", _lib.ptr(v), N, V, _lib.ptr(adj.offsets), _lib.ptr(adj.nbr), _lib.ptr(out), _lib.stream_of(v))
+    _lib.launch("sr_vertex_normals", v, v, N, V, adj.offsets, adj.nbr, out)
     return out
 
 
@@ -166,22 +153,20 @@ def shade_phong(verts, normals, faces, frags, cam_pos, light_loc=PHONG_LIGHT, am
     of `rasterize_meshes` (verts, normals [N,V,3]; cam_pos, light_loc [3] or [N,3], world space).  Colours are the light's times the
     material's.  Alpha is 1 (unpinned, see sr_shade_phong).  No autograd."""
     _lib.require_gpu(verts)
-    p2f = frags.pix_to_face[..., 0].long().contiguous()
-    bary = frags.bary_coords[..., 0, :].contiguous().float()
+    p2f = _lib.i64c(frags.pix_to_face[..., 0])
+    bary = _lib.f32c(frags.bary_coords[..., 0, :])
     N, H, W = p2f.shape
     if bary.shape != (N, H, W, 3):
         raise ValueError(f"shade_phong: bary_coords {tuple(frags.bary_coords.shape)} for pix_to_face {tuple(frags.pix_to_face.shape)}")
     _require_square(H, W, "shade_phong")
-    v = _verts(verts); n = normals.detach().contiguous().float(); faces = _faces(faces)
+    v = _verts(verts); n = _lib.f32c(normals); faces = _faces(faces)
     if v.shape[0] != N or n.shape != v.shape:
         raise ValueError(f"shade_phong: verts {tuple(v.shape)} / normals {tuple(n.shape)} for {N} images")
     dev = v.device
     cam, light = _per_image(cam_pos, N, dev), _per_image(light_loc, N, dev)
     coeffs = (ctypes.c_float * 13)(*[float(c) for c in (*ambient, *diffuse, *specular, shininess, *background)])
     rgba = torch.empty((N, H, W, 4), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_shade_phong", _lib.ptr(v), _lib.ptr(n), _lib.ptr(faces), N, v.shape[1], faces.shape[0], H, W, _lib.ptr(p2f), _lib.ptr(bary),
-                  _lib.ptr(cam), _lib.ptr(light), coeffs, _lib.ptr(rgba), _lib.stream_of(v))
+    _lib.launch("sr_shade_phong", v, v, n, faces, N, v.shape[1], faces.shape[0], H, W, p2f, bary, cam, light, coeffs, rgba)
     return rgba
 
 
@@ -197,15 +182,13 @@ def lbsw_knn_blend(verts, vert_ws, bmin, bmax, resolutions, k, align_corners=Fal
     if verts.dim() != 2 or verts.shape[1] != 3 or vert_ws.dim() != 2 or vert_ws.shape[0] != verts.shape[0]:
         raise ValueError(f"lbsw_knn_blend: verts [nv,3] and vert_ws [nv,nj] expected, got {tuple(verts.shape)} / {tuple(vert_ws.shape)}")
     W, H, D = (int(r) for r in resolutions)
-    v = verts.detach().contiguous().float(); ws = vert_ws.detach().to(v.device).contiguous().float()
+    v = _lib.f32c(verts); ws = _lib.f32c(vert_ws.to(v.device))
     nv, nj = ws.shape
     if not 1 <= int(k) <= min(LBSW_MAX_K, nv):
         raise ValueError(f"lbsw_knn_blend: k = {k} neighbours of {nv} vertices (1 <= k <= min({LBSW_MAX_K}, nv))")
     lo = (ctypes.c_float * 3)(*[float(x) for x in bmin]); hi = (ctypes.c_float * 3)(*[float(x) for x in bmax])
     field = torch.empty((nj, D, H, W), dtype=torch.float32, device=v.device)
-    with _lib.on_device(v.device):
-        _lib.call("sr_lbsw_knn_blend", _lib.ptr(v), _lib.ptr(ws), nv, nj, int(k), W, H, D, lo, hi, int(bool(align_corners)), _lib.ptr(field),
-                  _lib.stream_of(v))
+    _lib.launch("sr_lbsw_knn_blend", v, v, ws, nv, nj, int(k), W, H, D, lo, hi, int(bool(align_corners)), field)
     return field
 
 
@@ -217,13 +200,12 @@ def lbsw_smooth(field, times, consume=False):
         raise ValueError(f"lbsw_smooth: contiguous float32 field [nj,D,H,W] expected, got {tuple(field.shape)} {field.dtype}")
     nj, D, H, W = field.shape
     src, pool = field, [None, field if consume else None]            # the two destinations, taken in turn
-    with _lib.on_device(field.device):
-        for t in range(int(times)):
-            if pool[t % 2] is None:
-                pool[t % 2] = torch.empty_like(field)
-            dst = pool[t % 2]
-            _lib.call("sr_lbsw_smooth", _lib.ptr(src), _lib.ptr(dst), nj, W, H, D, _lib.stream_of(field))
-            src = dst
+    for t in range(int(times)):
+        if pool[t % 2] is None:
+            pool[t % 2] = torch.empty_like(field)
+        dst = pool[t % 2]
+        _lib.launch("sr_lbsw_smooth", field, src, dst, nj, W, H, D)
+        src = dst
     return src
 
 
@@ -244,8 +226,7 @@ def smpl_shape(v_template, shapedirs, beta):
     nv, (B, nbeta) = v_template.shape[0], beta.shape
     _smpl_f32(v_template, (nv, 3), "v_template"); _smpl_f32(shapedirs, (nbeta, 3 * nv), "shapedirs"); _smpl_f32(beta, (B, nbeta), "beta")
     out = torch.empty((B, nv, 3), dtype=torch.float32, device=beta.device)
-    with _lib.on_device(beta.device):
-        _lib.call("sr_smpl_shape", _lib.ptr(v_template), _lib.ptr(shapedirs), _lib.ptr(beta), B, nbeta, nv, _lib.ptr(out), _lib.stream_of(beta))
+    _lib.launch("sr_smpl_shape", beta, v_template, shapedirs, beta, B, nbeta, nv, out)
     return out
 
 
@@ -254,13 +235,9 @@ def smpl_regress(x, reg):
     _lib.require_gpu(x, reg)
     B, nv, nk = x.shape[0], x.shape[1], reg.shape[1]
     _smpl_f32(x, (B, nv, 3), "x"); _smpl_f32(reg, (nv, nk), "regressor")
-    n = _lib.raw("sr_smpl_regress_workspace_floats")(B, nv, nk)
-    if n < 0:
-        raise _lib.SrError("sr_smpl_regress_workspace_floats: bad argument")
-    partial = torch.empty((int(n),), dtype=torch.float32, device=x.device)
+    partial = _lib.workspace("sr_smpl_regress_workspace_floats", B, nv, nk, device=x.device, dtype=torch.float32)
     out = torch.empty((B, nk, 3), dtype=torch.float32, device=x.device)
-    with _lib.on_device(x.device):
-        _lib.call("sr_smpl_regress", _lib.ptr(x), _lib.ptr(reg), B, nv, nk, _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(x))
+    _lib.launch("sr_smpl_regress", x, x, reg, B, nv, nk, partial, out)
     return out
 
 
@@ -281,8 +258,7 @@ def smpl_pose(J, parents, theta=None, Rs=None):
     feature = torch.empty((B, SMPL_NPOSE), dtype=torch.float32, device=dev)
     Jt = torch.empty((B, SMPL_NJ, 3), dtype=torch.float32, device=dev)
     A = torch.empty((B, SMPL_NJ, 4, 4), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_smpl_pose", _lib.ptr(theta), _lib.ptr(Rs), _lib.ptr(J), pa, B, _lib.ptr(feature), _lib.ptr(Jt), _lib.ptr(A), _lib.stream_of(J))
+    _lib.launch("sr_smpl_pose", J, theta, Rs, J, pa, B, feature, Jt, A)
     return Rs, feature, Jt, A
 
 
@@ -299,9 +275,7 @@ def smpl_skin(rest, weights, A, posedirs=None, feature=None):
     if posedirs is not None:
         _smpl_f32(posedirs, (SMPL_NPOSE, 3 * nv), "posedirs"); _smpl_f32(feature, (B, SMPL_NPOSE), "pose feature")
     verts = torch.empty((B, nv, 3), dtype=torch.float32, device=A.device)
-    with _lib.on_device(A.device):
-        _lib.call("sr_smpl_skin", _lib.ptr(rest), stride, _lib.ptr(posedirs), _lib.ptr(feature), _lib.ptr(weights), _lib.ptr(A), B, nv, _lib.ptr(verts),
-                  _lib.stream_of(A))
+    _lib.launch("sr_smpl_skin", A, rest, stride, posedirs, feature, weights, A, B, nv, verts)
     return verts
 
 
@@ -330,11 +304,9 @@ def meshreg_fwd(verts, nbr_row, nbr, pairs, terms, target_length=0., stage_grad=
     lap_q = torch.empty_like(verts) if terms & MESHREG_LAP else None
     edge_g = torch.empty_like(verts) if terms & MESHREG_EDGE else None
     pair_g = torch.empty((P, 4, 3), dtype=torch.float32, device=dev) if terms & MESHREG_NORMAL and stage_grad and P > 0 else None
-    ws = torch.empty((max(1, _lib.raw("sr_meshreg_workspace_bytes")(V, P) // 8),), dtype=torch.float64, device=dev)
+    ws = _lib.workspace("sr_meshreg_workspace_bytes", V, P, device=dev)
     out = torch.empty((3,), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_meshreg_fwd", _lib.ptr(verts), V, _lib.ptr(nbr_row), _lib.ptr(nbr), E, _lib.ptr(pairs), P, terms, float(target_length),
-                  _lib.ptr(lap_q), _lib.ptr(edge_g), _lib.ptr(pair_g), _lib.ptr(ws), _lib.ptr(out), _lib.stream_of(verts))
+    _lib.launch("sr_meshreg_fwd", verts, verts, V, nbr_row, nbr, E, pairs, P, terms, float(target_length), lap_q, edge_g, pair_g, ws, out)
     return out, (lap_q, edge_g, pair_g)
 
 
@@ -349,7 +321,5 @@ def meshreg_bwd(saved, nbr_row, nbr, pair_row, pair_ent, num_verts, g_lap, g_edg
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
             raise ValueError(f"meshreg_bwd: {name} must be contiguous float32 with {n} elements, got {t.dtype} {tuple(t.shape)}")
     grad = torch.empty((V, 3), dtype=torch.float32, device=nbr_row.device)
-    with _lib.on_device(grad.device):
-        _lib.call("sr_meshreg_bwd", V, _lib.ptr(nbr_row), _lib.ptr(nbr), E, _lib.ptr(pair_row), _lib.ptr(pair_ent), P, _lib.ptr(lap_q), _lib.ptr(edge_g),
-                  _lib.ptr(pair_g), _lib.ptr(g_lap), _lib.ptr(g_edge), _lib.ptr(g_nc), _lib.ptr(grad), _lib.stream_of(grad))
+    _lib.launch("sr_meshreg_bwd", grad, V, nbr_row, nbr, E, pair_row, pair_ent, P, lap_q, edge_g, pair_g, g_lap, g_edge, g_nc, grad)
     return grad

@@ -79,10 +79,8 @@ class FusedAdam(torch.optim.Optimizer):
             if c is None:
                 c = corr[k] = (1.0 - b1 ** k, 1.0 / math.sqrt(1.0 - b2 ** k))
             T.g, T.lr, T.bias1, T.inv_sqrt_bias2 = g.data_ptr(), group['lr'], c[0], c[1]
-        with _lib.on_device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for t in cache[1]:
-                _lib.call("sr_adam_step", ctypes.byref(t), stream)
+        for t in cache[1]:
+            _lib.launch("sr_adam_step", todo[0][0], ctypes.byref(t))
         torch.autograd.graph.increment_version([p for p, _, _, _ in todo])      # the kernel wrote the parameters behind torch's version counters
         return loss
 

@@ -14,6 +14,7 @@ import torch
 from torch.autograd import Function
 
 from . import _lib
+from ._lib import f32c, i64c
 
 ENABLED = os.environ.get("SR_FUSED_STEP_OPS", "1") != "0"
 ENABLED_CAMERA = ENABLED          # model/CameraMine.py reads this one (projection / rays), everything else reads ENABLED
@@ -21,25 +22,17 @@ MAX_FRAMES = _lib.SR_STEP_MAX_FRAMES
 _SLOTS = _lib.SR_STEP_LOSS_SLOTS
 
 
-def _f32c(t):
-    t = t.detach()
-    if t.dtype != torch.float32:
-        t = t.float()
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def _i64c(t):
-    t = t.detach()
-    if t.dtype != torch.int64:
-        t = t.long()
-    return t if t.is_contiguous() else t.contiguous()
-
-
 def _loss_buffers(rows, dev):
     blocks = _lib.raw("sr_step_reduce_blocks")(int(rows))
     out = torch.empty((_SLOTS,), dtype=torch.float32, device=dev)
     partial = torch.empty((blocks, _SLOTS - 1), dtype=torch.float32, device=dev) if blocks > 1 else None
     return out, partial
+
+
+def _param_buffers(n, dev):
+    """(gparams [16], per-block partials) of the camera-parameter gradient reductions over n rows."""
+    blocks = max(_lib.raw("sr_step_param_blocks")(n), 1)
+    return torch.empty((16,), dtype=torch.float32, device=dev), torch.empty((blocks, 16), dtype=torch.float32, device=dev)
 
 
 def _gscalar(g):
@@ -54,7 +47,7 @@ class _CamArgs:
     """sr_camera for one (R, T, f, c, W, H): keeps the tensors it points to alive."""
 
     def __init__(self, R, T, f, c, W, H):
-        self.keep = (_f32c(R), None if T is None else _f32c(T), _f32c(f), _f32c(c))
+        self.keep = (f32c(R), None if T is None else f32c(T), f32c(f), f32c(c))
         a = _lib.SrCamera()
         a.R, a.T, a.f, a.c = _lib.ptr(self.keep[0]), _lib.ptr(self.keep[1]), _lib.ptr(self.keep[2]), _lib.ptr(self.keep[3])
         a.W, a.H = float(W), float(H)
@@ -79,13 +72,12 @@ class ProjectNDC(Function):
     @staticmethod
     def forward(ctx, ps, R, T, f, c, W, H):
         _lib.require_gpu(ps, R, f, c)
-        p = _f32c(ps).view(-1, 3)
+        p = f32c(ps).view(-1, 3)
         n = p.shape[0]
         cam = _CamArgs(R, T, f, c, W, H)
         xy = torch.empty((n, 2), dtype=torch.float32, device=p.device)
         z = torch.empty((n,), dtype=torch.float32, device=p.device)
-        with _lib.on_device(p.device):
-            _lib.call("sr_cam_project_ndc_fwd", _lib.ptr(p), n, cam.ref(), _lib.ptr(xy), _lib.ptr(z), _lib.stream_of(p))
+        _lib.launch("sr_cam_project_ndc_fwd", p, p, n, cam.ref(), xy, z)
         ctx.save_for_backward(p, R, T, f, c)
         ctx.WH, ctx.pshape = (W, H), ps.shape
         ctx.set_materialize_grads(False)
@@ -103,13 +95,10 @@ class ProjectNDC(Function):
         gps = torch.empty_like(p) if need_p else None
         gparams = partial = None
         if need_par:
-            gparams = torch.empty((16,), dtype=torch.float32, device=p.device)
-            partial = torch.empty((max(_lib.raw("sr_step_param_blocks")(n), 1), 16), dtype=torch.float32, device=p.device)
-        gxy_c = None if gxy is None else _f32c(gxy).view(-1, 2)
-        gz_c = None if gz is None else _f32c(gz).view(-1)
-        with _lib.on_device(p.device):
-            _lib.call("sr_cam_project_ndc_bwd", _lib.ptr(p), n, cam.ref(), _lib.ptr(gxy_c), _lib.ptr(gz_c), _lib.ptr(gps), _lib.ptr(partial),
-                      _lib.ptr(gparams), _lib.stream_of(p))
+            gparams, partial = _param_buffers(n, p.device)
+        gxy_c = None if gxy is None else f32c(gxy).view(-1, 2)
+        gz_c = None if gz is None else f32c(gz).view(-1)
+        _lib.launch("sr_cam_project_ndc_bwd", p, p, n, cam.ref(), gxy_c, gz_c, gps, partial, gparams)
         gR = gT = gf = gc = None
         if need_par:
             gR, gT, gf, gc = _param_grads(ctx.needs_input_grad[1:5], gparams, R, T, f, c)
@@ -122,12 +111,11 @@ class ViewRays(Function):
     @staticmethod
     def forward(ctx, pixels, R, f, c):
         _lib.require_gpu(pixels, R, f, c)
-        px = _f32c(pixels).view(-1, 3)
+        px = f32c(pixels).view(-1, 3)
         n = px.shape[0]
         cam = _CamArgs(R, None, f, c, 2., 2.)
         rays = torch.empty((n, 3), dtype=torch.float32, device=px.device)
-        with _lib.on_device(px.device):
-            _lib.call("sr_cam_view_rays_fwd", _lib.ptr(px), n, cam.ref(), _lib.ptr(rays), _lib.stream_of(px))
+        _lib.launch("sr_cam_view_rays_fwd", px, px, n, cam.ref(), rays)
         ctx.save_for_backward(px, R, f, c)
         ctx.set_materialize_grads(False)
         return rays
@@ -139,11 +127,8 @@ class ViewRays(Function):
             return None, None, None, None
         n = px.shape[0]
         cam = _CamArgs(R, None, f, c, 2., 2.)
-        gparams = torch.empty((16,), dtype=torch.float32, device=px.device)
-        partial = torch.empty((max(_lib.raw("sr_step_param_blocks")(n), 1), 16), dtype=torch.float32, device=px.device)
-        with _lib.on_device(px.device):
-            _lib.call("sr_cam_view_rays_bwd", _lib.ptr(px), n, cam.ref(), _lib.ptr(_f32c(grays)), _lib.ptr(partial), _lib.ptr(gparams),
-                      _lib.stream_of(px))
+        gparams, partial = _param_buffers(n, px.device)
+        _lib.launch("sr_cam_view_rays_bwd", px, px, n, cam.ref(), f32c(grays), partial, gparams)
         needs = (ctx.needs_input_grad[1], False, ctx.needs_input_grad[2], ctx.needs_input_grad[3])
         gR, _, gf, gc = _param_grads(needs, gparams, R, None, f, c)
         return None, gR, gf, gc
@@ -156,12 +141,11 @@ class CardinalRays(Function):
     @staticmethod
     def forward(ctx, J, v):
         _lib.require_gpu(J, v)
-        Jc, vc = _f32c(J).view(-1, 3, 3), _f32c(v).view(-1, 3)
+        Jc, vc = f32c(J).view(-1, 3, 3), f32c(v).view(-1, 3)
         n = Jc.shape[0]
         out = torch.empty((n, 3), dtype=torch.float32, device=Jc.device)
         ok = torch.empty((n,), dtype=torch.bool, device=Jc.device)
-        with _lib.on_device(Jc.device):
-            _lib.call("sr_cardinal_rays_fwd", _lib.ptr(Jc), _lib.ptr(vc), n, _lib.ptr(out), _lib.ptr(ok), _lib.stream_of(Jc))
+        _lib.launch("sr_cardinal_rays_fwd", Jc, Jc, vc, n, out, ok)
         ctx.save_for_backward(Jc, vc)
         ctx.mark_non_differentiable(ok)
         ctx.set_materialize_grads(False)
@@ -177,24 +161,22 @@ class CardinalRays(Function):
         gv = torch.empty_like(vc) if ctx.needs_input_grad[1] else None
         if gJ is None and gv is None:
             return None, None
-        with _lib.on_device(Jc.device):
-            _lib.call("sr_cardinal_rays_bwd", _lib.ptr(Jc), _lib.ptr(vc), n, _lib.ptr(_f32c(gout)), _lib.ptr(gJ), _lib.ptr(gv), _lib.stream_of(Jc))
+        _lib.launch("sr_cardinal_rays_bwd", Jc, Jc, vc, n, f32c(gout), gJ, gv)
         return gJ, gv
 
 
 def deformed_normals(J, onx):
     """utils/utils.py:132-153 in 'test' phase (no gradient): normalize(J^-T n), J n where J is singular."""
     _lib.require_gpu(J, onx)
-    Jc, oc = _f32c(J).view(-1, 3, 3), _f32c(onx).view(-1, 3)
+    Jc, oc = f32c(J).view(-1, 3, 3), f32c(onx).view(-1, 3)
     out = torch.empty_like(oc)
-    with _lib.on_device(Jc.device):
-        _lib.call("sr_deformed_normals", _lib.ptr(Jc), _lib.ptr(oc), Jc.shape[0], _lib.ptr(out), _lib.stream_of(Jc))
+    _lib.launch("sr_deformed_normals", Jc, Jc, oc, Jc.shape[0], out)
     return out
 
 
 # ------------------------------------------------------------------------------------------------ loss reductions
 def _pixels(b, r, c, N, H, W):
-    keep = (_i64c(b), _i64c(r), _i64c(c))
+    keep = (i64c(b), i64c(r), i64c(c))
     px = _lib.SrRayPixels()
     px.b, px.r, px.c = _lib.ptr(keep[0]), _lib.ptr(keep[1]), _lib.ptr(keep[2])
     px.P, px.N, px.H, px.W = keep[0].shape[0], N, H, W
@@ -207,12 +189,11 @@ class ColorLoss(Function):
     @staticmethod
     def forward(ctx, colors, gt, b, r, c):
         _lib.require_gpu(colors, gt)
-        col, g = _f32c(colors), _f32c(gt)
+        col, g = f32c(colors), f32c(gt)
         N, H, W = g.shape[0], g.shape[1], g.shape[2]
         px, keep = _pixels(b, r, c, N, H, W)
         out, partial = _loss_buffers(px.P, col.device)
-        with _lib.on_device(col.device):
-            _lib.call("sr_color_loss_fwd", ctypes.byref(px), _lib.ptr(col), _lib.ptr(g), _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(col))
+        _lib.launch("sr_color_loss_fwd", col, ctypes.byref(px), col, g, partial, out)
         ctx.save_for_backward(col, g, out, *keep)
         ctx.dims = (N, H, W)
         return out[0]
@@ -222,9 +203,7 @@ class ColorLoss(Function):
         col, g, out, b, r, c = ctx.saved_tensors
         px, _ = _pixels(b, r, c, *ctx.dims)
         gcol = torch.empty_like(col)
-        with _lib.on_device(col.device):
-            _lib.call("sr_color_loss_bwd", ctypes.byref(px), _lib.ptr(col), _lib.ptr(g), _lib.ptr(out), _lib.ptr(_gscalar(gloss)), _lib.ptr(gcol),
-                      _lib.stream_of(col))
+        _lib.launch("sr_color_loss_bwd", col, ctypes.byref(px), col, g, out, _gscalar(gloss), gcol)
         return gcol, None, None, None, None
 
 
@@ -234,14 +213,12 @@ class NormalLoss(Function):
     @staticmethod
     def forward(ctx, nx_raw, J, gt_normals, R, rays, weighted, b, r, c):
         _lib.require_gpu(nx_raw, J, gt_normals, R)
-        nx, Jc, g, Rc = _f32c(nx_raw).view(-1, 3), _f32c(J).view(-1, 3, 3), _f32c(gt_normals), _f32c(R).view(3, 3)
-        rc = _f32c(rays).view(-1, 3) if weighted else None
+        nx, Jc, g, Rc = f32c(nx_raw).view(-1, 3), f32c(J).view(-1, 3, 3), f32c(gt_normals), f32c(R).view(3, 3)
+        rc = f32c(rays).view(-1, 3) if weighted else None
         N, H, W = g.shape[0], g.shape[1], g.shape[2]
         px, keep = _pixels(b, r, c, N, H, W)
         out, partial = _loss_buffers(px.P, nx.device)
-        with _lib.on_device(nx.device):
-            _lib.call("sr_normal_loss_fwd", ctypes.byref(px), _lib.ptr(nx), _lib.ptr(Jc), _lib.ptr(g), _lib.ptr(Rc), _lib.ptr(rc), 1 if weighted else 0,
-                      _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(nx))
+        _lib.launch("sr_normal_loss_fwd", nx, ctypes.byref(px), nx, Jc, g, Rc, rc, 1 if weighted else 0, partial, out)
         ctx.save_for_backward(nx, Jc, g, Rc, out, *keep, *(() if rc is None else (rc,)))
         ctx.dims, ctx.weighted = (N, H, W), bool(weighted)
         return out[0]
@@ -254,9 +231,7 @@ class NormalLoss(Function):
         px, _ = _pixels(b, r, c, *ctx.dims)
         gnx = torch.empty_like(nx)
         gJ = torch.empty_like(Jc) if ctx.needs_input_grad[1] else None
-        with _lib.on_device(nx.device):
-            _lib.call("sr_normal_loss_bwd", ctypes.byref(px), _lib.ptr(nx), _lib.ptr(Jc), _lib.ptr(g), _lib.ptr(Rc), _lib.ptr(rc), 1 if ctx.weighted else 0,
-                      _lib.ptr(out), _lib.ptr(_gscalar(gloss)), _lib.ptr(gnx), _lib.ptr(gJ), _lib.stream_of(nx))
+        _lib.launch("sr_normal_loss_bwd", nx, ctypes.byref(px), nx, Jc, g, Rc, rc, 1 if ctx.weighted else 0, out, _gscalar(gloss), gnx, gJ)
         return gnx, gJ, None, None, None, None, None, None, None
 
 
@@ -266,10 +241,9 @@ class EikonalLoss(Function):
     @staticmethod
     def forward(ctx, g):
         _lib.require_gpu(g)
-        gc = _f32c(g).view(-1, 3)
+        gc = f32c(g).view(-1, 3)
         out, partial = _loss_buffers(gc.shape[0], gc.device)
-        with _lib.on_device(gc.device):
-            _lib.call("sr_eikonal_loss_fwd", _lib.ptr(gc), gc.shape[0], _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(gc))
+        _lib.launch("sr_eikonal_loss_fwd", gc, gc, gc.shape[0], partial, out)
         ctx.save_for_backward(gc)
         ctx.shape = g.shape
         return out[0]
@@ -278,8 +252,7 @@ class EikonalLoss(Function):
     def backward(ctx, gloss):
         gc, = ctx.saved_tensors
         gg = torch.empty_like(gc)
-        with _lib.on_device(gc.device):
-            _lib.call("sr_eikonal_loss_bwd", _lib.ptr(gc), gc.shape[0], _lib.ptr(_gscalar(gloss)), _lib.ptr(gg), _lib.stream_of(gc))
+        _lib.launch("sr_eikonal_loss_bwd", gc, gc, gc.shape[0], _gscalar(gloss), gg)
         return gg.view(ctx.shape)
 
 
@@ -289,15 +262,13 @@ class DefReguLoss(Function):
     @staticmethod
     def forward(ctx, J, c):
         _lib.require_gpu(J)
-        A = _f32c(J).view(-1, 3, 3)
+        A = f32c(J).view(-1, 3, 3)
         n = A.shape[0]
         U = torch.empty_like(A); V = torch.empty_like(A)
         S = torch.empty((n, 3), dtype=torch.float32, device=A.device)
         out, partial = _loss_buffers(n, A.device)
-        with _lib.on_device(A.device):
-            st = _lib.stream_of(A)
-            _lib.call("sr_svd3x3", _lib.ptr(A), n, _lib.ptr(U), _lib.ptr(S), _lib.ptr(V), st)
-            _lib.call("sr_def_regu_loss_fwd", _lib.ptr(S), n, float(c), _lib.ptr(partial), _lib.ptr(out), st)
+        _lib.launch("sr_svd3x3", A, A, n, U, S, V)
+        _lib.launch("sr_def_regu_loss_fwd", A, S, n, float(c), partial, out)
         ctx.save_for_backward(U, S, V)
         ctx.c, ctx.shape = float(c), J.shape
         return out[0]
@@ -306,9 +277,7 @@ class DefReguLoss(Function):
     def backward(ctx, gloss):
         U, S, V = ctx.saved_tensors
         gJ = torch.empty_like(U)
-        with _lib.on_device(U.device):
-            _lib.call("sr_def_regu_loss_bwd", _lib.ptr(U), _lib.ptr(S), _lib.ptr(V), U.shape[0], ctx.c, _lib.ptr(_gscalar(gloss)), _lib.ptr(gJ),
-                      _lib.stream_of(U))
+        _lib.launch("sr_def_regu_loss_bwd", U, U, S, V, U.shape[0], ctx.c, _gscalar(gloss), gJ)
         return gJ.view(ctx.shape), None
 
 
@@ -318,12 +287,11 @@ class MaskIoULoss(Function):
     @staticmethod
     def forward(ctx, masks, gt):
         _lib.require_gpu(masks, gt)
-        m, g = _f32c(masks), _f32c(gt)
+        m, g = f32c(masks), f32c(gt)
         N = m.shape[0]
         hw = m.numel() // N
         out, partial = _loss_buffers(m.numel(), m.device)
-        with _lib.on_device(m.device):
-            _lib.call("sr_mask_iou_loss_fwd", _lib.ptr(m), _lib.ptr(g), N, hw, _lib.ptr(partial), _lib.ptr(out), _lib.stream_of(m))
+        _lib.launch("sr_mask_iou_loss_fwd", m, m, g, N, hw, partial, out)
         ctx.save_for_backward(m, g, out)
         return out[0]
 
@@ -332,9 +300,7 @@ class MaskIoULoss(Function):
         m, g, out = ctx.saved_tensors
         N = m.shape[0]
         gm = torch.empty_like(m)
-        with _lib.on_device(m.device):
-            _lib.call("sr_mask_iou_loss_bwd", _lib.ptr(m), _lib.ptr(g), N, m.numel() // N, _lib.ptr(out), _lib.ptr(_gscalar(gloss)), _lib.ptr(gm),
-                      _lib.stream_of(m))
+        _lib.launch("sr_mask_iou_loss_bwd", m, m, g, N, m.numel() // N, out, _gscalar(gloss), gm)
         return gm, None
 
 
@@ -342,16 +308,14 @@ class MaskIoULoss(Function):
 def implicit_solve(grad_f, J, v, grad_l):
     """model/network.py:702-771 (no gradient): -> cot_f [P], rhs_tail [P,3], temp [P,3], ok [P] bool."""
     _lib.require_gpu(grad_f, J, v, grad_l)
-    gf, Jc, vc, gl = _f32c(grad_f).view(-1, 3), _f32c(J).view(-1, 3, 3), _f32c(v).view(-1, 3), _f32c(grad_l).view(-1, 3)
+    gf, Jc, vc, gl = f32c(grad_f).view(-1, 3), f32c(J).view(-1, 3, 3), f32c(v).view(-1, 3), f32c(grad_l).view(-1, 3)
     n = gf.shape[0]
     dev = gf.device
     cot_f = torch.empty((n,), dtype=torch.float32, device=dev)
     tail = torch.empty((n, 3), dtype=torch.float32, device=dev)
     temp = torch.empty((n, 3), dtype=torch.float32, device=dev)
     ok = torch.empty((n,), dtype=torch.bool, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_implicit_solve", _lib.ptr(gf), _lib.ptr(Jc), _lib.ptr(vc), _lib.ptr(gl), n, _lib.ptr(cot_f), _lib.ptr(tail), _lib.ptr(temp),
-                  _lib.ptr(ok), _lib.stream_of(gf))
+    _lib.launch("sr_implicit_solve", gf, gf, Jc, vc, gl, n, cot_f, tail, temp, ok)
     return cot_f, tail, temp, ok
 
 

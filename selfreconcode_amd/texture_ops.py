@@ -17,12 +17,11 @@ def uv_texel_map(vt, ft, resolution):
     _lib.require_gpu(vt, ft)
     if vt.dim() != 2 or vt.shape[1] != 2:
         raise ValueError(f"vt [Vt,2] expected, got {tuple(vt.shape)}")
-    vt = vt.detach().contiguous().float(); ft = _faces(ft)
+    vt = _lib.f32c(vt); ft = _faces(ft)
     R, dev = int(resolution), vt.device
     face = torch.empty((max(R, 0), max(R, 0)), dtype=torch.int32, device=dev)
     bary = torch.empty((max(R, 0), max(R, 0), 3), dtype=torch.float32, device=dev)
-    with _lib.on_device(dev):
-        _lib.call("sr_uv_rasterize", _lib.ptr(vt), _lib.ptr(ft), vt.shape[0], ft.shape[0], R, _lib.ptr(face), _lib.ptr(bary), _lib.stream_of(vt))
+    _lib.launch("sr_uv_rasterize", vt, vt, ft, vt.shape[0], ft.shape[0], R, face, bary)
     texel = torch.nonzero(face.view(-1) >= 0).view(-1)
     return TexelMap(face, bary, texel.int(), face.view(-1)[texel].contiguous(), bary.view(-1, 3)[texel].contiguous(), R)
 
@@ -31,30 +30,27 @@ def face_visibility(pix_to_face, faces, xy_pix, masks):
     """visible [N,F] uint8 (sr_face_visibility): the face owns a pixel of `pix_to_face` [N,H,W] (rasterize_meshes' packed indices) and its
     three vertices' pixel positions xy_pix [N,V,2] round into the viewport onto a set pixel of masks [N,H,W]."""
     _lib.require_gpu(pix_to_face, faces, xy_pix, masks)
-    p2f = pix_to_face.long().contiguous(); faces = _faces(faces)
-    xy = xy_pix.detach().contiguous().float()
+    p2f = _lib.i64c(pix_to_face); faces = _faces(faces)
+    xy = _lib.f32c(xy_pix)
     N, H, W = p2f.shape
     _require_square(H, W, "face_visibility")
     if xy.dim() != 3 or xy.shape[0] != N or xy.shape[2] != 2 or tuple(masks.shape) != (N, H, W):
         raise ValueError(f"face_visibility: xy_pix {tuple(xy.shape)} / masks {tuple(masks.shape)} for pix_to_face {tuple(p2f.shape)}")
     m = (masks != 0).to(torch.uint8).contiguous()
     vis = torch.empty((N, faces.shape[0]), dtype=torch.uint8, device=xy.device)
-    with _lib.on_device(xy.device):
-        _lib.call("sr_face_visibility", _lib.ptr(p2f), _lib.ptr(faces), N, xy.shape[1], faces.shape[0], _lib.ptr(xy), _lib.ptr(m), H, W, _lib.ptr(vis),
-                  _lib.stream_of(xy))
+    _lib.launch("sr_face_visibility", xy, p2f, faces, N, xy.shape[1], faces.shape[0], xy, m, H, W, vis)
     return vis
 
 
 def view_alpha(verts, normals, cam_pos):
     """alpha [N,V] = max(0, dot(normalize(verts - cam_pos), -normals)) (sr_view_alpha); cam_pos [3] or [N,3]."""
     _lib.require_gpu(verts, normals)
-    v = _verts(verts); n = normals.detach().contiguous().float()
+    v = _verts(verts); n = _lib.f32c(normals)
     if n.shape != v.shape:
         raise ValueError(f"view_alpha: normals {tuple(n.shape)} for verts {tuple(v.shape)}")
     cam = torch.as_tensor(cam_pos, dtype=torch.float32).to(v.device).reshape(-1, 3).expand(v.shape[0], 3).contiguous()
     out = torch.empty(v.shape[:2], dtype=torch.float32, device=v.device)
-    with _lib.on_device(v.device):
-        _lib.call("sr_view_alpha", _lib.ptr(v), _lib.ptr(n), _lib.ptr(cam), v.shape[0], v.shape[1], _lib.ptr(out), _lib.stream_of(v))
+    _lib.launch("sr_view_alpha", v, v, n, cam, v.shape[0], v.shape[1], out)
     return out
 
 
@@ -104,13 +100,10 @@ class TextureAccumulator:
         fid = torch.as_tensor(fids).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
         if fid.numel() != N:
             raise ValueError(f"accumulate: {fid.numel()} frame ids for {N} views")
-        img = images.detach().contiguous().float(); al = alpha.detach().contiguous().float(); xy = xy_pix.detach().contiguous().float()
+        img, al, xy = _lib.f32c(images), _lib.f32c(alpha), _lib.f32c(xy_pix)
         vis = visible.contiguous()
-        P = _lib.ptr
-        with _lib.on_device(dev):
-            _lib.call("sr_texture_accumulate", self.T, P(self.map.tface), P(self.map.tbary), P(self.faces), F, V, N, P(vis), P(al), P(xy), P(img), H, W,
-                      P(fid), self.agg_num, self.cosv0, P(self.slot_cos), P(self.slot_rgb), P(self.slot_view), P(self.count), P(self.min_cos),
-                      P(self.min_idx), _lib.stream_of(img))
+        _lib.launch("sr_texture_accumulate", img, self.T, self.map.tface, self.map.tbary, self.faces, F, V, N, vis, al, xy, img, H, W, fid,
+                    self.agg_num, self.cosv0, self.slot_cos, self.slot_rgb, self.slot_view, self.count, self.min_cos, self.min_idx)
 
     def resolve(self, check_num=5):
         """Step 7 on the [R,R] grid: count int32, mask_final bool, view_id int32 (-1 outside mask_final), tex_median [R,R,3] float32."""
@@ -122,10 +115,8 @@ class TextureAccumulator:
         view_id = torch.full((R, R), -1, dtype=torch.int32, device=dev)
         med = torch.zeros((R, R, 3), dtype=torch.float32, device=dev)
         if self.T:
-            P = _lib.ptr
-            with _lib.on_device(dev):
-                _lib.call("sr_texture_resolve", self.T, P(self.map.texel), self.agg_num, self.cosv0, int(check_num), P(self.slot_cos), P(self.slot_rgb),
-                          P(self.slot_view), P(count), P(mask_final), P(view_id), P(med), _lib.stream_of(med))
+            _lib.launch("sr_texture_resolve", med, self.T, self.map.texel, self.agg_num, self.cosv0, int(check_num), self.slot_cos, self.slot_rgb,
+                        self.slot_view, count, mask_final, view_id, med)
         return Resolved(count, mask_final.bool(), view_id, med)
 
 
@@ -143,15 +134,9 @@ def fill(tex_median, mask_final, tex_mask, dilate=None):
     if tuple(tex_median.shape) != (R, R, 3) or tuple(mask_final.shape) != (R, R) or tuple(tex_mask.shape) != (R, R):
         raise ValueError(f"fill: tex_median {tuple(tex_median.shape)} / mask_final {tuple(mask_final.shape)} / tex_mask {tuple(tex_mask.shape)}")
     k = int(0.1 * R) if dilate is None else int(dilate)
-    tex = tex_median.detach().contiguous().float()
+    tex = _lib.f32c(tex_median)
     mf = (mask_final != 0).to(torch.uint8).contiguous(); tm = (tex_mask != 0).to(torch.uint8).contiguous()
-    dev = tex.device
-    nbytes = _lib.raw("sr_texture_fill_workspace_bytes")(R)
-    if nbytes < 0:
-        raise _lib.SrError("sr_texture_fill_workspace_bytes: bad argument")
-    ws = torch.empty((int(nbytes) + 255,), dtype=torch.uint8, device=dev)
-    off = (-ws.data_ptr()) % 256
+    ws = _lib.workspace("sr_texture_fill_workspace_bytes", R, device=tex.device)
     out = torch.empty_like(tex)
-    with _lib.on_device(dev):
-        _lib.call("sr_texture_fill", _lib.ptr(tex), _lib.ptr(mf), _lib.ptr(tm), R, k, _lib.ptr(out), ws.data_ptr() + off, _lib.stream_of(tex))
+    _lib.launch("sr_texture_fill", tex, tex, mf, tm, R, k, out, ws)
     return out

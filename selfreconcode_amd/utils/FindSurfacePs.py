@@ -86,8 +86,7 @@ class _FusedEval:
         E = 0 if extra is None else extra.shape[1]
         ldo = me.pad4(3 + 6 * L + E)
         out = torch.empty((P * group, ldo), dtype=torch.float32, device=x.device)
-        _lib.call("sr_pe_embed", _lib.ptr(x), P, L, _lib.ptr(wt), _lib.ptr(extra), 0 if extra is None else extra.stride(0), E,
-                  _lib.ptr(index), group, _lib.ptr(out), ldo, _lib.stream_of(x))
+        _lib.launch("sr_pe_embed", x, x, P, L, wt, extra, 0 if extra is None else extra.stride(0), E, index, group, out, ldo)
         return out
 
     def evaluate(self, x, bi, group):
@@ -128,10 +127,10 @@ def _newton_reverse(ev, x, bi, rays, cam, dthr, athr, w1, w2, update):
         ones = ev.unit_cotangent(M)
         A0bar, _, _ = me.reverse(ev.sdf_spec, A0, ev.sdf_WT, acts, ones, 1, True, False)
         gf = torch.empty_like(x)
-        _lib.call("sr_pe_embed_bwd", _lib.ptr(x), M, ev.sdf.multires, _lib.ptr(ev.w_sdf), 1, _lib.ptr(A0bar), A0bar.stride(0), _lib.ptr(gf), _lib.stream_of(x))
+        _lib.launch("sr_pe_embed_bwd", x, x, M, ev.sdf.multires, ev.w_sdf, 1, A0bar, A0bar.stride(0), gf)
         A0dbar, _, _ = me.reverse(ev.tr.spec, A0d, ev.def_WT, actsd, t, 1, True, False)
         goff = torch.empty_like(x)
-        _lib.call("sr_pe_embed_bwd", _lib.ptr(x), M, ev.tr.multires, _lib.ptr(ev.w_def), 1, _lib.ptr(A0dbar), A0dbar.stride(0), _lib.ptr(goff), _lib.stream_of(x))
+        _lib.launch("sr_pe_embed_bwd", x, x, M, ev.tr.multires, ev.w_def, 1, A0dbar, A0dbar.stride(0), goff)
         xnew = torch.empty_like(x)
         a.grad_f, a.grad_off, a.p, a.p_out = _lib.ptr(gf), _lib.ptr(goff), _lib.ptr(x), _lib.ptr(xnew)
         _lib.call("sr_newton_apply", ctypes.byref(a), _lib.stream_of(x))
@@ -253,13 +252,7 @@ def _optimize_device_driven(ev, cam, rays, initTmpPs, batch_inds, dthreshold, at
     a.p0, a.rays, a.batch_inds, a.cam = _lib.ptr(x0), _lib.ptr(rays), _lib.ptr(bi), _lib.ptr(cam)
     a.L_sdf, a.w_sdf, a.L_def, a.w_def = ev.sdf.multires, _lib.ptr(ev.w_sdf), ev.tr.multires, _lib.ptr(ev.w_def)
     a.conds, a.ld_conds, a.E = _lib.ptr(ev.conds), ev.conds.stride(0), ev.conds.shape[1]
-    A12 = ev.A[:, :, :3, :].contiguous()
-    vol = ev.skin.ws.permute(0, 2, 3, 4, 1)
-    a.A, a.trans, a.nframes = _lib.ptr(A12), _lib.ptr(ev.trans), A12.shape[0]
-    a.vol, a.D, a.H, a.W = _lib.ptr(vol), vol.shape[1], vol.shape[2], vol.shape[3]
-    box = ev.skin._box_consts()
-    for i in range(3):
-        a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
+    keep = ev.skin.fill_lbs_fields(a, ev.A, ev.trans)               # noqa: F841 (held until the launches below are enqueued)
     a.dthreshold, a.athreshold, a.w1, a.w2 = dthreshold, athreshold, w1, w2
     a.live = _lib.ptr(ws.live)
     for i in range(2):

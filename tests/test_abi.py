@@ -17,6 +17,16 @@ def _declared():
     return sorted(set(names))
 
 
+def _defines():
+    """{name: value} of the integer `#define SR_*` lines of the header, in file order (a later one may use an earlier one)."""
+    vals = {}
+    txt = open(os.path.join(ROOT, "include", "selfrecon_hip.h")).read()
+    for name, expr in re.findall(r"^[ \t]*#define[ \t]+(SR_\w+)[ \t]+([^/\n]+?)[ \t]*(?:/\*.*)?$", txt, flags=re.M):
+        if re.fullmatch(r"[\w \t()+*-]+", expr) and not re.search(r"[a-z]", expr):
+            vals[name] = int(eval(expr, {"__builtins__": {}}, dict(vals)))
+    return vals
+
+
 def test_library_builds_and_exports_every_declared_symbol():
     from selfreconcode_amd.build import build_lib
     lib = ctypes.CDLL(build_lib(verbose=False))
@@ -79,6 +89,25 @@ def test_ctypes_structs_have_the_size_the_header_declares(tmp_path):
     sizes = dict(line.split() for line in out.strip().splitlines())
     for n, cls in pairs.items():
         assert int(sizes[n]) == ctypes.sizeof(cls), (n, sizes[n], ctypes.sizeof(cls))
+
+
+def test_python_mirrors_of_the_header_constants():
+    """Constants that size no struct (the struct-size test cannot see them) but bound what the wrappers accept or allocate: every
+    Python mirror equals its #define, and the error codes _lib names are the header's."""
+    from selfreconcode_amd import _lib, ops, step_ops
+    d = _defines()
+    assert d["SR_OK"] == 0 and d["SR_STEP_LOSS_SLOTS"] == 1 + 2 * d["SR_STEP_MAX_FRAMES"]          # (the parser follows a #define that uses another)
+    mirrors = {"SR_TN_GROUP_MAX": _lib.SR_TN_GROUP_MAX, "SR_CHAIN_MAX_LAYERS": _lib.SR_CHAIN_MAX_LAYERS, "SR_PACK_MAX_LAYERS": _lib.SR_PACK_MAX_LAYERS,
+               "SR_ADAM_MAX_TENSORS": _lib.SR_ADAM_MAX_TENSORS, "SR_STEP_MAX_FRAMES": _lib.SR_STEP_MAX_FRAMES, "SR_STEP_LOSS_SLOTS": _lib.SR_STEP_LOSS_SLOTS,
+               "SR_LBSW_MAX_K": ops.LBSW_MAX_K, "SR_SMPL_BATCH_TILE": ops.SMPL_BATCH_TILE, "SR_MESHREG_LAP": ops.MESHREG_LAP,
+               "SR_MESHREG_EDGE": ops.MESHREG_EDGE, "SR_MESHREG_NORMAL": ops.MESHREG_NORMAL}
+    for name, value in mirrors.items():
+        assert d[name] == value, (name, d[name], value)
+    assert step_ops.MAX_FRAMES == d["SR_STEP_MAX_FRAMES"]
+    codes = {d[n]: n for n in ("SR_EINVAL", "SR_ELAUNCH", "SR_ENOSPC")}
+    assert set(codes) == set(_lib._CODES)
+    for value, name in codes.items():
+        assert _lib._CODES[value].startswith(name + " "), (value, _lib._CODES[value])
 
 
 def test_pack_cache_entries_die_with_their_parameters():
