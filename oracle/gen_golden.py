@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 from oracle.ref_harness import load_reference  # noqa: E402
 from oracle import fixtures as fx  # noqa: E402
 from oracle import torch_oracle as orc  # noqa: E402
+from oracle import scene  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 os.makedirs(OUT, exist_ok=True)
@@ -266,22 +267,13 @@ ref.network.Fast3x3Minv = lambda m: list(orc.minv3x3(m))
 Fn, Hh, Ww = 5, 64, 48
 
 
-class _Seq:
-    def __init__(self):
-        leaf = lambda t: t.clone().requires_grad_(True)
-        self.poses = leaf(fx.det_tensor((Fn, 24, 3), 71, 0.15)); self.trans = leaf(fx.det_tensor((Fn, 3), 72, 0.05))
-        self.conds = [leaf(fx.det_tensor((Fn, 128), 73, 0.1)), leaf(fx.det_tensor((Fn, 256), 74, 0.1))]
-        self.focal = leaf(torch.tensor([58.0, 60.0])); self.princ = leaf(torch.tensor([23.0, 33.5])); self.T = leaf(torch.tensor([0.03, -0.1, 2.5]))
-        self.R = orc.quat2mat(torch.tensor([[0.02, 0.01, 0.999, 0.03]]))
-
-    def get_grad_parameters(self, idxs, device):
-        return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-    def get_camera_parameters(self, N, device):
-        return self.focal.view(1, 2).expand(N, 2), self.princ.view(1, 2).expand(N, 2), self.R.expand(N, 3, 3), self.T.view(1, 3).expand(N, 3), Hh, Ww
+def _seq():                                       # scene.Sequence on this fixture's own arrays: 5 frames, a 64 x 48 image, a tilted camera
+    return scene.Sequence(Fn, Hh, Ww, tensors=dict(
+        poses=fx.det_tensor((Fn, 24, 3), 71, 0.15), trans=fx.det_tensor((Fn, 3), 72, 0.05), dcond=fx.det_tensor((Fn, 128), 73, 0.1), rcond=fx.det_tensor((Fn, 256), 74, 0.1),
+        focal=torch.tensor([58.0, 60.0]), princ=torch.tensor([23.0, 33.5]), T=torch.tensor([0.03, -0.1, 2.5]), R=orc.quat2mat(torch.tensor([[0.02, 0.01, 0.999, 0.03]]))))
 
 
-seq = _Seq()
+seq = _seq()
 for m in (sdf, tr):
     for prm in m.parameters():
         prm.grad = None
@@ -341,7 +333,7 @@ class _DictConf:
 for m in (sdf, tr):
     for prm in m.parameters():
         prm.grad = None
-seq2 = _Seq()
+seq2 = _seq()
 pcnet = object.__new__(ref.network.OptimNetwork)
 torch.nn.Module.__init__(pcnet)
 pcnet.sdf, pcnet.deformer, pcnet.info = sdf, comp, {'pc_loss': {}}

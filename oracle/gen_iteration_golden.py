@@ -23,6 +23,7 @@ from oracle.ref_harness import load_reference  # noqa: E402
 from oracle import fixtures as fx  # noqa: E402
 from oracle import torch_oracle as orc  # noqa: E402
 from oracle import raster_oracle as ro  # noqa: E402
+from oracle import scene  # noqa: E402   (free of the reference; oracle/ref_scene.py, which builds on this module, is not)
 
 OUT = os.path.join(os.path.dirname(HERE), "tests", "golden")
 ref = load_reference()
@@ -156,28 +157,7 @@ def main():
     rn = ref.RenderNet.RenderingNetwork_view_norm(256, 'idr', 9, 3, [512, 512, 512, 512], True, multires_n=0, multires_v=4)
     rn.load_state_dict(fx.det_params(fx.REND_SPEC, 303), strict=True)
 
-    class Seq:
-        frame_num = F
-        video_segmented_index = []
-
-        def __init__(self):
-            leaf = lambda t: t.clone().requires_grad_(True)
-            self.poses = leaf(fx.det_tensor((F, 24, 3), 91, 0.12)); self.trans = leaf(fx.det_tensor((F, 3), 92, 0.04))
-            self.conds = [leaf(fx.det_tensor((F, 128), 93, 0.1)), leaf(fx.det_tensor((F, 256), 94, 0.1))]
-            self.focal = leaf(torch.tensor([1.2 * W, 1.2 * W])); self.princ = leaf(torch.tensor([W / 2.0, H / 2.0])); self.T = leaf(torch.tensor([0., 0.1, 2.4]))
-            self.R = orc.quat2mat(torch.tensor([[0., 0., 1., 0.]]))
-
-        def get_grad_parameters(self, idxs, device):
-            return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-        def get_camera_parameters(self, n, device):
-            return self.focal.view(1, 2).expand(n, 2), self.princ.view(1, 2).expand(n, 2), self.R.expand(n, 3, 3), self.T.view(1, 3).expand(n, 3), H, W
-
-        def get_batchframe_data(self, name, fids, batchsize):                     # dataset/dataset.py:128-147, unsegmented video
-            data = getattr(self, name)
-            starts = (fids - batchsize // 2).clamp(min=0, max=self.frame_num - batchsize)
-            return data[starts.view(-1, 1) + torch.arange(0, batchsize).view(1, batchsize)], fids - starts
-    ds = Seq()
+    ds = scene.Sequence(F, H, W)
     # ---- template: an icosphere pulled onto the zero set of the SDF along the radius
     dirs, faces = icosphere(3)
     with torch.no_grad():

@@ -29,7 +29,6 @@ of `infer` on EVAL_FRAMES and parameter digests.
 import os
 import sys
 import time
-import types
 import numpy as np
 import torch
 
@@ -38,17 +37,13 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, ROOT)
 from oracle import gen_iteration_golden as gi  # noqa: E402
 from oracle import gen_fullsize_golden as gf  # noqa: E402
-from oracle import gen_trajectory_golden as gt  # noqa: E402
-from oracle import fixtures as fx  # noqa: E402
-from oracle import raster_oracle as ro  # noqa: E402
-from oracle import mc as mco  # noqa: E402
+from oracle import scene  # noqa: E402
+from oracle import ref_scene as rs  # noqa: E402
 
-ref = gi.ref
 OUT = os.path.join(ROOT, "tests", "golden")
 K, REMESH_AT = 32, 12
 NUDGE_BELOW = 4e-5
 LR = 1e-4
-DRAW_BASE = 29000
 EVAL_FRAMES = [2, 11, 19, 30]
 RES_COARSE = [(15, 21, 9), (29, 41, 17), (57, 81, 33), (113, 161, 65), (225, 321, 129)]       # train.py:29-37
 RES_FINE = [(21, 27, 15), (41, 53, 29), (81, 105, 57), (161, 209, 113), (321, 417, 225)]        # train.py:45-51
@@ -58,92 +53,14 @@ STAGE = {"coarse": dict(N=3, res=RES_COARSE, lr=1e-4, radius=0.006, base=29000, 
          "fine": dict(N=1, res=RES_FINE, lr=1e-4 * 0.333 ** 3, radius=0.0041, base=39000, remesh=120, name="trajectory_full_fine.npz")}
 
 
-def frames_of(k, F, N=3):
-    if CONSISTENT:
-        c = CONS_FRAMES
-        return [c[k % 8], c[(k + 3) % 8], c[(k + 5) % 8]][:N]
-    return [(7 + 3 * k) % F, (21 + 5 * k) % F, (30 + 7 * k) % F][:N]
-
-
 # `--scene consistent` (round 6): a scene the optimisation can CONVERGE on.  The noise fixture above shows that the product follows the
 # reference through chaos (its mask error goes UP at the remesh); this one shows the quality metric FALLING on both sides at the same
 # rate: the ground-truth mask of a frame is the silhouette -- the reference's own deformer, the mesh-rasteriser restatement -- of the
 # initial template scaled by CONS_SCALE, so the template's SGD step on the mask loss has a silhouette it can reach; colour and normal
-# targets are smooth functions of the pixel inside that mask (the same torch formulas on both sides, `consistent_observation`), white /
+# targets are smooth functions of the pixel inside that mask (`scene.consistent_observation`, one function for both sides), white /
 # zero outside as `infer` renders them.  Eight frames cycle through the batch so that every frame comes back every few iterations.
-CONSISTENT = False
 CONS_FRAMES = [2, 7, 11, 19, 21, 26, 30, 35]
 CONS_SCALE = 1.05
-
-
-def consistent_observation(mask):
-    """mask [H, W] (0/1 float) -> (img [H,W,3] in [-1,1], white background; normal [H,W,3] unit inside the mask, 0 outside)."""
-    H, W = mask.shape
-    ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32, device=mask.device), torch.arange(W, dtype=torch.float32, device=mask.device), indexing='ij')
-    u, v = xs / W, ys / H
-    img = torch.stack([0.6 * torch.sin(6.2831853 * (1.0 * u + 3.0 * v)), 0.6 * torch.sin(6.2831853 * (2.0 * u + 1.0 * v) + 1.0),
-                       0.6 * torch.sin(6.2831853 * (3.0 * u + 2.0 * v) + 2.0)], dim=-1)
-    img = torch.where(mask[..., None] > 0, img, torch.ones_like(img))
-    a, b = (u - 0.5) / 0.32, (v - 0.45) / 0.36
-    c = torch.sqrt(torch.clamp(1.0 - a * a - b * b, min=0.04))
-    n = torch.stack([a, -b, -c], dim=-1)
-    n = n / n.norm(dim=-1, keepdim=True)
-    return img, n * mask[..., None]
-
-
-def ratio_of(k):
-    return {'sdfRatio': 1., 'deformerRatio': k / 2500. + 0.5, 'renderRatio': 1.}
-
-
-_OBS = {}
-
-
-_CONS_MASKS = {}
-
-
-def observations(fids, H, W):
-    """Per-frame observations keyed by the GLOBAL frame id (both sides rebuild them): noise colours / normals, the fixed elliptic mask."""
-    if CONSISTENT:
-        ms = [_CONS_MASKS[int(f)] for f in fids]
-        io = [consistent_observation(m) for m in ms]
-        return {'img': torch.stack([i for i, _ in io]), 'mask': torch.stack(ms), 'normal': torch.stack([n for _, n in io])}
-    imgs, nrms = [], []
-    for f in fids:
-        f = int(f)
-        if f not in _OBS:
-            n = fx.det_tensor((H, W, 3), 9200 + f, 1.0)
-            n[::5] = 0.
-            _OBS[f] = (fx.det_tensor((H, W, 3), 9100 + f, 1.0), n)
-        imgs.append(_OBS[f][0]); nrms.append(_OBS[f][1])
-    return {'img': torch.stack(imgs), 'mask': gf.mask_image(len(fids), H, W), 'normal': torch.stack(nrms)}
-
-
-class Draws(gt.Draws):
-    base = DRAW_BASE
-
-    def rand(self, *size, **kw):
-        shape = tuple(size[0]) if len(size) == 1 and not isinstance(size[0], int) else tuple(size)
-        self.calls.append(('rand', shape))
-        return fx.det_tensor(shape, self.base + 16 * self.k + len(self.calls) - 1, 0.5) + 0.5
-
-    def randn_like(self, x, **kw):
-        self.calls.append(('randn_like', tuple(x.shape)))
-        return fx.det_normal(tuple(x.shape), self.base + 16 * self.k + len(self.calls) - 1)
-
-
-class MaskRender(gt.MaskRender):
-    """as the trajectory harness's (topology of the mesh it is handed), and keeps the last fragments: their coverage is the silhouette
-    whose IoU error against the ground-truth mask is the reference's quality metric (network.py:322-324)."""
-
-    def __call__(self, meshes):
-        out = super().__call__(meshes)
-        self.last_p2f = out[1].pix_to_face
-        return out
-
-
-def mask_error(masks, gtm):
-    n = masks.shape[0]
-    return 1. - (masks * gtm).view(n, -1).sum(1) / (masks + gtm - masks * gtm).abs().view(n, -1).sum(1)
 
 
 def main():
@@ -153,12 +70,10 @@ def main():
     twin = "--twin" in sys.argv
     stage = sys.argv[sys.argv.index("--stage") + 1] if "--stage" in sys.argv else "coarse"
     cfg = STAGE[stage]
-    global CONSISTENT
     CONSISTENT = "--scene" in sys.argv and sys.argv[sys.argv.index("--scene") + 1] == "consistent"
     if CONSISTENT:
         assert stage == "coarse"
         cfg = dict(cfg, base=49000, name="trajectory_full_consistent.npz")
-    Draws.base = cfg["base"]
     noray = "--no-ray-terms" in sys.argv        # (diagnostics) colour / normal weights 0: no ray branch, no implicit-gradient pass -> trajectory_full_noray.npz
     cover_only = "--cover" in sys.argv          # re-run up to the remesh and merge the rasterised silhouettes of that iteration into the fixture (bit-packed)
     torch.set_num_threads(os.cpu_count())
@@ -188,114 +103,83 @@ def main():
     F = ds.frame_num
     N = cfg["N"]
     SPX = 2048                                   # (the fine stage's loss_fine carries sample_pix_num = 6144, which overrides it: network.py:520)
-    net.maskRender = MaskRender(H, W, faces)
-    net.engine = ref.MCAcc.Seg3dLossless(query_func=None, b_min=fx.LBS_BMIN, b_max=fx.LBS_BMAX, resolutions=cfg["res"], align_corners=False, balance_value=0.0,
-                                         device='cpu', visualize=False, debug=False, use_cuda_impl=False, faster=False)
+    net.engine = rs.seg3d_engine(cfg["res"])
     remeshed = {}
 
-    def mc_gpu(sdfs, xs, ys, zs, x0, y0, z0, iso):                       # MCGpu.mc_gpu (MCGpu/MCGpu.cpp:20-56) through the reference's kernels
-        t0 = time.perf_counter()
-        v, keys, f = mco.reference_marching_cubes(sdfs.numpy(), (float(xs), float(ys), float(zs)), (float(x0), float(y0), float(z0)), float(iso), mode="fma")
-        v, keys, f = mco.canonical(v, keys, f)
-        remeshed['V'], remeshed['F'] = torch.from_numpy(v.copy()), torch.from_numpy(f.copy())
-        print(f"    marching cubes (reference kernels, host build): {time.perf_counter() - t0:.1f} s, V = {v.shape[0]}, F = {f.shape[0]}", flush=True)
-        return [remeshed['V'].clone(), remeshed['F'].clone()]
-    ref.network.MCGpu = types.SimpleNamespace(mc_gpu=mc_gpu)
-
-    class _TriMesh:                                                      # openmesh.TriMesh: network.py:472-478 builds vertex->face tables nobody reads
-        def __init__(self, v, f):
-            self.n = len(v)
-
-        def vertex_face_indices(self):
-            return -np.ones((self.n, 1), np.int64)
-    ref.network.om = types.SimpleNamespace(TriMesh=_TriMesh)
-    net.forward_time, net.remesh_intersect, net.remesh_time = cfg["remesh"] - REMESH_AT, cfg["remesh"], 0.          # one remesh in the window: at the call with index REMESH_AT
-    learn = [ds.conds[0], ds.conds[1], ds.focal, ds.princ, ds.T, ds.poses, ds.trans]          # dataset.learnable_weights(): codes, camera, poses, trans
-    optimizer = torch.optim.Adam([{'params': learn}, {'params': [p for p in net.parameters() if p.requires_grad]}], lr=cfg["lr"])
-    gtm1 = gf.mask_image(1, H, W)
+    def on_remesh(V, Fc, seconds):
+        remeshed.update(V=V, F=Fc)
+        print(f"    marching cubes (reference kernels, host build): {seconds:.1f} s, V = {V.shape[0]}, F = {Fc.shape[0]}", flush=True)
+    rs.install_mc_stand_ins(on_remesh)
+    net.forward_time, net.remesh_intersect = cfg["remesh"] - REMESH_AT, cfg["remesh"]          # one remesh in the window: at the call with index REMESH_AT
+    optimizer = scene.adam_over(ds, net, cfg["lr"])
+    gtm1 = scene.elliptic_mask(H, W)[None]
+    cons_masks, obs_cache = {}, {}
+    frames_of = lambda k: scene.frames_full(k, F, N, CONS_FRAMES if CONSISTENT else None)
     if CONSISTENT:
         with torch.no_grad():
             cf = torch.tensor(CONS_FRAMES)
             poses, trans, dcond, _ = ds.get_grad_parameters(cf, 'cpu')
-            tgt = net.deformer((net.TmpVs.detach() * CONS_SCALE)[None].expand(len(CONS_FRAMES), -1, 3), [dcond, [poses, trans]], ratio=ratio_of(0))
-            xy, z = ro.ndc_projection(tgt, ds.focal.detach(), ds.princ.detach(), ds.R[0], ds.T.detach(), W, H)
-            p2f, _, _ = ro.rasterize_meshes(torch.cat([xy, z[..., None]], -1).float().numpy(), faces.numpy(), H, W)
+            tgt = net.deformer((net.TmpVs.detach() * CONS_SCALE)[None].expand(len(CONS_FRAMES), -1, 3), [dcond, [poses, trans]], ratio=scene.ratio_of(0))
+            cover = rs.silhouettes(tgt, ds, faces, H, W)
             for i, f in enumerate(CONS_FRAMES):
-                _CONS_MASKS[f] = torch.from_numpy((p2f[i, ..., 0] >= 0)).float()
-            print("consistent scene: target silhouettes of", CONS_FRAMES, "cover", [int(m.sum()) for m in _CONS_MASKS.values()], "pixels", flush=True)
+                cons_masks[f] = cover[i]
+            print("consistent scene: target silhouettes of", CONS_FRAMES, "cover", [int(m.sum()) for m in cons_masks.values()], "pixels", flush=True)
 
-    real_rand, real_randn_like = torch.rand, torch.randn_like
     out = dict(q=q.view(-1), nudge_idx=nudge_idx.to(torch.int32), HW=np.array([H, W]), SP=np.array(SPX), K=np.array(kk), remesh_at=np.array(REMESH_AT), remesh_intersect=np.array(cfg["remesh"]), frame_num=np.array(F), lr=np.array(cfg["lr"]), frames_per_iteration=np.array(N),
                radius=np.array(cfg["radius"]), ang_thr=np.array(net.angThred), res=np.array(cfg["res"]), eval_frames=np.array(EVAL_FRAMES), lbs_shape=np.array([65, 225, 129]),
                n_cube=np.array(gf.STAGES[stage]["n_cube"]), draw_base=np.array(cfg["base"]))
-    names = ('grad_loss', 'def_loss', 'dct_loss', 'color_loss', 'normal_loss', 'offset_loss', 'pc_loss_sdf')
-    curve = {n: [] for n in names + ('mask_loss', 'defconst_loss', 'total')}
-    ray_counts, draw_shapes, vcount, maskE_it, seconds = [], [], [], [], []
+    rows, ray_counts, draw_shapes, vcount, maskE_it, seconds = [], [], [], [], [], []
     for k in range(kk):
         t0 = time.perf_counter()
-        fids = torch.tensor(frames_of(k, F, N))
-        draws = Draws(k)
-        torch.rand, torch.randn_like = draws.rand, draws.randn_like
-        try:
+        fids = torch.tensor(frames_of(k))
+        draws = scene.KeyedDraws(cfg["base"], k)
+        with rs.patched(draws):
             optimizer.zero_grad()
-            obs = observations(fids, H, W)
+            obs = scene.consistent_batch([cons_masks[int(f)] for f in fids]) if CONSISTENT else scene.noise_observations(fids, H, W, cache=obs_cache)
             if f64:
                 obs = {k_: v_.double() for k_, v_ in obs.items()}
                 torch.Tensor.float, real_float = (lambda self, *a, **kw: self.to(torch.float64)), torch.Tensor.float
             try:
-                loss = net(obs, SPX, ratio_of(k), fids)
+                loss = net(obs, SPX, scene.ratio_of(k), fids)
             finally:
                 if f64:
                     torch.Tensor.float = real_float
             loss.backward()
-            net.propagateTmpPsGrad(fids, ratio_of(k))
+            net.propagateTmpPsGrad(fids, scene.ratio_of(k))
             optimizer.step()
-        finally:
-            torch.rand, torch.randn_like = real_rand, real_randn_like
         info = net.info
-        for n in names:
-            curve[n].append(float(info.get(n, float('nan'))) if not (n == 'color_loss' and float(info.get(n, -1.)) < 0) else float('nan'))
-        curve['mask_loss'].append(float(info['pc_loss']['mask_loss'])); curve['defconst_loss'].append(float(info['pc_loss']['defconst_loss']))
-        curve['total'].append(float(loss))
+        rows.append(scene.loss_row(info, loss))
         ray_counts.append([int(info['rayInfo'][0]), int(info['rayInfo'][1])])
-        draw_shapes.append([list(s) + [0] * (2 - len(s)) for _, s in draws.calls] + [[0, 0]] * (6 - len(draws.calls)))
+        draw_shapes.append(draws.shape_rows(pad_to=6))
         vcount.append(net.TmpVs.shape[0])
         cover = (net.maskRender.last_p2f[..., 0] >= 0).float()
-        maskE_it.append(mask_error(cover, obs['mask'].float() if CONSISTENT else gtm1.expand(N, H, W)).tolist())
+        maskE_it.append(scene.mask_error(cover, obs['mask'].float() if CONSISTENT else gtm1.expand(N, H, W)).tolist())
         if k == REMESH_AT:
             out["cover_at_remesh"] = np.packbits(cover.numpy().astype(np.uint8))
         if 'V' in remeshed and "remesh_V" not in out:
             out["remesh_V"], out["remesh_nV"], out["remesh_nF"], out["remesh_k"] = remeshed['V'][::11].clone(), np.array(remeshed['V'].shape[0]), np.array(remeshed['F'].shape[0]), np.array(k)
         seconds.append(time.perf_counter() - t0)
-        print(k, frames_of(k, F, N), "loss %.6f" % float(loss), "rays", info['rayInfo'], "V", net.TmpVs.shape[0], "maskE", np.round(maskE_it[-1], 4).tolist(),
+        print(k, frames_of(k), "loss %.6f" % float(loss), "rays", info['rayInfo'], "V", net.TmpVs.shape[0], "maskE", np.round(maskE_it[-1], 4).tolist(),
               "%.1f s" % seconds[-1], flush=True)
     if f64:
-        print("float64 evaluation: total loss per iteration", [round(v, 6) for v in curve['total']], "pc_loss_sdf", [round(v, 6) for v in curve['pc_loss_sdf']])
+        print("float64 evaluation: total loss per iteration", [round(r['total'], 6) for r in rows], "pc_loss_sdf", [round(r['pc_loss_sdf'], 6) for r in rows])
         return
     if kk > REMESH_AT:
         assert "remesh_V" in out and int(out["remesh_k"]) == REMESH_AT
     # ---- the end state: maskE of `infer` (network.py:306-324) on EVAL_FRAMES, parameter digests
-    with torch.no_grad():
-        ef = torch.tensor(CONS_FRAMES[:4] if CONSISTENT else EVAL_FRAMES)
-        poses, trans, dcond, _ = ds.get_grad_parameters(ef, 'cpu')
-        defV = net.deformer(net.TmpVs.detach()[None].expand(len(EVAL_FRAMES), -1, 3), [dcond, [poses, trans]], ratio=ratio_of(kk))
-        xy, z = ro.ndc_projection(defV, ds.focal.detach(), ds.princ.detach(), ds.R[0], ds.T.detach(), W, H)
-        p2f, _, _ = ro.rasterize_meshes(torch.cat([xy, z[..., None]], -1).float().numpy(), net.Tmpfs.numpy(), H, W)
-        masks = torch.from_numpy((p2f >= 0)[..., 0]).float()
-        maskE = mask_error(masks, torch.stack([_CONS_MASKS[f] for f in CONS_FRAMES[:4]]) if CONSISTENT else gtm1.expand(len(EVAL_FRAMES), H, W))
+    ef = CONS_FRAMES[:4] if CONSISTENT else EVAL_FRAMES
+    maskE = rs.end_state(net, ds, net.deformer, ef, scene.ratio_of(kk), H, W, torch.stack([cons_masks[f] for f in ef]) if CONSISTENT else gtm1.expand(len(ef), H, W))
     out.update(maskE=maskE, maskE_it=np.array(maskE_it), ray_counts=np.array(ray_counts), draw_shapes=np.array(draw_shapes), vcount=np.array(vcount),
                seconds_per_iteration=np.array(seconds), cores=np.array(os.cpu_count()),
-               **{"L_" + n: np.array(v) for n, v in curve.items()})
-    for tag, mod in (("sdf", net.sdf), ("tr", net.deformer.defs[0]), ("rn", net.netRender)):
-        for i, (name, p) in enumerate(mod.named_parameters()):
-            out[f"d_{tag}.{name}"] = gf.param_digest(p, 100 * i)
+               **rs.loss_curves(rows))
+    rs.write_digests(out, net.sdf, net.deformer.defs[0], net.netRender)
     out["final_cam"] = torch.cat([ds.focal.detach(), ds.princ.detach(), ds.T.detach()])
     if CONSISTENT:
         out["cons_frames"] = np.array(CONS_FRAMES)
         out["cons_scale"] = np.array(CONS_SCALE)
-        out["cons_masks"] = np.stack([np.packbits(_CONS_MASKS[f].numpy().astype(np.uint8)) for f in CONS_FRAMES])
-        out["eval_frames"] = np.array(CONS_FRAMES[:4])
-    conv = {k_: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k_, v in out.items()}
+        out["cons_masks"] = np.stack([np.packbits(cons_masks[f].numpy().astype(np.uint8)) for f in CONS_FRAMES])
+        out["eval_frames"] = np.array(ef)
+    conv = rs.to_numpy(out)
     if cover_only:
         main = dict(np.load(os.path.join(OUT, cfg["name"])))
         # (the reference on CPU is not bit-reproducible run to run -- multi-threaded reductions: after ~9 iterations a re-run accepts one ray

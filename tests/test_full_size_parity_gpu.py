@@ -19,18 +19,13 @@ import torch
 from oracle import torch_oracle as orc
 from oracle import iteration_oracle as ito
 from oracle import fixtures as fx
+from oracle import scene
+from oracle.scene import PROJ_SEEDS, slice_of
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 RATIO = {'sdfRatio': 1., 'deformerRatio': 0.62, 'renderRatio': 1.}
-DRAW_SEED0, PROJ_SEEDS = 5000, (7001, 7002)          # oracle/gen_fullsize_golden.py
-_VOLUME = {}
-
-
-def lbs_volume_cpu(shape):
-    if shape not in _VOLUME:
-        _VOLUME[shape] = fx.synthetic_lbs_volume(shape)          # on the CPU: bit-identical to the reference run's volume
-    return _VOLUME[shape]
+DRAW_SEED0 = 5000          # oracle/gen_fullsize_golden.py
 
 
 class Report:
@@ -119,83 +114,22 @@ def l1_sign_correction(net, f_ref, weight, ratio, max_frac=0.01):
     return corr, stats
 
 
-def slice_of(t):
-    return t[::29, ::7] if (t.dim() == 2 and t.shape[1] > 1) else t.reshape(-1)[::5]
-
-
-def draws_for(shapes):
-    kinds = ['rand', 'rand', 'randn_like', 'rand', 'rand', 'randn_like']
-    names = ['ray_select', 'vert_select', 'eik_local', 'eik_global', 'vert_select2', 'regu_local']
-    if len(shapes) == 5:
-        kinds, names = kinds[1:], names[1:]
-    out = {}
-    for k, (kind, name, shape) in enumerate(zip(kinds, names, shapes)):
-        shape = tuple(int(s) for s in shape if int(s) > 0)
-        out[name] = (fx.det_tensor(shape, DRAW_SEED0 + k, 0.5) + 0.5) if kind == 'rand' else fx.det_normal(shape, DRAW_SEED0 + k)
-    return out
-
-
 def _golden_scene(g, stage):
     """The product's modules on the inputs of oracle/gen_fullsize_golden.py::build."""
+    import _product_scene as ps
     from selfreconcode_amd.config import default_config
-    from selfreconcode_amd.model.network import getTmpSdf
-    from selfreconcode_amd.model.Deformer import MLPTranslator, LBSkinner, CompositeDeformer
-    from selfreconcode_amd.model.RenderNet import RenderingNetwork_view_norm
-    from selfreconcode_amd.model.optim_network import OptimNetwork
-    from selfreconcode_amd.utils import smpl_tmp_Apose, DCTNullSpace
     Hh, Ww, F = int(g["HW"][0]), int(g["HW"][1]), int(g["frame_num"])
-    sdf = getTmpSdf(DEV, 6, 0.6, 256)
-    sdf.load_state_dict(fx.sphere_sdf_params(7), strict=True)
-    tr = MLPTranslator(128, 6).to(DEV)
-    tr.load_state_dict(fx.det_params(fx.DEF_SPEC, 202, last_scale=0.05), strict=True)
-    rn = RenderingNetwork_view_norm(256, 'idr', 9, 3, [512, 512, 512, 512], True, multires_n=0, multires_v=4).to(DEV)
-    rn.load_state_dict(fx.det_params(fx.REND_SPEC, 303), strict=True)
-    skin = LBSkinner(lbs_volume_cpu(tuple(int(s) for s in g["lbs_shape"])), fx.LBS_BMIN, fx.LBS_BMAX, fx.synthetic_joints(), np.array(fx.SMPL_PARENTS),
-                     init_pose=torch.from_numpy(smpl_tmp_Apose(1)), align_corners=False).to(DEV)
-    leaf = lambda t: t.to(DEV).clone().requires_grad_(True)
     learn = [bool(x) for x in g["learn_cam"].tolist()] if "learn_cam" in g else [True, True, True]       # opt_camera of the config the fixture ran with
-    cam = lambda on, t: leaf(t) if on else t.to(DEV)
-
-    class Seq:                                                        # the accessors of dataset/dataset.py:76-81,117-147
-        frame_num = F
-        poses, trans = leaf(fx.det_tensor((F, 24, 3), 91, 0.12)), leaf(fx.det_tensor((F, 3), 92, 0.04))
-        conds = [leaf(fx.det_tensor((F, 128), 93, 0.1)), leaf(fx.det_tensor((F, 256), 94, 0.1))]
-        camera_params = {'focal_length': cam(learn[0], torch.tensor([1.2 * Ww, 1.2 * Ww])), 'princeple_points': cam(learn[1], torch.tensor([Ww / 2.0, Hh / 2.0])),
-                         'world2cam_coord_trans': cam(learn[2], torch.tensor([0., 0.1, 2.4]))}
-        R = orc.quat2mat(torch.tensor([[0., 0., 1., 0.]]))[0].to(DEV)
-
-        def get_grad_parameters(self, idxs, device=None):
-            return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-        def get_camera_parameters(self, N, device=None):
-            c = self.camera_params
-            return (c['focal_length'].view(1, 2).expand(N, 2), c['princeple_points'].view(1, 2).expand(N, 2), self.R.view(1, 3, 3).expand(N, 3, 3),
-                    c['world2cam_coord_trans'].view(1, 3).expand(N, 3), Hh, Ww)
-
-        def get_batchframe_data(self, name, fids, batchsize):
-            data = getattr(self, name)
-            starts = (fids - batchsize // 2).clamp(min=0, max=self.frame_num - batchsize)
-            return data[starts.view(-1, 1) + torch.arange(0, batchsize, device=fids.device).view(1, batchsize)], fids - starts
-
-        def learnable_weights(self):
-            return [self.conds[0], self.conds[1]] + [t for t in self.camera_params.values() if t.requires_grad] + [self.poses, self.trans]
-    ds = Seq()
+    ds = scene.Sequence(F, Hh, Ww, DEV, learn_cam=tuple(n for n, on in zip(("focal", "princ", "T"), learn) if on))
     conf = default_config().get_config('loss_' + ('coarse' if stage == 'loose1080' else stage))
     if "normal_weight" in g:
         conf['normal_weight'] = float(g["normal_weight"])          # config_loose.conf:70 switches the normal loss off
-    net = OptimNetwork(sdf, CompositeDeformer([tr, skin]).to(DEV), None, None, rn, conf=conf).to(DEV)
-    net.dataset = ds
-    net.dctnull = DCTNullSpace(10, 30).to(DEV)
-    net.point_radius, net.angThred = float(g["radius"]), float(g["ang_thr"])
+    nets = sdf, tr, _, rn = ps.product_networks(g, DEV)
     dirs, faces = fx.cube_sphere(int(g["n_cube"]))
-    V0 = dirs * (0.6 + g["q"].float().view(-1, 1) / 65536.) + fx.det_tensor((dirs.shape[0], 3), 97, 0.004)
-    net.TmpVs, net.Tmpfs = V0.to(DEV).clone().requires_grad_(True), faces.to(DEV)
-    net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
-    net.forward_time = 1
+    V0 = scene.template_from_q(dirs, g["q"])
+    net = ps.product_net(ds, nets, None, conf, g["radius"], g["ang_thr"], V0, faces)
     N = int(g["fids"].numel())
-    ys, xs = torch.meshgrid(torch.arange(Hh).float(), torch.arange(Ww).float(), indexing='ij')
-    mask = (((xs - Ww / 2.0) / (0.2963 * Ww)) ** 2 + ((ys - 0.45 * Hh) / (0.3426 * Hh)) ** 2 < 1.0).float()
-    datas = {'img': fx.det_tensor((N, Hh, Ww, 3), 95, 1.0).to(DEV), 'mask': mask[None].expand(N, Hh, Ww).contiguous().to(DEV),
+    datas = {'img': fx.det_tensor((N, Hh, Ww, 3), 95, 1.0).to(DEV), 'mask': scene.elliptic_mask(Hh, Ww)[None].expand(N, Hh, Ww).contiguous().to(DEV),
              'normal': fx.det_tensor((N, Hh, Ww, 3), 96, 1.0)}
     datas['normal'][:, ::5] = 0.
     datas['normal'] = datas['normal'].to(DEV)
@@ -265,7 +199,7 @@ def test_full_size_iteration_vs_the_references_own_run(golden, stage):
             or (stage == "loose1080" and V0.shape[0] == 84968 and datas['img'].shape[:3] == (3, 1080, 1080)))      # configs[4]: config_loose.conf at 1080 x 1080
     assert mlp_engine.TN_SIDE_STREAM and getattr(net, 'refiner_stream', 'side') == 'side'        # the schedule bench.py times
     fids = g["fids"].long().to(DEV)
-    rand = {k: v.to(DEV) for k, v in draws_for(g["draw_shapes"].tolist()).items()}
+    rand = scene.draws(0, g["draw_shapes"].tolist(), DRAW_SEED0, 0, DEV)
     SP = int(g["SP"])
     rep = Report()
 

@@ -11,6 +11,7 @@ import torch
 from oracle import torch_oracle as orc
 from oracle import iteration_oracle as ito
 from oracle import fixtures as fx
+from oracle import scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -192,25 +193,7 @@ def test_propagate_tmp_ps_grad_vs_the_references_own_run(golden):
     tr.load_state_dict(fx.det_params(fx.DEF_SPEC, 202), strict=True)
     skin = LBSkinner(fx.synthetic_lbs_volume((7, 11, 9)), fx.LBS_BMIN, fx.LBS_BMAX, fx.synthetic_joints(), np.array(fx.SMPL_PARENTS),
                      init_pose=torch.from_numpy(smpl_tmp_Apose(1)), align_corners=False).to(DEV)
-    leaf = lambda t: t.to(DEV).clone().requires_grad_(True)
-
-    class Seq:                                                        # the accessors of dataset/dataset.py:76-81,117-127
-        poses, trans, conds = leaf(g["poses"]), leaf(g["trans"]), [leaf(g["dcond"]), leaf(g["rcond"])]
-        camera_params = {'focal_length': leaf(g["focal"]), 'princeple_points': leaf(g["princ"]), 'world2cam_coord_trans': leaf(g["T"])}
-        R = g["R"].to(DEV)
-        H, W = int(g["HW"][0]), int(g["HW"][1])
-
-        def get_grad_parameters(self, idxs, device=None):
-            return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-        def get_camera_parameters(self, N, device=None):
-            c = self.camera_params
-            return (c['focal_length'].view(1, 2).expand(N, 2), c['princeple_points'].view(1, 2).expand(N, 2), self.R.view(1, 3, 3).expand(N, 3, 3),
-                    c['world2cam_coord_trans'].view(1, 3).expand(N, 3), self.H, self.W)
-
-        def learnable_weights(self):
-            return [self.conds[0], self.conds[1]] + list(self.camera_params.values()) + [self.poses, self.trans]
-    ds = Seq()
+    ds = scene.Sequence(g["poses"].shape[0], int(g["HW"][0]), int(g["HW"][1]), DEV, tensors=g)
     net = OptimNetwork(sdf, CompositeDeformer([tr, skin]).to(DEV), None, None, None, conf=None)
     net.dataset = ds
     fids = g["fids"].long().to(DEV)
@@ -252,56 +235,14 @@ def test_whole_iteration_vs_the_references_own_run(golden):
     output against the reference's (flags flip on single ulps, so it is compared on its own and the reference's is used after it);
     every loss term, the total, the template SGD step, dL/dTmpPs and the gradients of the three networks, poses / translations /
     codes and the learnable focal length / principal point / T."""
-    import numpy as np
-    from selfreconcode_amd import mlp_engine
+    import _product_scene as ps
     from selfreconcode_amd.config import default_config
-    from selfreconcode_amd.model.network import getTmpSdf
-    from selfreconcode_amd.model.Deformer import MLPTranslator, LBSkinner, CompositeDeformer
-    from selfreconcode_amd.model.RenderNet import RenderingNetwork_view_norm
-    from selfreconcode_amd.model.optim_network import OptimNetwork
-    from selfreconcode_amd.utils import smpl_tmp_Apose
     from selfreconcode_amd.utils.FindSurfacePs import OptimizeSurfacePs
     g = golden("iteration")
-    Hh, Ww = int(g["HW"][0]), int(g["HW"][1])
-    sdf = getTmpSdf(DEV, 6, 0.6, 256)
-    sdf.load_state_dict(fx.sphere_sdf_params(7), strict=True)
-    tr = MLPTranslator(128, 6).to(DEV)
-    tr.load_state_dict(fx.det_params(fx.DEF_SPEC, 202, last_scale=0.05), strict=True)
-    rn = RenderingNetwork_view_norm(256, 'idr', 9, 3, [512, 512, 512, 512], True, multires_n=0, multires_v=4).to(DEV)
-    rn.load_state_dict(fx.det_params(fx.REND_SPEC, 303), strict=True)
-    skin = LBSkinner(fx.synthetic_lbs_volume((7, 11, 9)), fx.LBS_BMIN, fx.LBS_BMAX, fx.synthetic_joints(), np.array(fx.SMPL_PARENTS),
-                     init_pose=torch.from_numpy(smpl_tmp_Apose(1)), align_corners=False).to(DEV)
-    leaf = lambda t: t.to(DEV).clone().requires_grad_(True)
-
-    class Seq:                                                        # the accessors of dataset/dataset.py:76-81,117-147
-        frame_num = g["poses"].shape[0]
-        poses, trans, conds = leaf(g["poses"]), leaf(g["trans"]), [leaf(g["dcond"]), leaf(g["rcond"])]
-        camera_params = {'focal_length': leaf(g["focal"]), 'princeple_points': leaf(g["princ"]), 'world2cam_coord_trans': leaf(g["T"])}
-        R = g["R"].to(DEV)
-
-        def get_grad_parameters(self, idxs, device=None):
-            return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-        def get_camera_parameters(self, N, device=None):
-            c = self.camera_params
-            return (c['focal_length'].view(1, 2).expand(N, 2), c['princeple_points'].view(1, 2).expand(N, 2), self.R.view(1, 3, 3).expand(N, 3, 3),
-                    c['world2cam_coord_trans'].view(1, 3).expand(N, 3), Hh, Ww)
-
-        def get_batchframe_data(self, name, fids, batchsize):
-            data = getattr(self, name)
-            starts = (fids - batchsize // 2).clamp(min=0, max=self.frame_num - batchsize)
-            return data[starts.view(-1, 1) + torch.arange(0, batchsize, device=fids.device).view(1, batchsize)], fids - starts
-
-        def learnable_weights(self):
-            return [self.conds[0], self.conds[1]] + list(self.camera_params.values()) + [self.poses, self.trans]
-    ds = Seq()
-    net = OptimNetwork(sdf, CompositeDeformer([tr, skin]).to(DEV), None, None, rn, conf=default_config().get_config('loss_coarse')).to(DEV)
-    net.dataset = ds
+    nets = sdf, tr, _, rn = ps.product_networks((7, 11, 9), DEV)
+    ds = scene.Sequence(g["poses"].shape[0], int(g["HW"][0]), int(g["HW"][1]), DEV, tensors=g)
+    net = ps.product_net(ds, nets, None, default_config().get_config('loss_coarse'), g["radius"], g["ang_thr"], g["V0"], g["faces"].long())
     net.dctnull = golden("misc")["dctnull"].to(DEV)
-    net.point_radius, net.angThred = float(g["radius"]), float(g["ang_thr"])
-    net.TmpVs, net.Tmpfs = g["V0"].to(DEV).clone().requires_grad_(True), g["faces"].long().to(DEV)
-    net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
-    net.forward_time = 1
     fids = g["fids"].long().to(DEV)
     datas = {'img': g["img"].to(DEV), 'mask': g["mask"].to(DEV), 'normal': g["normal"].to(DEV)}
     rand = {k[5:]: v.to(DEV) for k, v in g.items() if k.startswith("rand_")}
@@ -321,8 +262,7 @@ def test_whole_iteration_vs_the_references_own_run(golden):
 
     # (2) the whole iteration with the reference's draws and the reference's refiner output
     rand['refined'] = (g["sel_p1"], ref_ok)
-    mlp_engine.set_deferred_param_grads(True)
-    try:
+    with ps.deferred_param_grads():
         dbg = {}
         loss = net(datas, SP, RATIO, fids, rand=rand, debug=dbg)
         assert torch.equal(dbg['batch_inds'].cpu(), g["sel_bi"].long()) and dbg['batch_inds'].numel() == int(g["ray_info"][0])
@@ -340,8 +280,6 @@ def test_whole_iteration_vs_the_references_own_run(golden):
         loss.backward()
         close(net.TmpPs.grad, g["g_TmpPs"], 2e-3, 3e-3, "dL/dTmpPs")
         net.propagateTmpPsGrad(fids, RATIO)
-    finally:
-        mlp_engine.set_deferred_param_grads(False)
     assert int(net.info['invInfo'][0]) == int(g["inv_info"][0]) and abs(int(net.info['invInfo'][1]) - int(g["inv_info"][1])) <= 1
     sp, tp, rp = dict(sdf.named_parameters()), dict(tr.named_parameters()), dict(rn.named_parameters())
     tol = dict(rtol=4e-3, frac=4e-3)

@@ -6,6 +6,7 @@ import pytest
 import torch
 from oracle import torch_oracle as orc
 from oracle import fixtures as fx
+from oracle import scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -19,6 +20,10 @@ def close(a, b, rtol=1e-3, atol=None):
 
 
 class _MiniData:
+    """Not scene.Sequence: these tests pin single loss terms on a FIXED camera that is no `camera_params` dict (the product then builds
+    its cameras afresh on every call), with seeds and a tilt of their own; only the frame-window accessor is the shared one."""
+    get_batchframe_data = scene.Sequence.get_batchframe_data
+
     def __init__(self, F=40):
         self.poses = (fx.det_tensor((F, 24, 3), 1, 0.1)).to(DEV).requires_grad_(True)
         self.trans = (fx.det_tensor((F, 3), 2, 0.05)).to(DEV).requires_grad_(True)
@@ -32,11 +37,6 @@ class _MiniData:
         R = orc.quat2mat(torch.tensor([[0.02, 0.01, 0.999, 0.03]]))[0].to(DEV)
         return (torch.tensor([[150., 150.]], device=DEV).expand(N, 2), torch.tensor([[64., 64.]], device=DEV).expand(N, 2),
                 R[None].expand(N, 3, 3), torch.tensor([[0., 0.1, 2.4]], device=DEV).expand(N, 3), 128, 128)
-
-    def get_batchframe_data(self, name, fids, n):
-        data = getattr(self, name)
-        starts = (fids - n // 2).clamp(min=0, max=self.frame_num - n)
-        return data[starts.view(-1, 1) + torch.arange(0, n, device=fids.device).view(1, n)], fids - starts
 
 
 def _build():

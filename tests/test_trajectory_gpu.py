@@ -21,139 +21,60 @@ PRODUCT run twice, the second time with its initial template perturbed by one ul
 import numpy as np
 import pytest
 import torch
-from oracle import torch_oracle as orc
 from oracle import fixtures as fx
+from oracle import scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 DRAW_BASE = 9000
-
-
-def _draws(k, shapes):
-    shapes = [tuple(int(x) for x in s if int(x) > 0) for s in shapes if int(s[0]) > 0]
-    kinds = ['rand', 'rand', 'randn_like', 'rand', 'rand', 'randn_like']
-    names = ['ray_select', 'vert_select', 'eik_local', 'eik_global', 'vert_select2', 'regu_local']
-    if len(shapes) == 5:
-        kinds, names = kinds[1:], names[1:]
-    out = {}
-    for c, (kind, name, shape) in enumerate(zip(kinds, names, shapes)):
-        shape = (shape[0] + 64,) + tuple(shape[1:])         # a few spare rows (the tensors are functions of the flat index: same head): the product's
-        out[name] = ((fx.det_tensor(shape, DRAW_BASE + 16 * k + c, 0.5) + 0.5) if kind == 'rand' else fx.det_normal(shape, DRAW_BASE + 16 * k + c)).to(DEV)      # counts may differ by a ray
-    return out
+SPARE = 64          # a few spare rows per draw: the product's counts may differ by a ray
 
 
 def test_twenty_iterations_follow_the_references_own_run(golden):
     from _inject import keyed_refiner
-    from selfreconcode_amd import mlp_engine
+    import _product_scene as ps
     from selfreconcode_amd.config import default_config
-    from selfreconcode_amd.model.network import getTmpSdf
-    from selfreconcode_amd.model.Deformer import MLPTranslator, LBSkinner, CompositeDeformer
-    from selfreconcode_amd.model.RenderNet import RenderingNetwork_view_norm
-    from selfreconcode_amd.model.optim_network import OptimNetwork
-    from selfreconcode_amd.MCAcc import Seg3dLossless
-    from selfreconcode_amd.utils import smpl_tmp_Apose, DCTNullSpace
     g = golden("trajectory")
     H, W, F, K, SP = int(g["HW"][0]), int(g["HW"][1]), int(g["frame_num"]), int(g["K"]), int(g["SP"])
     REMESH = int(g["remesh_at"])
-    volume = fx.synthetic_lbs_volume(tuple(int(s) for s in g["lbs_shape"]))
-    ys, xs = torch.meshgrid(torch.arange(H).float(), torch.arange(W).float(), indexing='ij')
-    mask1 = (((xs - W / 2.0) / (0.2963 * W)) ** 2 + ((ys - 0.45 * H) / (0.3426 * H)) ** 2 < 1.0).float()
-    terms = ('grad_loss', 'def_loss', 'dct_loss', 'color_loss', 'normal_loss', 'offset_loss', 'pc_loss_sdf', 'mask_loss', 'defconst_loss')
-
-    def observations(fids):
-        img = torch.stack([fx.det_tensor((H, W, 3), 9100 + int(f), 1.0) for f in fids])
-        nrm = torch.stack([fx.det_tensor((H, W, 3), 9200 + int(f), 1.0) for f in fids])
-        nrm[:, ::5] = 0.
-        return {'img': img.to(DEV), 'mask': mask1[None].expand(len(fids), H, W).contiguous().to(DEV), 'normal': nrm.to(DEV)}
+    terms = scene.LOSS_TERMS + ('mask_loss', 'defconst_loss')
+    obs_cache = {}
 
     def run(perturb):
         """20 iterations of the product.  perturb: the initial template moved by one ulp (the 'twin').  Returns the per-iteration loss
         rows, the ray matching against the reference, the product's own remesh, maskE at the end."""
-        sdf = getTmpSdf(DEV, 6, 0.6, 256)
-        sdf.load_state_dict(fx.sphere_sdf_params(7), strict=True)
-        tr = MLPTranslator(128, 6).to(DEV)
-        tr.load_state_dict(fx.det_params(fx.DEF_SPEC, 202, last_scale=0.05), strict=True)
-        rn = RenderingNetwork_view_norm(256, 'idr', 9, 3, [512, 512, 512, 512], True, multires_n=0, multires_v=4).to(DEV)
-        rn.load_state_dict(fx.det_params(fx.REND_SPEC, 303), strict=True)
-        skin = LBSkinner(volume, fx.LBS_BMIN, fx.LBS_BMAX, fx.synthetic_joints(), np.array(fx.SMPL_PARENTS), init_pose=torch.from_numpy(smpl_tmp_Apose(1)),
-                         align_corners=False).to(DEV)
-        leaf = lambda t: t.to(DEV).clone().requires_grad_(True)
-
-        class Seq:
-            frame_num = F
-            poses, trans = leaf(fx.det_tensor((F, 24, 3), 91, 0.12)), leaf(fx.det_tensor((F, 3), 92, 0.04))
-            conds = [leaf(fx.det_tensor((F, 128), 93, 0.1)), leaf(fx.det_tensor((F, 256), 94, 0.1))]
-            camera_params = {'focal_length': leaf(torch.tensor([1.2 * W, 1.2 * W])), 'princeple_points': leaf(torch.tensor([W / 2.0, H / 2.0])),
-                             'world2cam_coord_trans': leaf(torch.tensor([0., 0.1, 2.4]))}
-            R = orc.quat2mat(torch.tensor([[0., 0., 1., 0.]]))[0].to(DEV)
-
-            def get_grad_parameters(self, idxs, device=None):
-                return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-            def get_camera_parameters(self, N, device=None):
-                c = self.camera_params
-                return (c['focal_length'].view(1, 2).expand(N, 2), c['princeple_points'].view(1, 2).expand(N, 2), self.R.view(1, 3, 3).expand(N, 3, 3),
-                        c['world2cam_coord_trans'].view(1, 3).expand(N, 3), H, W)
-
-            def get_batchframe_data(self, name, fids, batchsize):
-                data = getattr(self, name)
-                starts = (fids - batchsize // 2).clamp(min=0, max=self.frame_num - batchsize)
-                return data[starts.view(-1, 1) + torch.arange(0, batchsize, device=fids.device).view(1, batchsize)], fids - starts
-
-            def learnable_weights(self):
-                return [self.conds[0], self.conds[1]] + list(self.camera_params.values()) + [self.poses, self.trans]
-        ds = Seq()
-        engine = Seg3dLossless(query_func=None, b_min=fx.LBS_BMIN, b_max=fx.LBS_BMAX, resolutions=[tuple(int(x) for x in r) for r in g["res"]], align_corners=False,
-                               balance_value=0.0, use_cuda_impl=True).to(DEV)
-        net = OptimNetwork(sdf, CompositeDeformer([tr, skin]).to(DEV), engine, None, rn, conf=default_config().get_config('loss_coarse')).to(DEV)
-        net.dataset = ds
-        net.dctnull = DCTNullSpace(10, 30).to(DEV)
-        net.point_radius, net.angThred = float(g["radius"]), float(g["ang_thr"])
-        dirs, faces = fx.icosphere(3)
-        V0 = dirs * (0.6 + g["q"].float().view(-1, 1) / 65536.) + fx.det_tensor((dirs.shape[0], 3), 97, 0.004)
+        ds = scene.Sequence(F, H, W, DEV)
+        V0 = scene.template_from_q(fx.icosphere(3)[0], g["q"])
         if perturb:
             V0 = V0 * (1.0 + 1e-7 * fx.det_tensor(tuple(V0.shape), 4242, 1.0))
-        net.TmpVs, net.Tmpfs = V0.to(DEV).clone().requires_grad_(True), faces.to(DEV)
-        net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
-        net.remesh_intersect = 30
-        net.forward_time = 30 - REMESH
-        opt = torch.optim.Adam([{'params': ds.learnable_weights()}, {'params': [p for p in net.parameters() if p.requires_grad]}], lr=float(g["lr"]))
-        mlp_engine.set_deferred_param_grads(True)
-        state, log, matched, remesh = {}, [], [], None
-        try:
-            with keyed_refiner(state, H, W):
-                for k in range(K):
-                    fids = torch.tensor([(7 + 3 * k) % F, (21 + 5 * k) % F], device=DEV)
-                    ratio = {'sdfRatio': 1., 'deformerRatio': k / 2500. + 0.5, 'renderRatio': 1.}
-                    rand = _draws(k, g["draw_shapes"][k].tolist())
-                    opt.zero_grad(set_to_none=True)
-                    if k == REMESH:
-                        # The remesh of this iteration, done by hand so that it can be looked at; the run then continues on the REFERENCE's
-                        # mesh (a vertex more or less in the list would shift every later index and with it the index-keyed random subsets).
-                        with torch.no_grad():
-                            verts, faces_k = net.discretizeSDF(ratio, None, -net.sdfShrinkRadius)
-                        remesh = (verts.detach().clone(), faces_k.shape[0])
-                        net.TmpVs, net.Tmpfs = g["remesh_V"].to(DEV).clone().requires_grad_(True), g["remesh_F"].long().to(DEV)
-                        net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
-                        net.remesh_intersect = 10 ** 9                   # (forward must not remesh again)
-                    dbg = {}
-                    state.update(dbg=dbg, ref=(g[f"k{k}_bi"], g[f"k{k}_rc"][:, 0], g[f"k{k}_rc"][:, 1], g[f"k{k}_p1"], g[f"k{k}_check"]))
-                    loss = net(observations(fids), SP, ratio, fids, rand=rand, debug=dbg)
-                    matched.append(state['matched'])
-                    loss.backward()
-                    net.propagateTmpPsGrad(fids, ratio)
-                    opt.step()
-                    i = net.info
-                    row = {n: float(i[n]) if n in i and not (n == 'color_loss' and float(i[n]) < 0) else float('nan') for n in terms[:7]}
-                    row['mask_loss'], row['defconst_loss'] = float(i['pc_loss']['mask_loss']), float(i['pc_loss']['defconst_loss'])
-                    row['total'] = float(loss.detach())
-                    log.append(row)
-        finally:
-            mlp_engine.set_deferred_param_grads(False)
+        net = ps.product_net(ds, ps.product_networks(g, DEV), ps.product_engine(g["res"], DEV), default_config().get_config('loss_coarse'), g["radius"], g["ang_thr"],
+                             V0, fx.icosphere(3)[1], remesh_intersect=30, first_remesh=REMESH)
+        opt = ps.adam_over(ds, net, float(g["lr"]))
+        state, log, matched, remesh = {}, [], [], []
+
+        def remesh_by_hand():
+            # The remesh of this iteration, done by hand so that it can be looked at; the run then continues on the REFERENCE's
+            # mesh (a vertex more or less in the list would shift every later index and with it the index-keyed random subsets).
+            with torch.no_grad():
+                verts, faces_k = net.discretizeSDF(scene.ratio_of(REMESH), None, -net.sdfShrinkRadius)
+            remesh.append((verts.detach().clone(), faces_k.shape[0]))
+            net.TmpVs, net.Tmpfs = g["remesh_V"].to(DEV).clone().requires_grad_(True), g["remesh_F"].long().to(DEV)
+            net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
+            net.remesh_intersect = 10 ** 9                   # (forward must not remesh again)
+        with ps.deferred_param_grads(), keyed_refiner(state, H, W):
+            for k in range(K):
+                fids = torch.tensor(scene.frames_20(k, F), device=DEV)
+                dbg = {}
+                state.update(dbg=dbg, ref=(g[f"k{k}_bi"], g[f"k{k}_rc"][:, 0], g[f"k{k}_rc"][:, 1], g[f"k{k}_p1"], g[f"k{k}_check"]))
+                loss = ps.train_iteration(net, opt, scene.noise_observations(fids, H, W, DEV, obs_cache), SP, scene.ratio_of(k), fids,
+                                          scene.draws(k, g["draw_shapes"][k].tolist(), DRAW_BASE, SPARE, DEV), debug=dbg,
+                                          before_forward=remesh_by_hand if k == REMESH else None)
+                matched.append(state['matched'])
+                log.append(scene.loss_row(net.info, loss))
         ef = g["eval_frames"].long().to(DEV)
-        gts = {'mask': mask1[None].expand(ef.numel(), H, W).contiguous().to(DEV)}
-        net.infer(net.TmpVs.detach(), net.Tmpfs, H, W, {'sdfRatio': 1., 'deformerRatio': K / 2500. + 0.5, 'renderRatio': 1.}, ef, notcolor=True, gts=gts)
-        return log, matched, remesh, np.asarray(gts['maskE'])
+        gts = {'mask': scene.elliptic_mask(H, W)[None].expand(ef.numel(), H, W).contiguous().to(DEV)}
+        net.infer(net.TmpVs.detach(), net.Tmpfs, H, W, scene.ratio_of(K), ef, notcolor=True, gts=gts)
+        return log, matched, remesh[0], np.asarray(gts['maskE'])
 
     rel = lambda a, b: abs(a - b) / max(abs(b), 1e-12)
 

@@ -18,43 +18,22 @@ injected refiner output, the product's own remeshes):
 import numpy as np
 import pytest
 import torch
-from oracle import torch_oracle as orc
 from oracle import fixtures as fx
+from oracle import scene
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 DRAW_BASE = 19000
-
-
-def _draws(k, shapes):
-    shapes = [tuple(int(x) for x in s if int(x) > 0) for s in shapes if int(s[0]) > 0]
-    kinds = ['rand', 'rand', 'randn_like', 'rand', 'rand', 'randn_like']
-    names = ['ray_select', 'vert_select', 'eik_local', 'eik_global', 'vert_select2', 'regu_local']
-    if len(shapes) == 5:
-        kinds, names = kinds[1:], names[1:]
-    out = {}
-    for c, (kind, name, shape) in enumerate(zip(kinds, names, shapes)):
-        shape = (shape[0] + 4096,) + tuple(shape[1:])       # spare rows: free-running, the product's counts differ from the reference's
-        out[name] = ((fx.det_tensor(shape, DRAW_BASE + 16 * k + c, 0.5) + 0.5) if kind == 'rand' else fx.det_normal(shape, DRAW_BASE + 16 * k + c)).to(DEV)
-    return out
+SPARE = 4096        # spare rows per draw: free-running, the product's counts differ from the reference's
 
 
 def test_sixty_four_iterations_four_remeshes_and_a_stage_switch(golden):
-    from selfreconcode_amd import mlp_engine
+    import _product_scene as ps
     from selfreconcode_amd.config import default_config
-    from selfreconcode_amd.model.network import getTmpSdf
-    from selfreconcode_amd.model.Deformer import MLPTranslator, LBSkinner, CompositeDeformer
-    from selfreconcode_amd.model.RenderNet import RenderingNetwork_view_norm
-    from selfreconcode_amd.model.optim_network import OptimNetwork
-    from selfreconcode_amd.MCAcc import Seg3dLossless
-    from selfreconcode_amd.utils import smpl_tmp_Apose, DCTNullSpace
     from selfreconcode_amd.utils.checkpoint import set_hierarchical_config
     g = golden("trajectory_long")
     H, W, F, K, SP = int(g["HW"][0]), int(g["HW"][1]), int(g["frame_num"]), int(g["K"]), int(g["SP"])
     SWITCH, FIRST = int(g["switch_at"]), int(g["first_remesh"])
-    volume = fx.synthetic_lbs_volume(tuple(int(s) for s in g["lbs_shape"]))
-    ys, xs = torch.meshgrid(torch.arange(H).float(), torch.arange(W).float(), indexing='ij')
-    mask1 = (((xs - W / 2.0) / (0.2963 * W)) ** 2 + ((ys - 0.45 * H) / (0.3426 * H)) ** 2 < 1.0).float()
     res = {s: [tuple(int(x) for x in r) for r in g[s + "_res"]] for s in ("coarse", "medium")}
     # config.conf with the miniature's stage parameters (the generator's STAGE table)
     conf = default_config()
@@ -62,82 +41,27 @@ def test_sixty_four_iterations_four_remeshes_and_a_stage_switch(golden):
         conf['train'][s]['point_render']['radius'] = float(g[s + "_radius"])
         conf['train'][s]['point_render']['remesh_intersect'] = int(g[s + "_remesh"])
         conf['train'][s]['point_render']['batch_size'] = int(g[s + "_N"])
-
-    def observations(fids):
-        img = torch.stack([fx.det_tensor((H, W, 3), 9100 + int(f), 1.0) for f in fids])
-        nrm = torch.stack([fx.det_tensor((H, W, 3), 9200 + int(f), 1.0) for f in fids])
-        nrm[:, ::5] = 0.
-        return {'img': img.to(DEV), 'mask': mask1[None].expand(len(fids), H, W).contiguous().to(DEV), 'normal': nrm.to(DEV)}
-
-    sdf = getTmpSdf(DEV, 6, 0.6, 256)
-    sdf.load_state_dict(fx.sphere_sdf_params(7), strict=True)
-    tr = MLPTranslator(128, 6).to(DEV)
-    tr.load_state_dict(fx.det_params(fx.DEF_SPEC, 202, last_scale=0.05), strict=True)
-    rn = RenderingNetwork_view_norm(256, 'idr', 9, 3, [512, 512, 512, 512], True, multires_n=0, multires_v=4).to(DEV)
-    rn.load_state_dict(fx.det_params(fx.REND_SPEC, 303), strict=True)
-    skin = LBSkinner(volume, fx.LBS_BMIN, fx.LBS_BMAX, fx.synthetic_joints(), np.array(fx.SMPL_PARENTS), init_pose=torch.from_numpy(smpl_tmp_Apose(1)),
-                     align_corners=False).to(DEV)
-    leaf = lambda t: t.to(DEV).clone().requires_grad_(True)
-
-    class Seq:
-        frame_num = F
-        poses, trans = leaf(fx.det_tensor((F, 24, 3), 91, 0.12)), leaf(fx.det_tensor((F, 3), 92, 0.04))
-        conds = [leaf(fx.det_tensor((F, 128), 93, 0.1)), leaf(fx.det_tensor((F, 256), 94, 0.1))]
-        camera_params = {'focal_length': leaf(torch.tensor([1.2 * W, 1.2 * W])), 'princeple_points': leaf(torch.tensor([W / 2.0, H / 2.0])),
-                         'world2cam_coord_trans': leaf(torch.tensor([0., 0.1, 2.4]))}
-        R = orc.quat2mat(torch.tensor([[0., 0., 1., 0.]]))[0].to(DEV)
-
-        def get_grad_parameters(self, idxs, device=None):
-            return self.poses[idxs], self.trans[idxs], self.conds[0][idxs], self.conds[1][idxs]
-
-        def get_camera_parameters(self, N, device=None):
-            c = self.camera_params
-            return (c['focal_length'].view(1, 2).expand(N, 2), c['princeple_points'].view(1, 2).expand(N, 2), self.R.view(1, 3, 3).expand(N, 3, 3),
-                    c['world2cam_coord_trans'].view(1, 3).expand(N, 3), H, W)
-
-        def get_batchframe_data(self, name, fids, batchsize):
-            data = getattr(self, name)
-            starts = (fids - batchsize // 2).clamp(min=0, max=self.frame_num - batchsize)
-            return data[starts.view(-1, 1) + torch.arange(0, batchsize, device=fids.device).view(1, batchsize)], fids - starts
-
-        def learnable_weights(self):
-            return [self.conds[0], self.conds[1]] + list(self.camera_params.values()) + [self.poses, self.trans]
-    ds = Seq()
-    engine = Seg3dLossless(query_func=None, b_min=fx.LBS_BMIN, b_max=fx.LBS_BMAX, resolutions=res["coarse"], align_corners=False, balance_value=0.0, use_cuda_impl=True).to(DEV)
-    net = OptimNetwork(sdf, CompositeDeformer([tr, skin]).to(DEV), engine, None, rn, conf=conf.get_config('loss_coarse')).to(DEV)
-    net.dataset = ds
-    net.dctnull = DCTNullSpace(10, 30).to(DEV)
-    net.point_radius, net.angThred = float(g["coarse_radius"]), float(g["ang_thr"])
+    ds = scene.Sequence(F, H, W, DEV)
     dirs, faces = fx.icosphere(3)
-    V0 = dirs * (0.6 + g["q"].float().view(-1, 1) / 65536.) + fx.det_tensor((dirs.shape[0], 3), 97, 0.004)
-    net.TmpVs, net.Tmpfs = V0.to(DEV).clone().requires_grad_(True), faces.to(DEV)
-    net.TmpOptimizer = torch.optim.SGD([net.TmpVs], lr=0.05, momentum=0.9)
-    net.remesh_intersect = int(g["coarse_remesh"])
-    net.forward_time = net.remesh_intersect - FIRST
-    opt = torch.optim.Adam([{'params': ds.learnable_weights()}, {'params': [p for p in net.parameters() if p.requires_grad]}], lr=float(g["lr"]))
-    mlp_engine.set_deferred_param_grads(True)
-    rays, totals, remeshes, stage_of, nb = [], [], [], [], int(g["coarse_N"])
-    try:
+    net = ps.product_net(ds, ps.product_networks(g, DEV), ps.product_engine(res["coarse"], DEV), conf.get_config('loss_coarse'), g["coarse_radius"], g["ang_thr"],
+                         scene.template_from_q(dirs, g["q"]), faces, remesh_intersect=int(g["coarse_remesh"]), first_remesh=FIRST)
+    opt = ps.adam_over(ds, net, float(g["lr"]))
+    rays, totals, remeshes, stage_of, nb, obs_cache = [], [], [], [], int(g["coarse_N"]), {}
+    with ps.deferred_param_grads():
         for k in range(K):
             if k == SWITCH:                                  # train.py:148-152: the epoch boundary where the medium stage starts
                 set_hierarchical_config(conf, 'medium', net, None, res["medium"])
                 nb = conf.get_int('train.medium.point_render.batch_size')
-            fids = torch.tensor([(7 + 3 * k + 11 * j) % F for j in range(nb)], device=DEV)
-            ratio = {'sdfRatio': 1., 'deformerRatio': k / 2500. + 0.5, 'renderRatio': 1.}
+            fids = torch.tensor(scene.frames_64(k, F, nb), device=DEV)
             before = net.TmpVs
-            opt.zero_grad(set_to_none=True)
-            loss = net(observations(fids), SP, ratio, fids, rand=_draws(k, g["draw_shapes"][k].tolist()))
+            loss = ps.train_iteration(net, opt, scene.noise_observations(fids, H, W, DEV, obs_cache), SP, scene.ratio_of(k), fids,
+                                      scene.draws(k, g["draw_shapes"][k].tolist(), DRAW_BASE, SPARE, DEV))
             if net.TmpVs is not before:
                 remeshes.append((k, int(net.TmpVs.shape[0]), int(net.Tmpfs.shape[0])))
-            loss.backward()
-            net.propagateTmpPsGrad(fids, ratio)
-            opt.step()
             rays.append((int(net.info['rayInfo'][0]), int(net.info['rayInfo'][1])))
             totals.append(float(loss.detach()))
             stage_of.append(0 if net.next_conf is not None or k < int(g["remesh_iters"][2]) else 1)
             assert np.isfinite(totals[-1]), k
-    finally:
-        mlp_engine.set_deferred_param_grads(False)
     rays = np.array(rays, dtype=np.float64); ref_rays = g["ray_counts"].numpy().astype(np.float64)
     # ---- the schedule
     assert [r[0] for r in remeshes] == g["remesh_iters"].tolist() == [6, 18, 30, 50], remeshes
@@ -160,8 +84,8 @@ def test_sixty_four_iterations_four_remeshes_and_a_stage_switch(golden):
     print("converged fraction away from the remeshes: %.3f (reference %.3f)" % (rays[between, 1].sum() / rays[between, 0].sum(), ref_rays[between, 1].sum() / ref_rays[between, 0].sum()))
     # ---- the end state
     ef = g["eval_frames"].long().to(DEV)
-    gts = {'mask': mask1[None].expand(ef.numel(), H, W).contiguous().to(DEV)}
-    net.infer(net.TmpVs.detach(), net.Tmpfs, H, W, {'sdfRatio': 1., 'deformerRatio': K / 2500. + 0.5, 'renderRatio': 1.}, ef, notcolor=True, gts=gts)
+    gts = {'mask': scene.elliptic_mask(H, W)[None].expand(ef.numel(), H, W).contiguous().to(DEV)}
+    net.infer(net.TmpVs.detach(), net.Tmpfs, H, W, scene.ratio_of(K), ef, notcolor=True, gts=gts)
     maskE = np.asarray(gts['maskE'])
     print("maskE product", np.round(maskE, 4).tolist(), "reference", np.round(g["maskE"].numpy(), 4).tolist())
     assert np.abs(maskE - g["maskE"].numpy()).max() < 0.03
