@@ -604,6 +604,30 @@ int sr_meshreg_bwd(int64_t V, const int32_t* nbr_row, const int32_t* nbr, int64_
                    const float* lap_q, const float* edge_g, const float* pair_g, const float* g_lap, const float* g_edge, const float* g_nc,
                    float* grad, void* stream);
 
+/* Frames of a capture sequence kept on the GPU as bytes (csrc/frames.hip): what dataset/dataset.py:85-115 decodes and uploads per
+ * iteration, as one launch per batch.  The store, written once: img_u8 [F, pitch3] and normal_u8 [F, pitch3] (NULL: the sequence has
+ * no normals; then out_normal is NULL too) hold H*W*3 bytes per frame in the order cv2.imread gives them (B, G, R per pixel),
+ * mask_u8 [F, pitch1] holds H*W bytes, each 0 or 1.  The bytes behind a frame up to its pitch are padding and are never converted.
+ *   sr_frames_fetch: for slot n < N with frame f = ids[n], out_img [N,H,W,3] = (b / 255 - 0.5) * 2, out_normal [N,H,W,3] =
+ *     (2 b) / 255 - 1 with the three channels of each pixel reversed, out_mask [N,H,W] = (float) m: the reference's float32
+ *     expressions with IEEE division, bit for bit.  The ids come EITHER by value, ids_by_value a HOST pointer to an sr_frame_ids whose
+ *     first N entries are used (copied into the launch: no transfer, no synchronisation), OR from DEVICE memory, ids_device [N]
+ *     int64; exactly one of the two is non-NULL.  An id outside [0, F) reads nothing: its slot is NaN in out_img / out_normal and 0
+ *     in out_mask.
+ * Limits (SR_EINVAL beyond them): pitch3 and pitch1 multiples of 16 with pitch3 >= 3 H W and pitch1 >= H W; the three stores 16-byte
+ * aligned; 1 <= N <= SR_FRAMES_MAX_BATCH by value, N <= 65535 from device memory (the slot is a grid's second dimension);
+ * H W <= SR_FRAMES_MAX_PIXELS.  16-byte stores are used when H W % 4 == 0 and the outputs are 16-byte aligned, dword stores otherwise.
+ * No atomics: two calls give identical bits. */
+#define SR_FRAMES_MAX_BATCH 16
+#define SR_FRAMES_MAX_PIXELS 1073741824
+struct sr_frame_ids_s {
+  int32_t id[SR_FRAMES_MAX_BATCH];
+};
+typedef struct sr_frame_ids_s sr_frame_ids;
+int sr_frames_fetch(const uint8_t* img_u8, const uint8_t* normal_u8, const uint8_t* mask_u8, int64_t pitch3, int64_t pitch1, int32_t F, int32_t H,
+                    int32_t W, const sr_frame_ids* ids_by_value, const int64_t* ids_device, int32_t N, float* out_img, float* out_normal,
+                    float* out_mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

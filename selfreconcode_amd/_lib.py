@@ -123,6 +123,13 @@ class SrRayPixels(ctypes.Structure):
     _fields_ = [("b", _vp), ("r", _vp), ("c", _vp), ("P", _i64), ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
 
 
+SR_FRAMES_MAX_BATCH = 16
+
+
+class SrFrameIds(ctypes.Structure):
+    _fields_ = [("id", ctypes.c_int32 * SR_FRAMES_MAX_BATCH)]
+
+
 class SrError(RuntimeError):
     pass
 
@@ -242,6 +249,7 @@ SIGNATURES = {
     "sr_meshreg_workspace_bytes": [_i64, _i64],
     "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
     "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,
+    "sr_frames_fetch": [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
     "sr_pe_embed_bwd": [_vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp],
     "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
 }

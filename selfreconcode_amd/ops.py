@@ -323,3 +323,58 @@ def meshreg_bwd(saved, nbr_row, nbr, pair_row, pair_ent, num_verts, g_lap, g_edg
     grad = torch.empty((V, 3), dtype=torch.float32, device=nbr_row.device)
     _lib.launch("sr_meshreg_bwd", grad, V, nbr_row, nbr, E, pair_row, pair_ent, P, lap_q, edge_g, pair_g, g_lap, g_edge, g_nc, grad)
     return grad
+
+
+# ------------------------------------------------------------------ frames of a capture sequence kept on the GPU as bytes (csrc/frames.hip)
+FRAMES_MAX_BATCH = _lib.SR_FRAMES_MAX_BATCH
+FRAMES_PITCH_ALIGN = 16
+
+
+def frames_pitch(nbytes):
+    """The frame pitch of a store whose frames hold `nbytes` bytes: the next multiple of 16, so that every frame starts 16-byte aligned."""
+    return -(-int(nbytes) // FRAMES_PITCH_ALIGN) * FRAMES_PITCH_ALIGN
+
+
+def frames_fetch(img_u8, normal_u8, mask_u8, H, W, frame_ids, out=None):
+    """(img [N,H,W,3], normal [N,H,W,3] or None, mask [N,H,W]) float32 of the frames `frame_ids` (sr_frames_fetch) from the uint8 stores
+    img_u8 / normal_u8 [F, pitch3] (B, G, R per pixel as cv2.imread gives them; normal_u8 None: no normals) and mask_u8 [F, pitch1]
+    (0 / 1): img = (b / 255 - 0.5) * 2, normal = (2 b) / 255 - 1 with the channels of a pixel reversed, mask = float(m), bit for bit the
+    reference's float32 expressions.  `frame_ids` as a list, range or CPU tensor is range-checked here (IndexError) and travels by value
+    inside the launch, FRAMES_MAX_BATCH ids per launch: no copy, no synchronisation.  As a device tensor (int64) it is read by the
+    kernel in one launch; an id outside [0, F) then gives a frame of NaN (img, normal) / 0 (mask) and reads nothing.  `out`: the three
+    result tensors to write into (contiguous float32 of the result's size; None for the normal of a store without normals)."""
+    _lib.require_gpu(img_u8, normal_u8, mask_u8)
+    for t, name in ((img_u8, "img_u8"), (normal_u8, "normal_u8"), (mask_u8, "mask_u8")):
+        if t is not None and (t.dtype != torch.uint8 or t.dim() != 2 or not t.is_contiguous()):
+            raise ValueError(f"frames_fetch: {name} must be a contiguous uint8 store [F, pitch], got {t.dtype} {tuple(t.shape)}")
+    F, pitch3, pitch1, H, W = img_u8.shape[0], img_u8.shape[1], mask_u8.shape[1], int(H), int(W)
+    if mask_u8.shape[0] != F or (normal_u8 is not None and tuple(normal_u8.shape) != (F, pitch3)):
+        raise ValueError("frames_fetch: the stores disagree on the frame count or the pitch")
+    dev = img_u8.device
+    by_value = not (isinstance(frame_ids, torch.Tensor) and frame_ids.is_cuda)
+    if by_value:
+        ids = [int(i) for i in (frame_ids.view(-1).tolist() if isinstance(frame_ids, torch.Tensor) else frame_ids)]
+        bad = [i for i in ids if not 0 <= i < F]
+        if bad:
+            raise IndexError(f"frames_fetch: frame ids {bad} outside [0, {F})")
+        N = len(ids)
+    else:
+        ids = _lib.i64c(frame_ids).view(-1)
+        N = ids.numel()
+    shapes = ((N, H, W, 3), (N, H, W, 3) if normal_u8 is not None else None, (N, H, W))
+    if out is None:
+        out = [None if s is None else torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    for t, s in zip(out, shapes):
+        if (t is None) != (s is None) or (t is not None and (t.dtype != torch.float32 or tuple(t.shape) != s or not t.is_contiguous() or t.device != dev)):
+            raise ValueError(f"frames_fetch: out must hold contiguous float32 tensors of shapes {shapes} on {dev}")
+    o_img, o_normal, o_mask = out
+    if not by_value:
+        _lib.launch("sr_frames_fetch", img_u8, img_u8, normal_u8, mask_u8, pitch3, pitch1, F, H, W, None, ids, N, o_img, o_normal, o_mask)
+        return o_img, o_normal, o_mask
+    for s in range(0, max(N, 1), FRAMES_MAX_BATCH):                       # (an empty list still reaches the entry point, which refuses it)
+        part = ids[s:s + FRAMES_MAX_BATCH]
+        packed = _lib.SrFrameIds()
+        packed.id[:len(part)] = part
+        _lib.launch("sr_frames_fetch", img_u8, img_u8, normal_u8, mask_u8, pitch3, pitch1, F, H, W, ctypes.byref(packed), None, len(part),
+                    o_img[s:s + FRAMES_MAX_BATCH], None if o_normal is None else o_normal[s:s + FRAMES_MAX_BATCH], o_mask[s:s + FRAMES_MAX_BATCH])
+    return o_img, o_normal, o_mask

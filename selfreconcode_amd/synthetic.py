@@ -263,11 +263,40 @@ def per_face_atlas(F, resolution=1680, margin=0.5):
     return torch.from_numpy(vt.astype(np.float32)), torch.arange(3 * F, dtype=torch.long).view(F, 3)
 
 
+class CameraTableMixin:
+    """The one camera of a sequence as four tensors in `self.camera_params` (the reference's keys) plus `self.H` / `self.W`: shared by
+    SyntheticSequence and dataset.SceneDataset."""
+
+    def opt_camera_params(self, conf):
+        """dataset/dataset.py:64-74: which camera parameters are optimised (a bool for all, or train.opt_camera of the config)."""
+        names = {'focal_length': 'focal_length', 'princeple_points': 'princeple_points', 'cam2world_coord_quat': 'quat', 'world2cam_coord_trans': 'T'}
+        for key, cname in names.items():
+            self.camera_params[key].requires_grad_(bool(conf) if isinstance(conf, bool) else conf.get_bool(cname))
+
+    def get_camera_parameters(self, N, device=None):
+        """dataset/dataset.py:125-127.  The rotation of a quaternion that is not optimised (config.conf:13) is built once."""
+        q = self.camera_params['cam2world_coord_quat'].view(1, 4)
+        key = (q.data_ptr(), q._version)
+        cache = getattr(self, '_R_cache', None)
+        if not q.requires_grad and cache is not None and cache[0] == key:
+            R = cache[1]
+        else:
+            q = q / q.norm(p=2, dim=1, keepdim=True)
+            w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+            R = torch.stack([w * w + x * x - y * y - z * z, 2 * x * y - 2 * w * z, 2 * w * y + 2 * x * z,
+                             2 * w * z + 2 * x * y, w * w - x * x + y * y - z * z, 2 * y * z - 2 * w * x,
+                             2 * x * z - 2 * w * y, 2 * w * x + 2 * y * z, w * w - x * x - y * y + z * z], dim=1).view(1, 3, 3)
+            if not q.requires_grad:
+                self._R_cache = (key, R)
+        return (self.camera_params['focal_length'].view(1, 2).expand(N, 2), self.camera_params['princeple_points'].view(1, 2).expand(N, 2),
+                R.expand(N, 3, 3), self.camera_params['world2cam_coord_trans'].view(1, 3).expand(N, 3), self.H, self.W)
+
+
 # ------------------------------------------------------------------------------------------------
 # Synthetic sequence + scene builder (SURVEY.md 8(d) cfg2/cfg3): the tensor contract of
 # dataset/dataset.py (poses / trans / per-frame codes as dense learnable tensors, one camera),
 # resident on the GPU instead of being re-uploaded from the host at every call.
-class SyntheticSequence:
+class SyntheticSequence(CameraTableMixin):
     def __init__(self, frame_num=64, H=540, W=540, device="cuda:0", seed=0):
         self.frame_num, self.H, self.W = frame_num, H, W
         self.device = torch.device(device)
@@ -289,12 +318,6 @@ class SyntheticSequence:
         self.video_segmented_index = []
         self._R_cache = None
 
-    def opt_camera_params(self, conf):
-        """dataset/dataset.py:64-74: which camera parameters are optimised (a bool for all, or train.opt_camera of the config)."""
-        names = {'focal_length': 'focal_length', 'princeple_points': 'princeple_points', 'cam2world_coord_quat': 'quat', 'world2cam_coord_trans': 'T'}
-        for key, cname in names.items():
-            self.camera_params[key].requires_grad_(bool(conf) if isinstance(conf, bool) else conf.get_bool(cname))
-
     def learnable_weights(self):
         ws = [c for c in self.conds if c.requires_grad]
         ws += [v for v in self.camera_params.values() if v.requires_grad]
@@ -306,23 +329,6 @@ class SyntheticSequence:
         idxs = idxs.view(-1)
         return (torch.index_select(self.poses, 0, idxs), torch.index_select(self.trans, 0, idxs), torch.index_select(self.conds[0], 0, idxs),
                 torch.index_select(self.conds[1], 0, idxs))
-
-    def get_camera_parameters(self, N, device=None):
-        """dataset/dataset.py:125-127.  The rotation of a quaternion that is not optimised (config.conf:13) is built once."""
-        q = self.camera_params['cam2world_coord_quat'].view(1, 4)
-        key = (q.data_ptr(), q._version)
-        if not q.requires_grad and self._R_cache is not None and self._R_cache[0] == key:
-            R = self._R_cache[1]
-        else:
-            q = q / q.norm(p=2, dim=1, keepdim=True)
-            w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
-            R = torch.stack([w * w + x * x - y * y - z * z, 2 * x * y - 2 * w * z, 2 * w * y + 2 * x * z,
-                             2 * w * z + 2 * x * y, w * w - x * x + y * y - z * z, 2 * y * z - 2 * w * x,
-                             2 * x * z - 2 * w * y, 2 * w * x + 2 * y * z, w * w - x * x - y * y + z * z], dim=1).view(1, 3, 3)
-            if not q.requires_grad:
-                self._R_cache = (key, R)
-        return (self.camera_params['focal_length'].view(1, 2).expand(N, 2), self.camera_params['princeple_points'].view(1, 2).expand(N, 2),
-                R.expand(N, 3, 3), self.camera_params['world2cam_coord_trans'].view(1, 3).expand(N, 3), self.H, self.W)
 
     def get_batchframe_data(self, name, fids, batchsize):
         """Window of `batchsize` frames around each id, clamped to the sequence (dataset.py:128-147)."""

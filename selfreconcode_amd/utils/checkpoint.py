@@ -26,9 +26,9 @@ def load_model(name, optNet, dataset, device, subsdfmodel=None, model_rm_prefix=
     optNet = optNet.to(device)
     dev = dataset.poses.device
     if 'dcond' in saved:
-        dataset.conds[0] = saved['dcond'].to(dev).requires_grad_()
+        dataset.conds[0] = saved['dcond'].detach().to(dev).requires_grad_()          # (detach: a leaf again, like the tables below)
     if 'rcond' in saved:
-        dataset.conds[1] = saved['rcond'].to(dev).requires_grad_()
+        dataset.conds[1] = saved['rcond'].detach().to(dev).requires_grad_()
     for attr in ('poses', 'trans', 'shape'):
         grad = getattr(dataset, attr).requires_grad
         setattr(dataset, attr, saved[attr].detach().to(dev).requires_grad_(grad))
@@ -39,12 +39,14 @@ def load_model(name, optNet, dataset, device, subsdfmodel=None, model_rm_prefix=
 
 def set_hierarchical_config(conf, name, optNet, dataloader, resolutions):
     """Stage switch coarse -> medium -> fine (utils/utils.py:237-255), same signature and return value: a DataLoader over the same
-    dataset / sampler with the stage's batch size (None stays None: the synthetic sequence has no loader), the stage's loss /
-    point-render configuration left PENDING on the network (`next_conf`, `next_train_conf`: OptimNetwork adopts them at its next
+    dataset / sampler with the stage's batch size (a dataset.FrameLoader is re-made through its with_batch_size; None stays None: the
+    synthetic sequence has no loader), the stage's loss / point-render configuration left PENDING on the network (`next_conf`, `next_train_conf`: OptimNetwork adopts them at its next
     scheduled remesh, network.py:464) and a new Seg3dLossless engine at the stage's resolution pyramid, in place at once."""
     from ..MCAcc import Seg3dLossless
     batch_size = conf.get_int('train.' + name + '.point_render.batch_size')
-    if dataloader is not None:
+    if hasattr(dataloader, 'with_batch_size'):                   # dataset.FrameLoader: frames resident on the GPU, nothing to collate
+        dataloader = dataloader.with_batch_size(batch_size)
+    elif dataloader is not None:
         dataloader = torch.utils.data.DataLoader(dataloader.dataset, batch_size, sampler=dataloader.sampler, num_workers=dataloader.num_workers)
     optNet.next_conf = conf.get_config('loss_' + name)
     optNet.next_train_conf = conf.get_config('train.' + name)
