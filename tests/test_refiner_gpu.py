@@ -82,10 +82,9 @@ def test_chain_equals_layerwise_launches_on_a_device_row_count():
 
 
 @pytest.mark.parametrize("P,times", [(5000, 10), (777, 3), (64, 10), (130, 2)])
-def test_device_driven_refiner_equals_the_layerwise_loop(P, times):
+def test_device_driven_refiner_equals_the_layerwise_loop(P, times, N=3):
     from selfreconcode_amd.utils import FindSurfacePs as F
     sdf, comp = _nets()
-    N = 3
     defconds = [fx.det_tensor((N, 128), 3, 0.1).to(DEV), [fx.det_tensor((N, 24, 3), 1, 0.1).to(DEV), fx.det_tensor((N, 3), 2, 0.05).to(DEV)]]
     cam, _, p0, bi, jitter = _rays(P, N)
     with torch.no_grad():
@@ -127,6 +126,11 @@ def test_device_driven_refiner_equals_the_layerwise_loop(P, times):
     assert 0.15 * P < P - live[1] < 0.6 * P                                   # the on-surface quarter is retired by the initial test
     if times >= 10:
         assert live[times + 1] < 0.5 * P and float(ob.float().mean()) > 0.5, (live, float(ob.float().mean()))   # and most of the rest along the way
+
+
+def test_device_driven_refiner_equals_the_layerwise_loop_at_nine_frames():
+    """Beyond 8 frames refine_mid_kernel reads the posed transforms from global memory instead of its LDS copy."""
+    test_device_driven_refiner_equals_the_layerwise_loop(777, 3, N=9)
 
 
 def test_refiner_edge_cases():
