@@ -628,6 +628,32 @@ int sr_frames_fetch(const uint8_t* img_u8, const uint8_t* normal_u8, const uint8
                     int32_t W, const sr_frame_ids* ids_by_value, const int64_t* ids_device, int32_t N, float* out_img, float* out_normal,
                     float* out_mask, void* stream);
 
+/* Device-side training log (csrc/trainlog.hip): the scalars a training loop prints per iteration, gathered into one row of a float32
+ * ring in device memory by one small launch, so that the host reads rows later instead of waiting for each value.
+ *   sr_log_row: one workgroup of one wave.  Lane k < n reads slot k and writes ring[(row % ring_rows) * ld + k]; the columns
+ *     n <= k < ld of that row are written as NaN, so that a value of an earlier lap of the ring never reads as current.  Slot kinds:
+ *     SR_LOG_EMPTY -> NaN; SR_LOG_F32: src[k] is a DEVICE float32 scalar, copied bit for bit; SR_LOG_I64: src[k] is a DEVICE int64
+ *     scalar, converted with (float) (round to nearest even); SR_LOG_IMM: imm[k], a host float.
+ *   `slots_by_value` is a HOST pointer; the structure is copied into the launch (no transfer, no synchronisation).  The POINTERS and
+ *   the immediates are captured when the call is issued; the VALUES behind the pointers are read in stream order, i.e. the row holds
+ *   what earlier work on `stream` left there -- the caller keeps the sources alive until the launch has run.  No atomics, plain loads
+ *   and stores: two calls give identical bits.
+ * SR_EINVAL: n outside [1, SR_LOG_MAX_SLOTS], ld < n, ring_rows < 1, row < 0, a kind that is none of the four, a NULL src of an F32 /
+ * I64 slot, an F32 source that is not 4-byte aligned, an I64 source that is not 8-byte aligned, a NULL or not 4-byte aligned ring, a
+ * NULL slots_by_value. */
+#define SR_LOG_MAX_SLOTS 32
+#define SR_LOG_EMPTY 0
+#define SR_LOG_F32 1
+#define SR_LOG_I64 2
+#define SR_LOG_IMM 3
+struct sr_log_slots_s {
+  const void* src[SR_LOG_MAX_SLOTS];
+  float imm[SR_LOG_MAX_SLOTS];
+  uint8_t kind[SR_LOG_MAX_SLOTS];
+};
+typedef struct sr_log_slots_s sr_log_slots;
+int sr_log_row(const sr_log_slots* slots_by_value, int32_t n, float* ring, int32_t ring_rows, int32_t ld, int64_t row, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,14 @@ class SrFrameIds(ctypes.Structure):
     _fields_ = [("id", ctypes.c_int32 * SR_FRAMES_MAX_BATCH)]
 
 
+SR_LOG_MAX_SLOTS = 32
+SR_LOG_EMPTY, SR_LOG_F32, SR_LOG_I64, SR_LOG_IMM = 0, 1, 2, 3
+
+
+class SrLogSlots(ctypes.Structure):
+    _fields_ = [("src", _vp * SR_LOG_MAX_SLOTS), ("imm", ctypes.c_float * SR_LOG_MAX_SLOTS), ("kind", ctypes.c_uint8 * SR_LOG_MAX_SLOTS)]
+
+
 class SrError(RuntimeError):
     pass
 
@@ -250,6 +258,7 @@ SIGNATURES = {
     "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
     "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,
     "sr_frames_fetch": [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
+    "sr_log_row": [_vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp],
     "sr_pe_embed_bwd": [_vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp],
     "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
 }

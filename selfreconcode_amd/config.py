@@ -90,6 +90,39 @@ def parse_hocon(text):
     return block()
 
 
+def _dump_scalar(v):
+    if isinstance(v, bool):
+        return 'true' if v else 'false'
+    if isinstance(v, (int, float)):
+        return repr(v)
+    if isinstance(v, str):
+        if '"' in v or '\n' in v or _scalar(v) != v:
+            raise ValueError(f"dump_hocon: the string {v!r} would not parse back as itself")
+        return '"' + v + '"'
+    raise TypeError(f"dump_hocon: {type(v).__name__} values are not supported")
+
+
+def dump_hocon(conf, indent=0):
+    """The text of a configuration in the subset parse_hocon reads (what the reference writes with pyhocon's HOCONConverter into
+    save_root/config.conf): parse_hocon(dump_hocon(c)) == c for nested dicts of bools, ints, finite floats, strings and flat lists."""
+    pad, lines = '  ' * indent, []
+    for key, v in conf.items():
+        key = str(key)
+        if not re.fullmatch(r'[^\s{}\[\]="#,./]+', key):
+            raise ValueError(f"dump_hocon: key {key!r}")
+        if isinstance(v, dict):
+            lines += [f'{pad}{key} {{', dump_hocon(v, indent + 1).rstrip('\n'), f'{pad}}}'] if v else [f'{pad}{key} {{', f'{pad}}}']
+        elif isinstance(v, (list, tuple)):
+            items = [_dump_scalar(x) for x in v]
+            if any(isinstance(x, str) for x in v):                    # (one per line: a comma behind a quoted string is a token of its own)
+                lines += [f'{pad}{key} = ['] + [f'{pad}  {x}' for x in items] + [f'{pad}]']
+            else:
+                lines.append(f'{pad}{key} = [' + ', '.join(items) + ']')
+        else:
+            lines.append(f'{pad}{key} = {_dump_scalar(v)}')
+    return '\n'.join(lines) + '\n'
+
+
 def load_config(path):
     with open(path) as fh:
         return parse_hocon(fh.read())

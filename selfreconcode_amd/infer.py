@@ -1,0 +1,82 @@
+"""The inference driver: the reference's infer.py over infer_export.export_frames.
+
+    python -m selfreconcode_amd.infer --gpu-ids 0 --rec-root <capture folder>/result [--frames N] [--nColor] [--C]
+
+Reads rec_root/config.conf, opens the capture folder rec_root/.. in order (shuffle off, nothing learnable), loads rec_root/latest.pth,
+extracts the template with discretizeSDF(ratio, None, 0.) and writes what infer_export lists under rec_root.  `--nV` is accepted;
+videos are not written either way, and the command says so once.  `--nI` cannot be honoured for the same reason (the
+reference refuses --nV --nI together): the images are what this command writes.
+"""
+import argparse
+import os.path as osp
+
+import torch
+
+from .config import load_config
+
+# infer.py:47-53
+RESOLUTIONS = [(14 + 1, 20 + 1, 8 + 1), (28 + 1, 40 + 1, 16 + 1), (56 + 1, 80 + 1, 32 + 1), (112 + 1, 160 + 1, 64 + 1), (224 + 1, 320 + 1, 128 + 1)]
+RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(prog='python -m selfreconcode_amd.infer', description='neu video body infer')
+    parser.add_argument('--gpu-ids', nargs='+', type=int, metavar='IDs', default=[0], help='gpu ids')
+    parser.add_argument('--batch-size', default=1, type=int, metavar='IDs', help='batch size')
+    parser.add_argument('--rec-root', default=None, metavar='M', help='data root')
+    parser.add_argument('--frames', default=-1, type=int, metavar='frames', help='render frame nums')
+    parser.add_argument('--nV', action='store_true', help='not save video')
+    parser.add_argument('--nI', action='store_true', help='not save image')
+    parser.add_argument('--C', action='store_true', help='overlay on gtimg')
+    parser.add_argument('--nColor', action='store_true', help='not render images')
+    return parser
+
+
+def limited(dataloader, batch_size, frames, out=None, no_color=False):
+    """The loader's batches up to the reference's cut (infer.py:133: stop at the first batch with data_index * batch_size > frames,
+    when frames >= 0), announcing each batch's first frame number as the reference prints it."""
+    for data_index, batch in enumerate(dataloader):
+        if frames >= 0 and data_index * batch_size > frames:
+            break
+        if out is not None:
+            out(data_index * batch_size) if no_color else out(data_index * batch_size, end='\t')
+        yield batch
+
+
+def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overlay=False, out=print, resolutions=None):
+    """-> (maskE, TmpVs, Tmpfs, optNet).  `resolutions`: the extraction pyramid instead of infer.py's (small scenes)."""
+    from .dataset import getDatasetAndLoader
+    from .infer_export import export_frames
+    from .model import getOptNet
+    from .utils.checkpoint import load_model
+    device = torch.device(device)
+    config = load_config(osp.join(rec_root, 'config.conf'))
+    condlen = {'deformer': config.get_int('mlp_deformer.condlen'), 'renderer': config.get_int('render_net.condlen')}
+    dataset, dataloader = getDatasetAndLoader(osp.normpath(osp.join(rec_root, osp.pardir)), condlen, batch_size, False,
+                                              config.get_int('train.num_workers'), False, False, False, device=device)
+    optNet, _ = getOptNet(dataset, batch_size, None, None, resolutions or RESOLUTIONS, device, config)
+    out('load model: ' + osp.join(rec_root, 'latest.pth'))
+    optNet, dataset = load_model(osp.join(rec_root, 'latest.pth'), optNet, dataset, device)
+    optNet.dataset = dataset
+    optNet.eval()
+    TmpVs, Tmpfs = optNet.discretizeSDF(RATIO, None, 0.)
+    maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, RATIO, color=color, overlay=overlay)
+    out('done')
+    return maskE, TmpVs, Tmpfs, optNet
+
+
+def main(argv=None, out=print, resolutions=None):
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.rec_root is None:
+        parser.error('--rec-root is required')
+    if args.nI:
+        parser.error('--nI: the images are all this command writes (videos are not written, see --nV)')
+    out('videos (meshs/video.mp4, def1meshs/video.mp4, colors/video.mp4) are not written' + ('' if args.nV else '; pass --nV to say so'))
+    infer(args.rec_root, torch.device('cuda', args.gpu_ids[0]), args.batch_size, args.frames, color=not args.nColor, overlay=args.C, out=out,
+          resolutions=resolutions)
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

@@ -378,3 +378,35 @@ def frames_fetch(img_u8, normal_u8, mask_u8, H, W, frame_ids, out=None):
         _lib.launch("sr_frames_fetch", img_u8, img_u8, normal_u8, mask_u8, pitch3, pitch1, F, H, W, ctypes.byref(packed), None, len(part),
                     o_img[s:s + FRAMES_MAX_BATCH], None if o_normal is None else o_normal[s:s + FRAMES_MAX_BATCH], o_mask[s:s + FRAMES_MAX_BATCH])
     return o_img, o_normal, o_mask
+
+
+# ------------------------------------------------------------------ device-side training log (csrc/trainlog.hip)
+LOG_MAX_SLOTS = _lib.SR_LOG_MAX_SLOTS
+
+
+def log_row(ring, row, values):
+    """One row of the log ring (sr_log_row) on the current stream: ring [ring_rows, ld] contiguous float32 on the GPU, `row` the running
+    row number (it lands in ring[row % ring_rows]), `values` up to LOG_MAX_SLOTS entries, each None (NaN), a Python int / float (rounded
+    to float32 now), or a one-element float32 / int64 DEVICE tensor, whose value is read by the kernel in stream order -- the caller keeps
+    it alive until the launch has run.  Columns behind the last value are written as NaN.  No copy, no synchronisation."""
+    _lib.require_gpu(ring)
+    if ring.dim() != 2 or ring.dtype != torch.float32 or not ring.is_contiguous():
+        raise ValueError(f"log_row: contiguous float32 ring [rows, ld] expected, got {ring.dtype} {tuple(ring.shape)}")
+    if len(values) > LOG_MAX_SLOTS:
+        raise ValueError(f"log_row: {len(values)} values (at most {LOG_MAX_SLOTS})")
+    slots = _lib.SrLogSlots()
+    for k, v in enumerate(values):
+        if v is None:
+            continue                                               # (SR_LOG_EMPTY is 0, what a fresh structure holds)
+        if isinstance(v, torch.Tensor):
+            _lib.require_gpu(v)
+            if v.numel() != 1 or v.dtype not in (torch.float32, torch.int64):
+                raise ValueError(f"log_row: value {k} must be a one-element float32 or int64 tensor, got {v.dtype} {tuple(v.shape)}")
+            if v.device != ring.device:
+                raise RuntimeError(f"selfreconcode_amd: log_row value {k} on {v.device}, ring on {ring.device} (there is deliberately no CPU fallback)")
+            slots.kind[k] = _lib.SR_LOG_F32 if v.dtype == torch.float32 else _lib.SR_LOG_I64
+            slots.src[k] = v.data_ptr()
+        else:
+            slots.kind[k] = _lib.SR_LOG_IMM
+            slots.imm[k] = float(v)
+    _lib.launch("sr_log_row", ring, ctypes.byref(slots), len(values), ring, ring.shape[0], ring.shape[1], int(row))
