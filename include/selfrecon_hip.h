@@ -540,6 +540,50 @@ int64_t sr_texture_fill_workspace_bytes(int32_t R);
 int sr_texture_fill(const float* tex_median, const uint8_t* mask_final, const uint8_t* tex_mask, int32_t R, int32_t dilate, float* texture,
                     void* workspace, void* stream);
 
+/* Template preparation for the texture stage (csrc/mesh_prep.hip): vertex-clustering simplification, box-projection charts and the
+ * contested-texel count of an atlas.  The reference leaves this step to the user; the semantics are stated in DESIGN.md 3.15, unpinned.
+ * Sorting, unique and compaction happen between the calls (mesh_prep_ops.py).  Integer and min / max atomics only.
+ *   sr_meshprep_bounds: box [8] int32 <- the bit patterns of the float32 per-axis minimum [0..3) and maximum [3..6) of verts [V,3] over
+ *     the finite coordinates (-0 counts as +0), and box[6] = 1 when a coordinate is not finite.
+ *   sr_meshprep_cell_keys: key [V] = (k ny + j) nx + i with ijk = floor((v - lo) / cell): float32 subtraction, IEEE float32 division;
+ *     lo [3] on the device.  cell > 0 and nx ny nz < 2^62, else SR_EINVAL.
+ *   sr_meshprep_cell_mean: out [C,3] = mean of verts[order[offsets[c] .. offsets[c + 1])], summed in that order in double.
+ *   sr_meshprep_face_keys: out_faces [F,3] = vertex_map[faces]; (key_hi, key_lo) = (lo Vn + mid, hi) of the sorted corners, (-1, -1)
+ *     for a face with a repeated corner or an index outside [0, V).  Vn <= 2^31.
+ *   sr_meshprep_face_first: with the faces sorted by (key_hi, key_lo), ties in original order (perm [F]: sorted position -> face),
+ *     keep[face] = 1 for the first of every run of equal non-negative keys, else 0.
+ *   sr_chart_classify: cls [F] = 2 axis + (negative ? 1 : 0) of the normal (b - a) x (c - a) in double from the float32 coordinates,
+ *     every product and difference rounded on its own (no fused multiply-add); axis = argmax |n|, lowest axis on a tie, zero normal 0.
+ *   sr_chart_edge_keys: key [3F] of half-edge 3 f + corner = (min V + max) 6 + cls[f]; -1 for an edge from a vertex to itself.
+ *     V <= 2^30.
+ *   sr_chart_hook: parent [F] int32 is a forest of stars.  next <- parent, then for neighbours i - 1, i of the sorted half-edge keys
+ *     (perm [3F]: position -> half-edge) with equal non-negative keys, whose faces have different roots: next[larger root] =
+ *     min(next[larger root], smaller root); changed [1] = 1 when there was one.  n = 3 F.
+ *   sr_chart_jump: next[f] = parent[parent[f]]; changed = 1 when some next[f] != parent[f].
+ *   sr_chart_bbox: per chart (chart [F] in [0, C)) the box of its faces' projected corners: for axis k and positive sign (u, v) =
+ *     (x_{k+1}, x_{k+2}), swapped for a negative sign.  bbox_min [C,2], extent [C,2] = max - min in float32; box [C,4] int32 is scratch.
+ *   sr_chart_uv: vt [3F,2], vt[3 f + corner] = (origin[chart] + padding + 0.5 + (p - bbox_min[chart]) scale) / R in double, rounded
+ *     once; origin [C,2] int64.
+ *   sr_uv_overlap_count: total [1] = the number of texel centres (sr_uv_rasterize's convention) that lie strictly inside two or more
+ *     non-degenerate UV triangles (every barycentric > eps); count [R,R] int32 = triangles per texel. */
+int sr_meshprep_bounds(const float* verts, int64_t V, int32_t* box, void* stream);
+int sr_meshprep_cell_keys(const float* verts, int64_t V, const float* lo, float cell, int64_t nx, int64_t ny, int64_t nz, int64_t* key, void* stream);
+int sr_meshprep_cell_mean(const float* verts, int64_t V, const int64_t* order, const int64_t* offsets, int64_t C, float* out, void* stream);
+int sr_meshprep_face_keys(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t Vn, int64_t* out_faces, int64_t* key_hi,
+                          int64_t* key_lo, void* stream);
+int sr_meshprep_face_first(const int64_t* key_hi, const int64_t* key_lo, const int64_t* perm, int64_t F, uint8_t* keep, void* stream);
+int sr_chart_classify(const float* verts, int64_t V, const int64_t* faces, int64_t F, int32_t* cls, void* stream);
+int sr_chart_edge_keys(const int64_t* faces, int64_t F, int64_t V, const int32_t* cls, int64_t* key, void* stream);
+int sr_chart_hook(const int64_t* sorted_key, const int64_t* perm, int64_t n, const int32_t* parent, int32_t* next, int64_t F, int32_t* changed,
+                  void* stream);
+int sr_chart_jump(const int32_t* parent, int64_t F, int32_t* next, int32_t* changed, void* stream);
+int sr_chart_bbox(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int32_t* cls, const int64_t* chart, int64_t C, int32_t* box,
+                  float* bbox_min, float* extent, void* stream);
+int sr_chart_uv(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int32_t* cls, const int64_t* chart, int64_t C,
+                const float* bbox_min, const int64_t* origin, double scale, int32_t padding, int32_t R, float* vt, void* stream);
+int sr_uv_overlap_count(const float* vt, const int64_t* ft, int64_t Vt, int64_t F, int32_t R, double eps, int32_t* count, int64_t* total,
+                        void* stream);
+
 /* Skinning-weight field of a body mesh (csrc/lbsw.hip): compute_lbswField + smooth_weights of model/Deformer.py:235-284.
  *   sr_lbsw_knn_blend: field [nj,D,H,W] (channel-major, W fastest) over the box [bmin, bmax] (host float[3] each).  Voxel (w, h, d) has
  *     centre ((w + 1/2) / W) (bmax - bmin) + bmin per axis, or (w / (W - 1)) ... with align_corners (every size >= 2 then).  Its value

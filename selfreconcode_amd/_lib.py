@@ -247,6 +247,18 @@ SIGNATURES = {
     "sr_texture_resolve": [_i64, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_texture_fill_workspace_bytes": [ctypes.c_int32],
     "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_meshprep_bounds": [_vp, _i64, _vp, _vp],
+    "sr_meshprep_cell_keys": [_vp, _i64, _vp, ctypes.c_float, _i64, _i64, _i64, _vp, _vp],
+    "sr_meshprep_cell_mean": [_vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "sr_meshprep_face_keys": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "sr_meshprep_face_first": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "sr_chart_classify": [_vp, _i64, _vp, _i64, _vp, _vp],
+    "sr_chart_edge_keys": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "sr_chart_hook": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "sr_chart_jump": [_vp, _i64, _vp, _vp, _vp],
+    "sr_chart_bbox": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
+    "sr_chart_uv": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
+    "sr_uv_overlap_count": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_double, _vp, _vp, _vp],
     "sr_lbsw_knn_blend": [_vp, _vp, _i64] + [ctypes.c_int32] * 5 + [_vp, _vp, ctypes.c_int32, _vp, _vp],
     "sr_lbsw_smooth": [_vp, _vp] + [ctypes.c_int32] * 4 + [_vp],
     "sr_smpl_shape": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _vp],

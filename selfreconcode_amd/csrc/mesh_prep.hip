@@ -1,0 +1,373 @@
+// Template preparation for the texture stage: vertex-clustering simplification and a box-projection chart unwrap of the marching-cubes
+// template, plus the contested-texel count of an atlas (semantics stated there, unpinned -- the reference leaves this
+// step to MeshLab / Blender).  Sorting, unique and compaction are torch's; everything per element is here.
+//
+//  * simplify: sr_meshprep_bounds (box of the vertices by min / max atomics on ordered integers, and a non-finite flag),
+//    sr_meshprep_cell_keys (grid cell of a vertex: float32 subtraction and IEEE float32 division), sr_meshprep_cell_mean (thread per
+//    occupied cell, its members summed in ascending original index in double), sr_meshprep_face_keys (remapped corners, the sorted
+//    triple as a two-part key, -1 for a collapsed face) and sr_meshprep_face_first (first of every run of equal keys after two stable
+//    sorts = the lowest original index).
+//  * unwrap: sr_chart_classify (dominant axis and sign of the float64 normal, every product and difference rounded on its own),
+//    sr_chart_edge_keys (half-edge keys that carry the class, so equal keys = same edge and same class), sr_chart_hook / sr_chart_jump
+//    (connected components by min-label hooking of roots and pointer doubling, both double-buffered: the number of passes is a function
+//    of the input alone), sr_chart_bbox (per-chart box of the projected corners) and sr_chart_uv.
+//  * sr_uv_overlap_count: texel centres strictly inside two or more UV triangles, with sr_uv_rasterize's texel convention.
+//
+// Stream / gather work bound by HBM and by atomics on a few addresses; no float atomics anywhere: sums are sequential per thread, the
+// atomics are integer adds and min / max, so two calls give identical bits.
+#include "sr_common.h"
+#include "uv_device.h"
+
+namespace {
+
+// float <-> int32 with the same order (-0 counts as +0), for atomicMin / atomicMax
+__device__ __forceinline__ int32_t ordered(float x) {
+  const int32_t b = __float_as_int(x + 0.f);
+  return b ^ ((b >> 31) & 0x7fffffff);
+}
+__device__ __forceinline__ float unordered(int32_t o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
+
+__device__ __forceinline__ int32_t wave_min(int32_t v) {
+  for (int m = SR_WAVE / 2; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, SR_WAVE));
+  return v;
+}
+__device__ __forceinline__ int32_t wave_max(int32_t v) {
+  for (int m = SR_WAVE / 2; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, SR_WAVE));
+  return v;
+}
+
+// ---------------------------------------------------------------------------------------------- simplify
+__global__ void bounds_init(int32_t* __restrict__ box) {
+  if (threadIdx.x < 3) box[threadIdx.x] = INT32_MAX;
+  else if (threadIdx.x < 6) box[threadIdx.x] = INT32_MIN;
+  else if (threadIdx.x < 8) box[threadIdx.x] = 0;
+}
+
+// box[0..3) = min, box[3..6) = max (ordered integers), box[6] = a coordinate is not finite
+__global__ __launch_bounds__(256) void bounds_reduce(const float* __restrict__ verts, int64_t V, int32_t* __restrict__ box) {
+  int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {INT32_MIN, INT32_MIN, INT32_MIN}, bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float x = verts[i * 3 + k];
+      if (!isfinite(x)) { bad = 1; continue; }
+      const int32_t o = ordered(x);
+      lo[k] = min(lo[k], o); hi[k] = max(hi[k], o);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { lo[k] = wave_min(lo[k]); hi[k] = wave_max(hi[k]); }
+  bad = wave_max(bad);
+  if ((threadIdx.x & (SR_WAVE - 1)) == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { atomicMin(box + k, lo[k]); atomicMax(box + 3 + k, hi[k]); }
+    if (bad) atomicOr(box + 6, 1);
+  }
+}
+
+__global__ void bounds_finish(int32_t* __restrict__ box) {
+  if (threadIdx.x < 6) box[threadIdx.x] = __float_as_int(unordered(box[threadIdx.x]));
+}
+
+__global__ __launch_bounds__(256) void cell_keys(const float* __restrict__ verts, int64_t V, const float* __restrict__ lo, float cell, int64_t nx,
+                                                  int64_t ny, int64_t nz, int64_t* __restrict__ key) {
+  const float lx = lo[0], ly = lo[1], lz = lo[2];
+  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V; v += (int64_t)gridDim.x * blockDim.x) {
+    int64_t i = (int64_t)floorf(__fdiv_rn(__fsub_rn(verts[v * 3], lx), cell));
+    int64_t j = (int64_t)floorf(__fdiv_rn(__fsub_rn(verts[v * 3 + 1], ly), cell));
+    int64_t k = (int64_t)floorf(__fdiv_rn(__fsub_rn(verts[v * 3 + 2], lz), cell));
+    i = i < 0 ? 0 : (i >= nx ? nx - 1 : i); j = j < 0 ? 0 : (j >= ny ? ny - 1 : j); k = k < 0 ? 0 : (k >= nz ? nz - 1 : k);   // (no-ops for the box's own vertices)
+    key[v] = (k * ny + j) * nx + i;
+  }
+}
+
+// thread per occupied cell: members order[offsets[c] .. offsets[c + 1]) are in ascending original index (a stable sort made them)
+__global__ __launch_bounds__(256) void cell_mean(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ order,
+                                                  const int64_t* __restrict__ offsets, int64_t C, float* __restrict__ out) {
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < C; c += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t s = offsets[c], e = offsets[c + 1];
+    double x = 0., y = 0., z = 0.;
+    int64_t n = 0;
+    for (int64_t m = s; m < e; ++m) {
+      const int64_t v = order[m];
+      if (v < 0 || v >= V) continue;
+      x += (double)verts[v * 3]; y += (double)verts[v * 3 + 1]; z += (double)verts[v * 3 + 2]; ++n;
+    }
+    const double d = n > 0 ? (double)n : 1.;
+    out[c * 3] = (float)(x / d); out[c * 3 + 1] = (float)(y / d); out[c * 3 + 2] = (float)(z / d);
+  }
+}
+
+__global__ __launch_bounds__(256) void face_keys(const int64_t* __restrict__ faces, int64_t F, const int64_t* __restrict__ vmap, int64_t V, int64_t Vn,
+                                                  int64_t* __restrict__ out_faces, int64_t* __restrict__ key_hi, int64_t* __restrict__ key_lo) {
+  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
+    int64_t x = -1, y = -1, z = -1;
+    if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) { x = vmap[a]; y = vmap[b]; z = vmap[c]; }
+    out_faces[f * 3] = x; out_faces[f * 3 + 1] = y; out_faces[f * 3 + 2] = z;
+    const bool dead = x < 0 || y < 0 || z < 0 || x >= Vn || y >= Vn || z >= Vn || x == y || y == z || x == z;
+    const int64_t lo = min(x, min(y, z)), hi = max(x, max(y, z)), mid = x + y + z - lo - hi;
+    key_hi[f] = dead ? -1 : lo * Vn + mid;
+    key_lo[f] = dead ? -1 : hi;
+  }
+}
+
+// position i of the faces sorted by (key_hi, key_lo), ties in original order: the first of a run of equal keys survives
+__global__ __launch_bounds__(256) void face_first(const int64_t* __restrict__ key_hi, const int64_t* __restrict__ key_lo, const int64_t* __restrict__ perm,
+                                                   int64_t F, uint8_t* __restrict__ keep) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < F; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = perm[i];
+    if (p < 0 || p >= F) continue;
+    keep[p] = key_hi[i] >= 0 && (i == 0 || key_hi[i] != key_hi[i - 1] || key_lo[i] != key_lo[i - 1]) ? 1 : 0;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- unwrap
+// class = 2 axis + (negative ? 1 : 0) of the unnormalised normal (b - a) x (c - a) in double, no contraction: the restatement rounds
+// every product and every difference on its own and must agree on ties
+__device__ int32_t face_class(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc) {
+#pragma clang fp contract(off)                      // (plain operators under this pragma: __dmul_rn / __dsub_rn are inline functions that contract)
+  const double ux = (double)pb[0] - (double)pa[0], uy = (double)pb[1] - (double)pa[1], uz = (double)pb[2] - (double)pa[2];
+  const double vx = (double)pc[0] - (double)pa[0], vy = (double)pc[1] - (double)pa[1], vz = (double)pc[2] - (double)pa[2];
+  const double yz = uy * vz, zy = uz * vy, zx = uz * vx, xz = ux * vz, xy = ux * vy, yx = uy * vx;
+  const double n[3] = {yz - zy, zx - xz, xy - yx};
+  int k = 0;
+  if (fabs(n[1]) > fabs(n[k])) k = 1;
+  if (fabs(n[2]) > fabs(n[k])) k = 2;                 // (strict: the lowest axis wins a tie, and a zero normal stays +x)
+  return 2 * k + (n[k] < 0. ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void chart_classify(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                                       int32_t* __restrict__ cls) {
+  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
+    const bool ok = a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
+    cls[f] = ok ? face_class(verts + a * 3, verts + b * 3, verts + c * 3) : 0;
+  }
+}
+
+// half-edge h = 3 f + corner: (min V + max) 6 + class; -1 for an edge between a vertex and itself
+__global__ __launch_bounds__(256) void chart_edge_keys(const int64_t* __restrict__ faces, int64_t F, int64_t V, const int32_t* __restrict__ cls,
+                                                        int64_t* __restrict__ key) {
+  for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < 3 * F; h += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = h / 3, c = h - 3 * f;
+    const int64_t a = faces[h], b = faces[f * 3 + (c + 1) % 3];
+    const bool ok = a >= 0 && b >= 0 && a < V && b < V && a != b;
+    key[h] = ok ? (min(a, b) * V + max(a, b)) * 6 + cls[f] : -1;
+  }
+}
+
+// neighbouring half-edges of the sorted list with one key join their faces: the larger of the two roots takes the smaller as parent
+// (atomicMin: the least of all offers).  P is a forest of stars here, so P[face] is its root; Q starts as a copy of P.
+__global__ __launch_bounds__(256) void chart_hook(const int64_t* __restrict__ skey, const int64_t* __restrict__ perm, int64_t n, const int32_t* __restrict__ P,
+                                                   int32_t* __restrict__ Q, int64_t F, int32_t* __restrict__ changed) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (skey[i] < 0 || skey[i] != skey[i - 1]) continue;
+    const int64_t a = perm[i - 1] / 3, b = perm[i] / 3;
+    if (a < 0 || b < 0 || a >= F || b >= F) continue;
+    const int32_t ra = P[a], rb = P[b];
+    if (ra == rb || ra < 0 || rb < 0 || ra >= F || rb >= F) continue;
+    atomicMin(Q + max(ra, rb), min(ra, rb));
+    *changed = 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void chart_jump(const int32_t* __restrict__ P, int64_t F, int32_t* __restrict__ Q, int32_t* __restrict__ changed) {
+  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t p = P[f];
+    const int32_t g = p >= 0 && p < F ? P[p] : p;
+    Q[f] = g;
+    if (g != p) *changed = 1;
+  }
+}
+
+// (u, v) of a point under class `c`: the two axes after the dominant one, swapped for a negative sign
+__device__ __forceinline__ void project(const float* __restrict__ p, int32_t c, float& u, float& v) {
+  const int k = c >> 1;
+  const float s = p[(k + 1) % 3], t = p[(k + 2) % 3];
+  u = (c & 1) ? t : s; v = (c & 1) ? s : t;
+}
+
+__global__ __launch_bounds__(256) void box_init(int32_t* __restrict__ box, int64_t C) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 4 * C; i += (int64_t)gridDim.x * blockDim.x)
+    box[i] = (i & 3) < 2 ? INT32_MAX : INT32_MIN;
+}
+
+__global__ __launch_bounds__(256) void chart_box(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                                  const int32_t* __restrict__ cls, const int64_t* __restrict__ chart, int64_t C, int32_t* __restrict__ box) {
+  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = chart[f];
+    if (c < 0 || c >= C) continue;
+    int32_t u0 = INT32_MAX, v0 = INT32_MAX, u1 = INT32_MIN, v1 = INT32_MIN;
+    bool ok = true;
+    for (int k = 0; k < 3; ++k) {
+      const int64_t a = faces[f * 3 + k];
+      if (a < 0 || a >= V) { ok = false; break; }
+      float u, v;
+      project(verts + a * 3, cls[f], u, v);
+      const int32_t ou = ordered(u), ov = ordered(v);
+      u0 = min(u0, ou); u1 = max(u1, ou); v0 = min(v0, ov); v1 = max(v1, ov);
+    }
+    if (!ok) continue;
+    atomicMin(box + c * 4, u0); atomicMin(box + c * 4 + 1, v0); atomicMax(box + c * 4 + 2, u1); atomicMax(box + c * 4 + 3, v1);
+  }
+}
+
+__global__ __launch_bounds__(256) void box_finish(const int32_t* __restrict__ box, int64_t C, float* __restrict__ bbox_min, float* __restrict__ extent) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < 2 * C; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t c = i >> 1, k = i & 1;
+    const int32_t lo = box[c * 4 + k], hi = box[c * 4 + 2 + k];
+    const bool any = lo <= hi;                          // (a chart always has a face; an untouched box gives 0, 0)
+    bbox_min[i] = any ? unordered(lo) : 0.f;
+    extent[i] = any ? __fsub_rn(unordered(hi), unordered(lo)) : 0.f;
+  }
+}
+
+// vt[3 f + corner] = (origin + padding + 0.5 + (p - bbox_min) scale) / R in double, rounded once
+__global__ __launch_bounds__(256) void chart_uv(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                                 const int32_t* __restrict__ cls, const int64_t* __restrict__ chart, int64_t C,
+                                                 const float* __restrict__ bbox_min, const int64_t* __restrict__ origin, double scale, int32_t padding,
+                                                 int32_t R, float* __restrict__ vt) {
+  for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < 3 * F; h += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = h / 3, a = faces[h], c = chart[f];
+    float u = 0.f, v = 0.f;
+    if (a >= 0 && a < V && c >= 0 && c < C) {
+      float pu, pv;
+      project(verts + a * 3, cls[f], pu, pv);
+      u = (float)(((double)origin[c * 2] + (double)padding + 0.5 + ((double)pu - (double)bbox_min[c * 2]) * scale) / (double)R);
+      v = (float)(((double)origin[c * 2 + 1] + (double)padding + 0.5 + ((double)pv - (double)bbox_min[c * 2 + 1]) * scale) / (double)R);
+    }
+    vt[h * 2] = u; vt[h * 2 + 1] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- contested texels
+// wavefront per face over the face's texel box (uv_claim's walk in texture.hip); a texel centre counts for the face when every
+// barycentric exceeds eps
+__global__ __launch_bounds__(256) void overlap_mark(const float* __restrict__ vt, const int64_t* __restrict__ ft, int64_t Vt, int64_t F, int32_t R,
+                                                     double eps, int32_t* __restrict__ count) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / SR_WAVE, nwaves = (int64_t)gridDim.x * blockDim.x / SR_WAVE;
+  for (int64_t f = wave; f < F; f += nwaves) {
+    const UvTri t = uv_tri(vt, ft, Vt, f);
+    if (!t.ok) continue;
+    const double umin = fmin(t.ax, fmin(t.bx, t.cx)), umax = fmax(t.ax, fmax(t.bx, t.cx));
+    const double vmin = fmin(t.ay, fmin(t.by, t.cy)), vmax = fmax(t.ay, fmax(t.by, t.cy));
+    if (!(umax >= 0. && umin <= 1. && vmax >= 0. && vmin <= 1.)) continue;
+    const int c0 = clampi((int)floor(fmax(umin, 0.) * R - 0.5) - 1, 0, R - 1), c1 = clampi((int)ceil(fmin(umax, 1.) * R - 0.5) + 1, 0, R - 1);
+    const int r0 = clampi((int)floor((1. - fmin(vmax, 1.)) * R - 0.5) - 1, 0, R - 1), r1 = clampi((int)ceil((1. - fmax(vmin, 0.)) * R - 0.5) + 1, 0, R - 1);
+    const int bw = c1 - c0 + 1;
+    const int64_t n = (int64_t)bw * (r1 - r0 + 1);
+    for (int64_t i = lane; i < n; i += SR_WAVE) {
+      const int r = r0 + (int)(i / bw), c = c0 + (int)(i % bw);
+      double e0, e1, e2;
+      uv_edges(t, (c + 0.5) / R, 1. - (r + 0.5) / R, e0, e1, e2);
+      if (e0 / t.area2 > eps && e1 / t.area2 > eps && e2 / t.area2 > eps) atomicAdd(count + (int64_t)r * R + c, 1);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void overlap_total(const int32_t* __restrict__ count, int64_t texels, unsigned long long* __restrict__ total) {
+  int32_t n = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < texels; i += (int64_t)gridDim.x * blockDim.x) n += count[i] >= 2 ? 1 : 0;
+  for (int m = SR_WAVE / 2; m > 0; m >>= 1) n += __shfl_xor(n, m, SR_WAVE);
+  if ((threadIdx.x & (SR_WAVE - 1)) == 0 && n) atomicAdd(total, (unsigned long long)n);
+}
+}  // namespace
+
+extern "C" int sr_meshprep_bounds(const float* verts, int64_t V, int32_t* box, void* stream) {
+  if (!verts || !box || V <= 0) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(bounds_init, dim3(1), dim3(64), 0, st, box);
+  hipLaunchKernelGGL(bounds_reduce, dim3(sr_stream_grid(V, 256)), dim3(256), 0, st, verts, V, box);
+  hipLaunchKernelGGL(bounds_finish, dim3(1), dim3(64), 0, st, box);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_cell_keys(const float* verts, int64_t V, const float* lo, float cell, int64_t nx, int64_t ny, int64_t nz, int64_t* key,
+                                     void* stream) {
+  if (!verts || !lo || !key || V <= 0 || !(cell > 0.f) || nx <= 0 || ny <= 0 || nz <= 0) return SR_EINVAL;
+  const __int128 lim = (__int128)1 << 62;                                                 // the keys need nx ny nz < 2^62
+  if ((__int128)nx * ny >= lim || (__int128)nx * ny * nz >= lim) return SR_EINVAL;
+  hipLaunchKernelGGL(cell_keys, dim3(sr_stream_grid(V, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, lo, cell, nx, ny, nz, key);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_cell_mean(const float* verts, int64_t V, const int64_t* order, const int64_t* offsets, int64_t C, float* out, void* stream) {
+  if (!verts || !order || !offsets || !out || V <= 0 || C <= 0) return SR_EINVAL;
+  hipLaunchKernelGGL(cell_mean, dim3(sr_stream_grid(C, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, order, offsets, C, out);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_face_keys(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t Vn, int64_t* out_faces,
+                                     int64_t* key_hi, int64_t* key_lo, void* stream) {
+  if (!faces || !vertex_map || !out_faces || !key_hi || !key_lo || F <= 0 || V <= 0 || Vn <= 0 || Vn > ((int64_t)1 << 31)) return SR_EINVAL;
+  hipLaunchKernelGGL(face_keys, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, vertex_map, V, Vn, out_faces, key_hi, key_lo);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_face_first(const int64_t* key_hi, const int64_t* key_lo, const int64_t* perm, int64_t F, uint8_t* keep, void* stream) {
+  if (!key_hi || !key_lo || !perm || !keep || F <= 0) return SR_EINVAL;
+  hipLaunchKernelGGL(face_first, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, key_hi, key_lo, perm, F, keep);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_classify(const float* verts, int64_t V, const int64_t* faces, int64_t F, int32_t* cls, void* stream) {
+  if (!verts || !faces || !cls || V <= 0 || F <= 0) return SR_EINVAL;
+  hipLaunchKernelGGL(chart_classify, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, cls);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_edge_keys(const int64_t* faces, int64_t F, int64_t V, const int32_t* cls, int64_t* key, void* stream) {
+  if (!faces || !cls || !key || F <= 0 || V <= 0 || V > ((int64_t)1 << 30)) return SR_EINVAL;       // (V V 6 < 2^63)
+  hipLaunchKernelGGL(chart_edge_keys, dim3(sr_stream_grid(3 * F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, V, cls, key);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_hook(const int64_t* sorted_key, const int64_t* perm, int64_t n, const int32_t* parent, int32_t* next, int64_t F, int32_t* changed,
+                             void* stream) {
+  if (!sorted_key || !perm || !parent || !next || !changed || F <= 0 || F >= INT32_MAX || n != 3 * F) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SR_ELAUNCH;
+  if (hipMemcpyAsync(next, parent, (size_t)F * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SR_ELAUNCH;
+  hipLaunchKernelGGL(chart_hook, dim3(sr_stream_grid(n, 256)), dim3(256), 0, st, sorted_key, perm, n, parent, next, F, changed);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_jump(const int32_t* parent, int64_t F, int32_t* next, int32_t* changed, void* stream) {
+  if (!parent || !next || !changed || F <= 0 || F >= INT32_MAX) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SR_ELAUNCH;
+  hipLaunchKernelGGL(chart_jump, dim3(sr_stream_grid(F, 256)), dim3(256), 0, st, parent, F, next, changed);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_bbox(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int32_t* cls, const int64_t* chart, int64_t C,
+                             int32_t* box, float* bbox_min, float* extent, void* stream) {
+  if (!verts || !faces || !cls || !chart || !box || !bbox_min || !extent || V <= 0 || F <= 0 || C <= 0) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(box_init, dim3(sr_stream_grid(4 * C, 256)), dim3(256), 0, st, box, C);
+  hipLaunchKernelGGL(chart_box, dim3(sr_stream_grid(F, 256)), dim3(256), 0, st, verts, V, faces, F, cls, chart, C, box);
+  hipLaunchKernelGGL(box_finish, dim3(sr_stream_grid(2 * C, 256)), dim3(256), 0, st, (const int32_t*)box, C, bbox_min, extent);
+  return sr_launch_status();
+}
+
+extern "C" int sr_chart_uv(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int32_t* cls, const int64_t* chart, int64_t C,
+                           const float* bbox_min, const int64_t* origin, double scale, int32_t padding, int32_t R, float* vt, void* stream) {
+  if (!verts || !faces || !cls || !chart || !bbox_min || !origin || !vt || V <= 0 || F <= 0 || C <= 0 || !(scale >= 0.) || padding < 0 || R <= 0)
+    return SR_EINVAL;
+  hipLaunchKernelGGL(chart_uv, dim3(sr_stream_grid(3 * F, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, cls, chart, C, bbox_min, origin,
+                     scale, padding, R, vt);
+  return sr_launch_status();
+}
+
+extern "C" int sr_uv_overlap_count(const float* vt, const int64_t* ft, int64_t Vt, int64_t F, int32_t R, double eps, int32_t* count, int64_t* total,
+                                   void* stream) {
+  if (!vt || !ft || !count || !total || Vt <= 0 || F <= 0 || R <= 0 || R > 32768 || !(eps >= 0.)) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t texels = (int64_t)R * R;
+  if (hipMemsetAsync(count, 0, (size_t)texels * 4, st) != hipSuccess || hipMemsetAsync(total, 0, 8, st) != hipSuccess) return SR_ELAUNCH;
+  hipLaunchKernelGGL(overlap_mark, dim3(sr_stream_grid(F * SR_WAVE, 256)), dim3(256), 0, st, vt, ft, Vt, F, R, eps, count);
+  hipLaunchKernelGGL(overlap_total, dim3(sr_stream_grid(texels, 256)), dim3(256), 0, st, (const int32_t*)count, texels, (unsigned long long*)total);
+  return sr_launch_status();
+}

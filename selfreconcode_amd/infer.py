@@ -43,10 +43,10 @@ def limited(dataloader, batch_size, frames, out=None, no_color=False):
         yield batch
 
 
-def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overlay=False, out=print, resolutions=None):
-    """-> (maskE, TmpVs, Tmpfs, optNet).  `resolutions`: the extraction pyramid instead of infer.py's (small scenes)."""
+def load_network(rec_root, device="cuda:0", batch_size=1, out=print, resolutions=None):
+    """-> (optNet, dataset, dataloader): the capture folder rec_root/.. opened in order (shuffle off, nothing learnable), the network
+    of rec_root/config.conf with rec_root/latest.pth loaded, in eval mode.  What `infer` and the texture command start from."""
     from .dataset import getDatasetAndLoader
-    from .infer_export import export_frames
     from .model import getOptNet
     from .utils.checkpoint import load_model
     device = torch.device(device)
@@ -59,6 +59,13 @@ def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overla
     optNet, dataset = load_model(osp.join(rec_root, 'latest.pth'), optNet, dataset, device)
     optNet.dataset = dataset
     optNet.eval()
+    return optNet, dataset, dataloader
+
+
+def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overlay=False, out=print, resolutions=None):
+    """-> (maskE, TmpVs, Tmpfs, optNet).  `resolutions`: the extraction pyramid instead of infer.py's (small scenes)."""
+    from .infer_export import export_frames
+    optNet, dataset, dataloader = load_network(rec_root, device, batch_size, out, resolutions)
     TmpVs, Tmpfs = optNet.discretizeSDF(RATIO, None, 0.)
     maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, RATIO, color=color, overlay=overlay)
     out('done')

@@ -1,0 +1,205 @@
+"""Template preparation for the texture stage, on the GPU: what the reference's README leaves to the user ("you need to simplify and
+parameterize the template mesh tmp.ply yourself, then save the result mesh as .../template/uvmap.obj").
+
+    simplify_mesh / simplify_to   vertex clustering on a uniform grid (87k-196k marching-cubes vertices -> a face budget)
+    unwrap_charts                 box projection: charts = connected faces of one dominant normal axis and sign, shelf-packed
+    prepare_template              extract -> simplify -> unwrap -> template/uvmap.obj
+
+The reference has no code for this step and pytorch3d / xatlas are not dependencies, so the semantics are this package's own (DESIGN.md
+3.15: stated, unpinned) and are held to a float64 numpy restatement by the tests.  Known limits, also in DESIGN: the stretch of box
+projection (UV area / surface area of a face is |n_axis| / |n|, between 1 / sqrt(3) and 1), seams at every change of the dominant axis,
+vertices placed at cell means rather than quadric optima, and no repair of a chart that overlaps itself in projection -- that is
+counted (`overlap_texels`), not fixed.
+"""
+import os
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import mesh_prep_ops as mp
+
+SimplifiedMesh = namedtuple("SimplifiedMesh", "verts faces vertex_map cell")
+ChartAtlas = namedtuple("ChartAtlas", "vt ft chart labels bbox_min extent origin size scale rounds overlap_texels")
+PreparedTemplate = namedtuple("PreparedTemplate", "mesh atlas obj_path source_faces")
+
+BISECT_STEPS = 16
+PACK_STEPS = 24
+
+
+def _grid(verts, cell):
+    lo, hi = mp.mesh_bounds(verts)
+    return lo, mp.grid_shape(lo.cpu().numpy(), hi.cpu().numpy(), cell)
+
+
+def _clustered(verts, faces, lo, n, cell):
+    """(vertex_map, number of cells, remapped faces, keep) of one grid."""
+    cells, vmap = mp.cluster(mp.cell_keys(verts, lo, cell, n))
+    remapped, keep = mp.surviving_faces(faces, vmap, cells.shape[0])
+    return vmap, cells.shape[0], remapped, keep
+
+
+def simplify_mesh(verts, faces, cell):
+    """Vertex clustering of verts [V,3] float32 / faces [F,3] int64 (GPU tensors) on a uniform grid of side `cell`.
+
+    Faces with a negative index are dropped first.  With lo the per-axis float32 minimum, a vertex lies in cell ijk = floor((v - lo) /
+    cell) (float32 subtraction and IEEE division), key (k n_y + j) n_x + i, n = max ijk + 1.  The new vertices are the occupied cells
+    in ascending key, each at the mean of its members (summed in ascending original index, in double, rounded once); vertex_map [V]
+    gives old -> new.  Faces are remapped; a face with a repeated corner is dropped, and of the faces with the same unordered vertex set
+    the one with the lowest original index stays.  Survivors keep their corner order and their relative order; new vertices no face
+    references are kept.  ValueError for cell <= 0, non-finite vertices or a grid of 2^62 cells or more.  Two calls give identical
+    bits.  -> SimplifiedMesh(verts [Vn,3], faces [Fn,3], vertex_map [V], cell)."""
+    _lib.require_gpu(verts, faces)
+    verts = _lib.f32c(verts)
+    faces = mp.clean_faces(faces)
+    cell = float(np.float32(cell))
+    if not cell > 0:
+        raise ValueError(f"cell must be positive, got {cell}")
+    lo, n = _grid(verts, cell)
+    vmap, C, remapped, keep = _clustered(verts, faces, lo, n, cell)
+    return SimplifiedMesh(mp.cell_means(verts, vmap, C), remapped[keep].contiguous(), vmap, cell)
+
+
+def simplify_to(verts, faces, target_faces, probes=None):
+    """simplify_mesh at the smallest probed cell that leaves at most `target_faces` faces.  A mesh that is within the budget already
+    comes back cleaned (no negative rows) with the identity map and cell 0.  Otherwise the cell is bisected geometrically in [d / 1024,
+    d / 2], d the longest side of the box, in 16 steps of keys -> count of surviving faces (no positions); ValueError if even d / 2
+    leaves more.  `probes`, a list, receives every (cell, face count) tried, in order."""
+    _lib.require_gpu(verts, faces)
+    verts = _lib.f32c(verts)
+    faces = mp.clean_faces(faces)
+    target = int(target_faces)
+    if faces.shape[0] <= target:
+        mp.mesh_bounds(verts)                                            # (the refusal of non-finite vertices holds here too)
+        return SimplifiedMesh(verts, faces, torch.arange(verts.shape[0], dtype=torch.int64, device=verts.device), 0.)
+    lo, hi = mp.mesh_bounds(verts)
+    lo_h, hi_h = lo.cpu().numpy(), hi.cpu().numpy()
+    d = float((hi_h - lo_h).max())
+    if not (np.isfinite(d) and d > 0):
+        raise ValueError(f"simplify_to: the box of the vertices has longest side {d}")
+
+    def count(cell):
+        cell = float(np.float32(cell))
+        _, _, _, keep = _clustered(verts, faces, lo, mp.grid_shape(lo_h, hi_h, cell), cell)
+        k = int(keep.sum())
+        if probes is not None:
+            probes.append((cell, k))
+        return cell, k
+    a, b = d / 1024., d / 2.
+    best, k = count(b)
+    if k > target:
+        raise ValueError(f"simplify_to: {k} faces are left at the coarsest cell {best}, more than the target {target}")
+    for _ in range(BISECT_STEPS):
+        cell, k = count((a * b) ** 0.5)
+        if k <= target:
+            b = best = cell
+        else:
+            a = cell
+    return simplify_mesh(verts, faces, best)
+
+
+def _shelves(size, R):
+    """Shelf packing of the rectangles size [C,2] (w, h) into R x R: order (height desc, width desc, label asc), left to right, a new
+    shelf when x + w > R, a shelf as high as its first rectangle.  -> origin [C,2] int64, or None when it does not fit."""
+    w, h = size[:, 0], size[:, 1]
+    if w.max() > R:
+        return None
+    order = np.lexsort((np.arange(len(w)), -w, -h))
+    origin = np.zeros((len(w), 2), np.int64)
+    x = y = shelf = 0
+    for i, wi, hi in zip(order.tolist(), w[order].tolist(), h[order].tolist()):
+        if x + wi > R:
+            x, y = 0, y + shelf
+            shelf = 0
+        if shelf == 0:
+            shelf = hi
+            if y + shelf > R:
+                return None
+        origin[i] = (x, y)
+        x += wi
+    return origin
+
+
+def pack_charts(extent, R, padding):
+    """Host-side packing of charts with projected extents extent [C,2] (numpy) into an R x R atlas.  A chart's rectangle is size =
+    ceil(extent scale) + 2 padding + 1 texels, which leaves `padding` texels and half a texel around its triangles, so different
+    charts stay at least 2 padding texels apart.  `scale` (texels per unit length) is the largest value for which the shelf packing
+    (see _shelves) fits, found by 24 bisection steps on [0, R / max extent]; all-zero extents give scale 0.  ValueError if the charts
+    do not fit even at scale 0.  Deterministic.  -> (scale float, origin [C,2] int64, size [C,2] int64)."""
+    extent = np.asarray(extent, np.float64).reshape(-1, 2)
+    R, padding = int(R), int(padding)
+    if len(extent) == 0:
+        return 0., np.zeros((0, 2), np.int64), np.zeros((0, 2), np.int64)
+    if not np.isfinite(extent).all() or (extent < 0).any() or padding < 0 or R <= 0:
+        raise ValueError("pack_charts: finite non-negative extents, padding >= 0 and R > 0 expected")
+
+    def sizes(s):
+        return np.ceil(extent * s).astype(np.int64) + 2 * padding + 1
+    lo, origin = 0., _shelves(sizes(0.), R)
+    if origin is None:
+        raise ValueError(f"pack_charts: {len(extent)} charts do not fit a {R} x {R} atlas at padding {padding}, even as points")
+    emax = float(extent.max())
+    if emax > 0:
+        hi = R / emax
+        for _ in range(PACK_STEPS):
+            mid = 0.5 * (lo + hi)
+            o = _shelves(sizes(mid), R)
+            if o is None:
+                hi = mid
+            else:
+                lo, origin = mid, o
+    return lo, origin, sizes(lo)
+
+
+def unwrap_charts(verts, faces, resolution=1680, padding=2):
+    """Box-projection UV atlas of verts [V,3] float32 / faces [F,3] int64 (GPU tensors, every index valid).
+
+    A face's class is the axis of the largest |component| of its float64 normal (lowest axis on a tie, +x for a zero normal) and that
+    component's sign; charts are the connected components of faces of one class that share an edge (label: lowest face index).  A chart
+    is projected along its axis -- (u, v) = (x_{k+1}, x_{k+2}), swapped for a negative sign, so UV areas are positive --, all charts are
+    scaled by one factor and shelf-packed (pack_charts; one device -> host copy of the boxes), and vt[3 f + c] = (origin + padding + 0.5
+    + (p - bbox_min) scale) / R.  Faces do not share UV vertices: ft = arange(3 F).  A chart that overlaps itself in projection (a spiral
+    ramp) is not split; `overlap_texels` (uv_overlap_count) reports the texels it costs.
+    -> ChartAtlas(vt [3F,2] f32, ft [F,3] i64, chart [F] i64 (index into labels), labels [C] i64, bbox_min [C,2] f32, extent [C,2] f32,
+    origin [C,2] i64, size [C,2] i64, scale, rounds, overlap_texels).  Two calls give identical bits."""
+    _lib.require_gpu(verts, faces)
+    verts = _lib.f32c(verts)
+    if verts.dim() != 2 or verts.shape[1] != 3 or verts.shape[0] == 0:
+        raise ValueError(f"verts [V,3] expected, got {tuple(verts.shape)}")
+    cls = mp.face_classes(verts, faces)                                  # (checks the indices)
+    faces = _lib.i64c(faces)
+    F, dev = faces.shape[0], verts.device
+    if F == 0:
+        raise ValueError("unwrap_charts: no faces")
+    R, padding = int(resolution), int(padding)
+    label, rounds = mp.chart_components(faces, verts.shape[0], cls)
+    labels, chart = torch.unique(label.long(), sorted=True, return_inverse=True)
+    chart = chart.contiguous()
+    C = labels.shape[0]
+    bbox_min, extent = mp.chart_boxes(verts, faces, cls, chart, C)
+    scale, origin, size = pack_charts(extent.cpu().numpy(), R, padding)
+    origin_d = torch.from_numpy(origin).to(dev)
+    vt = mp.chart_uv(verts, faces, cls, chart, bbox_min, origin_d, scale, padding, R)
+    ft = torch.arange(3 * F, dtype=torch.int64, device=dev).view(F, 3)
+    return ChartAtlas(vt, ft, chart, labels, bbox_min, extent, origin_d, torch.from_numpy(size).to(dev), float(scale), rounds,
+                      mp.uv_overlap_count(vt, ft, R))
+
+
+def prepare_template(net, out_root, ratio=None, target_faces=20000, resolution=1680, padding=2, TmpVs=None, Tmpfs=None):
+    """Extracts the template of `net` with discretizeSDF(ratio, None, 0.) as infer does (all ratios 1 unless given; or takes TmpVs /
+    Tmpfs), simplifies it to `target_faces`, unwraps it and writes out_root/template/uvmap.obj, the file export_texture reads.
+    -> PreparedTemplate(mesh SimplifiedMesh, atlas ChartAtlas, obj_path, source_faces: the faces of the extracted template).
+
+    20000 faces is a default, not a measured optimum: at 1680^2 texels with about half of the atlas covered it leaves some 70 texels
+    per face."""
+    from .texture import FULL_RATIO, write_obj_uv
+    if TmpVs is None or Tmpfs is None:
+        TmpVs, Tmpfs = net.discretizeSDF(ratio or FULL_RATIO, None, 0.)
+    mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces)
+    atlas = unwrap_charts(mesh.verts, mesh.faces, resolution, padding)
+    folder = os.path.join(out_root, "template")
+    os.makedirs(folder, exist_ok=True)
+    obj = os.path.join(folder, "uvmap.obj")
+    write_obj_uv(obj, mesh.verts.cpu().numpy(), mesh.faces.cpu().numpy(), atlas.vt.cpu().numpy(), atlas.ft.cpu().numpy())
+    return PreparedTemplate(mesh, atlas, obj, int((Tmpfs >= 0).all(1).sum()))

@@ -1,0 +1,184 @@
+"""Operators of the template preparation (csrc/mesh_prep.hip): GPU tensors only, no autograd.  `mesh_prep.py` is the public interface.
+Sorting, unique and compaction are torch's; everything per element is a HIP kernel.  Two calls give identical bits."""
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _faces
+
+MAX_ROUNDS = 4096          # passes of the component search before it is declared stuck (a 40 000-face strip needs about 20)
+
+
+def _verts2(verts):
+    if verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError(f"verts [V,3] expected, got {tuple(verts.shape)}")
+    if verts.shape[0] == 0:
+        raise ValueError("verts [V,3] expected, got no vertices")
+    return _lib.f32c(verts)
+
+
+def _indexed(faces, V, what):
+    """faces [F,3] int64 with every index in [0, V) (ValueError otherwise: the kernels would skip such a face silently)."""
+    faces = _faces(faces)
+    if faces.shape[0] and (int(faces.min()) < 0 or int(faces.max()) >= V):
+        raise ValueError(f"{what}: face indices outside [0, {V})")
+    return faces
+
+
+def clean_faces(faces):
+    """The rows of faces [F,3] without a negative index (marching cubes pads its list with -1 rows), in order."""
+    _lib.require_gpu(faces)
+    faces = _faces(faces)
+    return faces[(faces >= 0).all(1)].contiguous()
+
+
+def mesh_bounds(verts):
+    """(lo [3], hi [3]) float32 on the device: the per-axis extremes of verts [V,3] (sr_meshprep_bounds).  ValueError for a
+    non-finite coordinate.  One device -> host copy (the flag)."""
+    _lib.require_gpu(verts)
+    verts = _verts2(verts)
+    box = torch.empty((8,), dtype=torch.int32, device=verts.device)
+    _lib.launch("sr_meshprep_bounds", verts, verts, verts.shape[0], box)
+    if int(box[6]):
+        raise ValueError("non-finite vertex coordinates")
+    b = box[:6].view(torch.float32)
+    return b[:3], b[3:]
+
+
+def grid_shape(lo, hi, cell):
+    """(n_x, n_y, n_z) = floor((hi - lo) / cell) + 1 in float32 arithmetic (what the kernel evaluates for the extreme vertices), as
+    Python ints.  ValueError for cell <= 0 or a grid of 2^62 cells or more."""
+    cell = np.float32(cell)
+    if not cell > 0 or not np.isfinite(cell):
+        raise ValueError(f"cell must be a positive float32, got {cell}")
+    with np.errstate(over="ignore", invalid="ignore"):
+        q = np.floor((np.asarray(hi, np.float32) - np.asarray(lo, np.float32)) / cell)
+    if not np.isfinite(q).all():
+        raise ValueError(f"cell {cell}: the grid has 2^62 cells or more")
+    n = [int(x) + 1 for x in q.tolist()]
+    if n[0] * n[1] * n[2] >= 1 << 62:
+        raise ValueError(f"cell {cell}: the grid {n[0]} x {n[1]} x {n[2]} has 2^62 cells or more")
+    return tuple(n)
+
+
+def cell_keys(verts, lo, cell, n):
+    """key [V] int64 = (k n_y + j) n_x + i of every vertex's grid cell (sr_meshprep_cell_keys); lo [3] on the device."""
+    _lib.require_gpu(verts, lo)
+    verts = _verts2(verts)
+    key = torch.empty((verts.shape[0],), dtype=torch.int64, device=verts.device)
+    _lib.launch("sr_meshprep_cell_keys", verts, verts, verts.shape[0], _lib.f32c(lo), float(np.float32(cell)), n[0], n[1], n[2], key)
+    return key
+
+
+def cluster(key):
+    """(cells [C] ascending, vertex_map [V]) of the keys: torch.unique."""
+    cells, vmap = torch.unique(key, sorted=True, return_inverse=True)
+    return cells, vmap.contiguous()
+
+
+def cell_means(verts, vertex_map, C):
+    """[C,3] float32: the mean of every cell's members, summed in ascending original index in double (sr_meshprep_cell_mean)."""
+    _lib.require_gpu(verts, vertex_map)
+    verts = _verts2(verts)
+    vmap = _lib.i64c(vertex_map)
+    order = torch.sort(vmap, stable=True)[1].contiguous()
+    offsets = torch.zeros((C + 1,), dtype=torch.int64, device=verts.device)
+    offsets[1:] = torch.cumsum(torch.bincount(vmap, minlength=C), 0)
+    out = torch.empty((C, 3), dtype=torch.float32, device=verts.device)
+    _lib.launch("sr_meshprep_cell_mean", verts, verts, verts.shape[0], order, offsets, C, out)
+    return out
+
+
+def surviving_faces(faces, vertex_map, Vn):
+    """(remapped [F,3], keep [F] bool): vertex_map[faces], and which faces survive -- no repeated corner, and the lowest index among
+    the faces with the same unordered vertex set (sr_meshprep_face_keys, two stable sorts, sr_meshprep_face_first)."""
+    _lib.require_gpu(faces, vertex_map)
+    faces = _faces(faces); vmap = _lib.i64c(vertex_map)
+    F, dev = faces.shape[0], faces.device
+    out = torch.empty((F, 3), dtype=torch.int64, device=dev)
+    if F == 0:
+        return out, torch.zeros((0,), dtype=torch.bool, device=dev)
+    key_hi = torch.empty((F,), dtype=torch.int64, device=dev); key_lo = torch.empty_like(key_hi)
+    _lib.launch("sr_meshprep_face_keys", faces, faces, F, vmap, vmap.shape[0], int(Vn), out, key_hi, key_lo)
+    lo_sorted, p1 = torch.sort(key_lo, stable=True)
+    hi_sorted, p2 = torch.sort(key_hi[p1], stable=True)
+    keep = torch.empty((F,), dtype=torch.uint8, device=dev)
+    _lib.launch("sr_meshprep_face_first", faces, hi_sorted.contiguous(), lo_sorted[p2].contiguous(), p1[p2].contiguous(), F, keep)
+    return out, keep.bool()
+
+
+def face_classes(verts, faces):
+    """cls [F] int32 = 2 axis + (negative ? 1 : 0) of every face's float64 normal (sr_chart_classify)."""
+    _lib.require_gpu(verts, faces)
+    verts = _verts2(verts); faces = _indexed(faces, verts.shape[0], "face_classes")
+    cls = torch.empty((faces.shape[0],), dtype=torch.int32, device=verts.device)
+    if faces.shape[0]:
+        _lib.launch("sr_chart_classify", verts, verts, verts.shape[0], faces, faces.shape[0], cls)
+    return cls
+
+
+def chart_components(faces, V, cls):
+    """(label [F] int32, rounds): label = the lowest face index of the connected component of faces of equal class that share an edge
+    (all faces on a non-manifold edge are connected).  Min-label hooking of roots, then pointer doubling until every tree is a star,
+    repeated until no edge joins two trees; `rounds` counts every pass over the faces or edges, and each pass costs one flag read."""
+    _lib.require_gpu(faces, cls)
+    faces = _faces(faces)
+    F, dev = faces.shape[0], faces.device
+    key = torch.empty((3 * F,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_chart_edge_keys", faces, faces, F, int(V), cls, key)
+    skey, perm = torch.sort(key)
+    P = torch.arange(F, dtype=torch.int32, device=dev); Q = torch.empty_like(P)
+    changed = torch.zeros((1,), dtype=torch.int32, device=dev)
+    rounds = 0
+    while True:
+        _lib.launch("sr_chart_hook", faces, skey, perm, 3 * F, P, Q, F, changed)
+        rounds += 1
+        if not int(changed):
+            return P, rounds
+        P, Q = Q, P
+        while True:
+            _lib.launch("sr_chart_jump", faces, P, F, Q, changed)
+            rounds += 1
+            P, Q = Q, P
+            if not int(changed):
+                break
+            if rounds > MAX_ROUNDS:
+                raise RuntimeError(f"chart_components: no fixed point after {rounds} passes")
+
+
+def chart_boxes(verts, faces, cls, chart, C):
+    """(bbox_min [C,2], extent [C,2]) float32 of the charts' projected corners (sr_chart_bbox)."""
+    _lib.require_gpu(verts, faces, cls, chart)
+    verts = _verts2(verts); faces = _faces(faces)
+    dev = verts.device
+    box = torch.empty((C, 4), dtype=torch.int32, device=dev)
+    bbox_min = torch.empty((C, 2), dtype=torch.float32, device=dev); extent = torch.empty_like(bbox_min)
+    _lib.launch("sr_chart_bbox", verts, verts, verts.shape[0], faces, faces.shape[0], cls, _lib.i64c(chart), C, box, bbox_min, extent)
+    return bbox_min, extent
+
+
+def chart_uv(verts, faces, cls, chart, bbox_min, origin, scale, padding, resolution):
+    """vt [3F,2] float32 (sr_chart_uv): every corner's place in its chart's rectangle of the atlas."""
+    _lib.require_gpu(verts, faces, cls, chart, bbox_min, origin)
+    verts = _verts2(verts); faces = _faces(faces)
+    vt = torch.empty((3 * faces.shape[0], 2), dtype=torch.float32, device=verts.device)
+    _lib.launch("sr_chart_uv", verts, verts, verts.shape[0], faces, faces.shape[0], cls, _lib.i64c(chart), bbox_min.shape[0], _lib.f32c(bbox_min),
+                _lib.i64c(origin), float(scale), int(padding), int(resolution), vt)
+    return vt
+
+
+def uv_overlap_count(vt, ft, resolution, eps=1e-6):
+    """The number of texel centres (uv_texel_map's convention: u = (c + 0.5) / R, v = 1 - (r + 0.5) / R) that lie strictly inside two
+    or more UV triangles, i.e. every barycentric > eps (sr_uv_overlap_count: an int32 count image and integer atomics).  0 for an atlas
+    whose triangles do not overlap; a patch that folds over itself in projection, as a spiral ramp does, gives a positive count."""
+    _lib.require_gpu(vt, ft)
+    if vt.dim() != 2 or vt.shape[1] != 2:
+        raise ValueError(f"vt [Vt,2] expected, got {tuple(vt.shape)}")
+    vt = _lib.f32c(vt); ft = _faces(ft)
+    R = int(resolution)
+    if ft.shape[0] == 0 or vt.shape[0] == 0:
+        return 0
+    count = torch.empty((max(R, 0), max(R, 0)), dtype=torch.int32, device=vt.device)
+    total = torch.empty((1,), dtype=torch.int64, device=vt.device)
+    _lib.launch("sr_uv_overlap_count", vt, vt, ft, vt.shape[0], ft.shape[0], R, float(eps), count, total)
+    return int(total)

@@ -1,6 +1,8 @@
 """Texture baking: the third stage of the reference pipeline (train, infer, texture) -- texture_mesh_prepare.py +
 texture_mesh_extract.py -- for a UV-mapped template, on the GPU.
 
+    python -m selfreconcode_amd.texture --gpu-ids 0 --rec-root <capture folder>/result [--num 120] [--faces 20000] [--resolution 1680] [--padding 2]
+
 The reference's scripts hand the unwrap and the per-view partial textures to opendr and VideoAvatar's Isomapper and the final fill to
 cv2; none of them is part of the reference repository.  What the script computes with them is restated here (restated,
 unpinned):
@@ -18,8 +20,13 @@ unpinned):
 
 Files written by `export_texture`, as texture_mesh_extract.py names them: tex_mask.png, mask_final.png, tex_median.png, texture.png
 (uint8(x 255)), view_id.npy and tex_predata.npz (vt, ft, tmpvs, fs, defVs, fids; the opendr camera entries are not written).
-UV unwrapping of the marching-cubes template is left to the user, as in the reference (template/uvmap.obj).
+
+The reference leaves simplifying and unwrapping the marching-cubes template to the user, who saves the result as template/uvmap.obj.
+The command honours such a file; without one it makes it (mesh_prep.prepare_template: vertex clustering to `--faces` faces and a
+box-projection chart atlas), so a trained folder gives template/texture.png with no hand-made file.  Everything it
+writes goes under rec_root/template/.
 """
+import argparse
 import os
 from collections import namedtuple
 
@@ -169,3 +176,58 @@ def export_texture(net, obj_path, views, out_root, ratio=None, resolution=1680, 
     np.save(os.path.join(out_root, "view_id.npy"), baked.view_id)
     np.savez(os.path.join(out_root, "tex_predata.npz"), vt=vt, ft=ft, tmpvs=v, fs=f, defVs=baked.def_verts, fids=baked.fids)
     return baked
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(prog='python -m selfreconcode_amd.texture', description='neu video body texture')
+    parser.add_argument('--gpu-ids', nargs='+', type=int, metavar='IDs', default=[0], help='gpu ids')
+    parser.add_argument('--num', default=120, type=int, metavar='IDs', help='Number of used frames')
+    parser.add_argument('--rec-root', default=None, metavar='M', help='data root')
+    parser.add_argument('--faces', default=20000, type=int, metavar='F', help='face budget of the template when template/uvmap.obj has to be made')
+    parser.add_argument('--resolution', default=1680, type=int, metavar='R', help='texture size')
+    parser.add_argument('--padding', default=2, type=int, metavar='P', help='texels kept free around every chart')
+    return parser
+
+
+def dataset_views(dataset, fids):
+    """The views bake_texture takes, one frame at a time from dataset.batch: the image from B, G, R in [-1, 1] to R, G, B in [0, 1]."""
+    for f in fids:
+        b = dataset.batch([int(f)])
+        yield int(f), (b['img'][0].flip(-1) + 1.) * 0.5, b['mask'][0] > 0.5
+
+
+def main(argv=None, out=print, resolutions=None):
+    """The texture stage on a result folder: template/uvmap.obj (used if it is there, as in the reference; made by
+    mesh_prep.prepare_template otherwise), then export_texture over the frames texture_frames(frame_num, --num).  `resolutions`: the
+    extraction pyramid instead of infer.py's (small scenes)."""
+    from .infer import load_network
+    from .mesh_prep import prepare_template
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.rec_root is None:
+        parser.error('--rec-root is required')
+    device = torch.device('cuda', args.gpu_ids[0])
+    net, dataset, _ = load_network(args.rec_root, device, 1, out, resolutions)
+    folder = os.path.join(args.rec_root, 'template')
+    obj = os.path.join(folder, 'uvmap.obj')
+    if os.path.isfile(obj):
+        out('reusing ' + obj)
+    else:
+        prep = prepare_template(net, args.rec_root, target_faces=args.faces, resolution=args.resolution, padding=args.padding)
+        mesh, atlas = prep.mesh, prep.atlas
+        out('template: %d vertices / %d faces -> %d vertices / %d faces' % (mesh.vertex_map.shape[0], prep.source_faces, mesh.verts.shape[0],
+                                                                           mesh.faces.shape[0]))
+        out('atlas: %d charts, scale %.4f texels per unit, overlap_texels %d' % (atlas.labels.shape[0], atlas.scale, atlas.overlap_texels))
+        if atlas.overlap_texels > 0:
+            out('warning: %d texels are claimed by more than one face (a chart overlaps itself in projection); they take the colour of the '
+                'lowest face' % atlas.overlap_texels)
+        out('wrote ' + obj)
+    fids = texture_frames(dataset.frame_num, args.num)
+    baked = export_texture(net, obj, dataset_views(dataset, fids), folder, resolution=args.resolution, device=device)
+    out('texture: %d of %d atlas texels in mask_final; wrote %s' % (int(baked.mask_final.sum()), int(baked.tex_mask.sum()),
+                                                                  os.path.join(folder, 'texture.png')))
+    return 0
+
+
+if __name__ == '__main__':
+    raise SystemExit(main())

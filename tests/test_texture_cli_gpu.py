@@ -1,0 +1,68 @@
+"""`python -m selfreconcode_amd.texture` on the folder a training run left (tests/_train_scene.py): with no template/uvmap.obj it makes
+one (simplify -> unwrap), bakes and writes export_texture's files under rec_root/template/; a second call reuses the OBJ and writes the
+same content; nothing else in the result folder or the capture folder is created or changed (the other driver tests read them)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _train_scene as ts
+from _png import read_png
+
+pytestmark = pytest.mark.gpu
+WRITTEN = ["mask_final.png", "tex_mask.png", "tex_median.png", "tex_predata.npz", "texture.png", "uvmap.obj", "view_id.npy"]
+ARGS = ['--gpu-ids', '0', '--num', '3', '--faces', '400', '--resolution', '128']
+
+
+def _snapshot(root, skip=None):
+    """{relative path: bytes} under root, without the subtree `skip`; an .npz as its arrays (the zip container stamps the time)."""
+    out = {}
+    for dp, dns, fns in os.walk(root):
+        if skip is not None and os.path.abspath(dp) == os.path.abspath(skip):
+            dns[:] = []
+            continue
+        for fn in fns:
+            path = os.path.join(dp, fn)
+            if fn.endswith(".npz"):
+                with np.load(path) as z:
+                    out[os.path.relpath(path, root)] = {k: (z[k].dtype.str, z[k].shape, z[k].tobytes()) for k in z.files}
+            else:
+                with open(path, "rb") as fh:
+                    out[os.path.relpath(path, root)] = fh.read()
+    return out
+
+
+def test_texture_command_makes_reuses_and_stays_in_its_folder(tmp_path_factory):
+    from selfreconcode_amd import texture
+    from selfreconcode_amd.texture import read_obj_uv
+    capture, first = ts.folder(tmp_path_factory)
+    rec_root = first.save_root
+    folder = os.path.join(rec_root, 'template')
+    assert not os.path.exists(os.path.join(folder, 'uvmap.obj'))
+    before = [_snapshot(capture, skip=folder), _snapshot(rec_root, skip=folder)]
+    said = []
+    assert texture.main(ARGS + ['--rec-root', rec_root], out=lambda *a, **k: said.append(' '.join(str(x) for x in a)), resolutions=ts.PYRAMID) == 0
+    assert sorted(os.listdir(folder)) == WRITTEN
+    lines = [s for s in said if 'charts' in s and 'overlap_texels' in s]
+    assert len(lines) == 1
+    m = re.search(r'(\d+) charts, scale ([0-9.]+) texels per unit, overlap_texels (\d+)', lines[0])
+    assert m and int(m.group(1)) >= 6 and float(m.group(2)) > 0
+    assert (int(m.group(3)) > 0) == any(s.startswith('warning') for s in said)
+    m = [re.fullmatch(r'template: (\d+) vertices / (\d+) faces -> (\d+) vertices / (\d+) faces', s) for s in said]
+    m = [x for x in m if x]
+    assert len(m) == 1 and int(m[0].group(4)) <= min(400, int(m[0].group(2))) and int(m[0].group(3)) <= int(m[0].group(1))
+    assert not any('reusing' in s for s in said)
+    v, f, vt, ft = read_obj_uv(os.path.join(folder, 'uvmap.obj'))
+    assert len(v) == int(m[0].group(3)) and len(f) == int(m[0].group(4)) and len(vt) == 3 * len(f) and 0. <= vt.min() and vt.max() <= 1.
+    assert read_png(os.path.join(folder, 'texture.png')).shape == (128, 128, 3)
+    assert read_png(os.path.join(folder, 'tex_mask.png')).reshape(128, 128).any()
+    pre = np.load(os.path.join(folder, 'tex_predata.npz'))
+    assert pre['fids'].tolist() == texture.texture_frames(ts.FRAMES, 3).tolist() == [0, 2, 4] and pre['defVs'].shape == (3, len(v), 3)
+    made = _snapshot(folder)
+    # again: the OBJ is there now, as a hand-made one would be
+    said2 = []
+    assert texture.main(ARGS + ['--rec-root', rec_root], out=lambda *a, **k: said2.append(' '.join(str(x) for x in a)), resolutions=ts.PYRAMID) == 0
+    assert sum('reusing' in s and 'uvmap.obj' in s for s in said2) == 1 and not any('charts' in s for s in said2)
+    assert _snapshot(folder) == made
+    assert [_snapshot(capture, skip=folder), _snapshot(rec_root, skip=folder)] == before

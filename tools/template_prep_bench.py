@@ -1,0 +1,71 @@
+"""Times the template preparation of the texture stage at the fine stage's template size -- cube_sphere(170): 173 402 vertices, 346 800
+faces -> simplify_to(20000) -> unwrap_charts(1680) -- on the GPU, stage by stage.  Wall time around synchronised calls after seconds of
+warm-up (these functions read flags and boxes back, so they are host-paced: HIP events around them would say the same).
+
+    python tools/template_prep_bench.py [--out profiles/template_prepare.md] [--seconds 2.0]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from selfreconcode_amd import mesh_prep  # noqa: E402
+from selfreconcode_amd.synthetic import cube_sphere  # noqa: E402
+
+N, TARGET, R = 170, 20000, 1680
+
+
+def timed(fn, seconds, min_runs=3):
+    """ms per call: warm up for `seconds` of wall time, then time as many synchronised calls."""
+    t0, n = time.time(), 0
+    while time.time() - t0 < seconds or n < 1:
+        fn(); torch.cuda.synchronize(); n += 1
+    runs = max(min_runs, n)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(runs):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / runs, runs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out"); ap.add_argument("--seconds", type=float, default=2.0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("template_prep_bench: needs the GPU (a CPU run says nothing about it)")
+    dev = "cuda:0"
+    v, f = (t.to(dev) for t in cube_sphere(N))
+    probes = []
+    mesh = mesh_prep.simplify_to(v, f, TARGET, probes=probes)
+    atlas = mesh_prep.unwrap_charts(mesh.verts, mesh.faces, R)
+    res = {"vertices": v.shape[0], "faces": f.shape[0], "target_faces": TARGET, "resolution": R, "cell": mesh.cell, "probes": len(probes),
+           "out_vertices": mesh.verts.shape[0], "out_faces": mesh.faces.shape[0], "charts": atlas.labels.shape[0], "scale": atlas.scale,
+           "rounds": atlas.rounds, "overlap_texels": atlas.overlap_texels}
+    res["simplify_mesh_ms"], res["simplify_mesh_runs"] = timed(lambda: mesh_prep.simplify_mesh(v, f, mesh.cell), args.seconds)
+    res["simplify_to_ms"], res["simplify_to_runs"] = timed(lambda: mesh_prep.simplify_to(v, f, TARGET), args.seconds)
+    res["unwrap_ms"], res["unwrap_runs"] = timed(lambda: mesh_prep.unwrap_charts(mesh.verts, mesh.faces, R), args.seconds)
+    res["unwrap_full_size_ms"], _ = timed(lambda: mesh_prep.unwrap_charts(v, f, R), args.seconds)       # the unsimplified template: the kernels at size
+    ext = atlas.extent.cpu().numpy()
+    res["pack_host_ms"], _ = timed(lambda: mesh_prep.pack_charts(ext, R, 2), min(args.seconds, 0.5))
+    res["device"] = torch.cuda.get_device_name(0)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as fh:
+            fh.write(f"| stage (cube_sphere({N}): {res['vertices']} vertices, {res['faces']} faces) | time |\n|---|---|\n")
+            fh.write(f"| simplify_mesh at the chosen cell {res['cell']:.5f} -> {res['out_vertices']} vertices, {res['out_faces']} faces | {res['simplify_mesh_ms']:.2f} ms |\n")
+            fh.write(f"| simplify_to({TARGET}): {res['probes']} probes + the mesh | {res['simplify_to_ms']:.2f} ms |\n")
+            fh.write(f"| unwrap_charts({R}) of the result: {res['charts']} charts, {res['rounds']} passes of the component search | {res['unwrap_ms']:.2f} ms |\n")
+            fh.write(f"| of which pack_charts on the host | {res['pack_host_ms']:.2f} ms |\n")
+            fh.write(f"| unwrap_charts({R}) of the unsimplified template | {res['unwrap_full_size_ms']:.2f} ms |\n\n")
+            fh.write(json.dumps(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()
