@@ -12,11 +12,14 @@
 #include <type_traits>
 
 #include "lbs_device.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "rot_device.h"
 
 namespace {
 using srlbs::NJ; using srlbs::Axis; using srlbs::make_axis;
+
+__device__ __forceinline__ int frame_of(const sr_lbs_args& g, int64_t idx) {
+  return g.batch_inds ? (int)g.batch_inds[idx] : (int)(idx / g.points_per_frame);
+}
 
 template <bool WITH_JAC>
 __global__ __launch_bounds__(256) void lbs_fwd_kernel(sr_lbs_args g) {
@@ -31,7 +34,7 @@ __global__ __launch_bounds__(256) void lbs_fwd_kernel(sr_lbs_args g) {
   for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < g.P; idx += (int64_t)gridDim.x * blockDim.x) {
     const float px = g.p[idx * 3], py = g.p[idx * 3 + 1], pz = g.p[idx * 3 + 2];
     const float qx = g.tp ? g.tp[idx * 3] : px, qy = g.tp ? g.tp[idx * 3 + 1] : py, qz = g.tp ? g.tp[idx * 3 + 2] : pz;
-    const int frame = g.batch_inds ? (int)g.batch_inds[idx] : (int)(idx / g.points_per_frame);
+    const int frame = frame_of(g, idx);
     const float* Af = stage ? sA + frame * NJ * 12 : g.A + (int64_t)frame * NJ * 12;
     const float* tf = stage ? sT + frame * 3 : g.trans + frame * 3;
     float y[3], J[9];
@@ -80,6 +83,13 @@ struct FramePass {
   }
 };
 
+// The point of this lane, one per lane from `base` on.  Lanes past the end run along on the last point with a zero cotangent
+// (`valid` false): the wave-wide reductions of the frame sums need all 64 lanes.
+__device__ __forceinline__ int64_t tail_lane_point(int64_t base, int64_t P, bool& valid) {
+  valid = base + threadIdx.x < P;
+  return valid ? base + threadIdx.x : P - 1;
+}
+
 // 16 outputs per workgroup, 16 lanes per output: lane l sums the partial rows l, l + 16, ... in double, then the 16 sums are folded
 // in a fixed order (a fixed function of nblocks alone: bit-reproducible).  One thread per output (the first version) was 512
 // dependent loads in a row: 65 us for 3.5 MB.
@@ -117,15 +127,15 @@ __global__ __launch_bounds__(256) void lbs_bwd_kernel(sr_lbs_args g, const float
   const bool lane0 = (threadIdx.x & 63) == 0;
   const int64_t sH = (int64_t)g.W * NJ, sD = (int64_t)g.H * g.W * NJ;
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < g.P; base += (int64_t)gridDim.x * blockDim.x) {
-    const bool valid = base + threadIdx.x < g.P;                  // lanes past the end run along on the last point with a zero cotangent:
-    const int64_t idx = valid ? base + threadIdx.x : g.P - 1;     // the wave-wide reductions below need all 64 lanes
+    bool valid;
+    const int64_t idx = tail_lane_point(base, g.P, valid);
     {
       const float px = g.p[idx * 3], py = g.p[idx * 3 + 1], pz = g.p[idx * 3 + 2];
       const float bx = valid ? ybar[idx * 3] : 0.f, by = valid ? ybar[idx * 3 + 1] : 0.f, bz = valid ? ybar[idx * 3 + 2] : 0.f;
       const Axis ax = make_axis(px, g.bmin[0], g.bmax[0], g.W);
       const Axis ay = make_axis(py, g.bmin[1], g.bmax[1], g.H);
       const Axis az = make_axis(pz, g.bmin[2], g.bmax[2], g.D);
-      const int frame = g.batch_inds ? (int)g.batch_inds[idx] : (int)(idx / g.points_per_frame);
+      const int frame = frame_of(g, idx);
       const float* Af = g.A + (int64_t)frame * NJ * 12;
       float w[NJ], s[NJ];                           // weights and s_j = ybar . (A_j [p;1])
 #pragma unroll
@@ -143,11 +153,11 @@ __global__ __launch_bounds__(256) void lbs_bwd_kernel(sr_lbs_args g, const float
         if (x < 0 || x >= g.W || y < 0 || y >= g.H || z < 0 || z >= g.D) continue;
         const float cx = dx ? ax.w1 : ax.w0, cy = dy ? ay.w1 : ay.w0, cz = dz ? az.w1 : az.w0;
         const float wk = cx * cy * cz;
-        const f32x4* src = reinterpret_cast<const f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ);
+        const sr_f32x4* src = reinterpret_cast<const sr_f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ);
         float dot = 0.f;
 #pragma unroll
         for (int v = 0; v < NJ / 4; ++v) {
-          const f32x4 c4 = src[v];
+          const sr_f32x4 c4 = src[v];
 #pragma unroll
           for (int e = 0; e < 4; ++e) { w[4 * v + e] += c4[e] * wk; dot += c4[e] * s[4 * v + e]; }
         }
@@ -220,8 +230,8 @@ __global__ __launch_bounds__(256) void lbs_jac_bwd_kernel(sr_lbs_args g, const f
   const bool lane0 = (threadIdx.x & 63) == 0;
   const int64_t sH = (int64_t)g.W * NJ, sD = (int64_t)g.H * g.W * NJ;
   for (int64_t base = (int64_t)blockIdx.x * blockDim.x; base < g.P; base += (int64_t)gridDim.x * blockDim.x) {
-    const bool valid = base + threadIdx.x < g.P;                  // (see lbs_bwd_kernel)
-    const int64_t idx = valid ? base + threadIdx.x : g.P - 1;
+    bool valid;
+    const int64_t idx = tail_lane_point(base, g.P, valid);
     {
       const float q[3] = {g.p[idx * 3], g.p[idx * 3 + 1], g.p[idx * 3 + 2]};
       float yb[3] = {0.f, 0.f, 0.f}, Jb[9];
@@ -231,7 +241,7 @@ __global__ __launch_bounds__(256) void lbs_jac_bwd_kernel(sr_lbs_args g, const f
       const Axis ax = make_axis(q[0], g.bmin[0], g.bmax[0], g.W);
       const Axis ay = make_axis(q[1], g.bmin[1], g.bmax[1], g.H);
       const Axis az = make_axis(q[2], g.bmin[2], g.bmax[2], g.D);
-      const int frame = g.batch_inds ? (int)g.batch_inds[idx] : (int)(idx / g.points_per_frame);
+      const int frame = frame_of(g, idx);
       const float* Af = g.A + (int64_t)frame * NJ * 12;
       // The joints are processed in two halves of 12 (every sum over j is additive): half the coefficient registers, and each half
       // reads only its own 48 bytes of a corner's 96-byte run.
@@ -253,10 +263,10 @@ __global__ __launch_bounds__(256) void lbs_jac_bwd_kernel(sr_lbs_args g, const f
           if (x < 0 || x >= g.W || y < 0 || y >= g.H || z < 0 || z >= g.D) continue;
           const float cx = dx ? ax.w1 : ax.w0, cy = dy ? ay.w1 : ay.w0, cz = dz ? az.w1 : az.w0;
           const float wk = cx * cy * cz, gx = (dx ? 1.f : -1.f) * cy * cz, gy = (dy ? 1.f : -1.f) * cx * cz, gz = (dz ? 1.f : -1.f) * cx * cy;
-          const f32x4* src = reinterpret_cast<const f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ + j0);
+          const sr_f32x4* src = reinterpret_cast<const sr_f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ + j0);
 #pragma unroll
           for (int v = 0; v < HJ / 4; ++v) {
-            const f32x4 c4 = src[v];
+            const sr_f32x4 c4 = src[v];
 #pragma unroll
             for (int e = 0; e < 4; ++e) { c0[4 * v + e] += c4[e] * wk; c1[4 * v + e] += c4[e] * gx; c2[4 * v + e] += c4[e] * gy; c3[4 * v + e] += c4[e] * gz; }
           }
@@ -313,11 +323,11 @@ __global__ __launch_bounds__(256) void lbs_jac_bwd_kernel(sr_lbs_args g, const f
             if (x < 0 || x >= g.W || y < 0 || y >= g.H || z < 0 || z >= g.D) continue;
             const float cx = dx ? ax.w1 : ax.w0, cy = dy ? ay.w1 : ay.w0, cz = dz ? az.w1 : az.w0;
             const float sx = dx ? 1.f : -1.f, sy = dy ? 1.f : -1.f, sz = dz ? 1.f : -1.f;
-            const f32x4* src = reinterpret_cast<const f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ + j0);
+            const sr_f32x4* src = reinterpret_cast<const sr_f32x4*>(g.vol + z * sD + y * sH + (int64_t)x * NJ + j0);
             float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
 #pragma unroll
             for (int v = 0; v < HJ / 4; ++v) {
-              const f32x4 c4 = src[v];
+              const sr_f32x4 c4 = src[v];
 #pragma unroll
               for (int e = 0; e < 4; ++e) { d0 += c4[e] * c0[4 * v + e]; d1 += c4[e] * c1[4 * v + e]; d2 += c4[e] * c2[4 * v + e]; d3 += c4[e] * c3[4 * v + e]; }
             }
@@ -378,24 +388,31 @@ static int lbs_bwd_launch(K kernel, const sr_lbs_args* a, float* Abar, float* tr
   return sr_launch_status();
 }
 
+// What all three entry points ask of their arguments, before and after their `P == 0` exit
+static bool lbs_shape_ok(const sr_lbs_args* a) { return a && a->P >= 0 && a->nframes > 0 && a->D > 0 && a->H > 0 && a->W > 0; }
+static bool lbs_points_ok(const sr_lbs_args* a) {
+  return a->p && a->A && a->vol && !((uintptr_t)a->vol & 15) && (a->batch_inds || a->points_per_frame > 0);
+}
+
+// no points: the sums are zero
+static int lbs_bwd_no_points(const sr_lbs_args* a, float* Abar, float* transbar, void* stream) {
+  if (Abar && hipMemsetAsync(Abar, 0, sizeof(float) * a->nframes * NJ * 12, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
+  if (transbar && hipMemsetAsync(transbar, 0, sizeof(float) * a->nframes * 3, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
+  return SR_OK;
+}
+
 extern "C" int sr_lbs_jac_bwd(const sr_lbs_args* a, const float* ybar, const float* Jbar, float* pbar, float* Abar, float* transbar, float* partials,
                               void* stream) {
-  if (!a || a->P < 0 || a->nframes <= 0 || a->nframes > 32 || a->D <= 0 || a->H <= 0 || a->W <= 0) return SR_EINVAL;
-  if (a->P == 0) {                                   // no points: the sums are zero
-    if (Abar && hipMemsetAsync(Abar, 0, sizeof(float) * a->nframes * NJ * 12, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
-    if (transbar && hipMemsetAsync(transbar, 0, sizeof(float) * a->nframes * 3, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
-    return SR_OK;
-  }
-  if (!a->p || !a->A || !a->vol || !Jbar || a->tp || ((uintptr_t)a->vol & 15) || !partials) return SR_EINVAL;
-  if (!a->batch_inds && a->points_per_frame <= 0) return SR_EINVAL;
+  if (!lbs_shape_ok(a) || a->nframes > 32) return SR_EINVAL;      // (the backward kernels hold one LDS row per frame)
+  if (a->P == 0) return lbs_bwd_no_points(a, Abar, transbar, stream);
+  if (!lbs_points_ok(a) || !Jbar || a->tp || !partials) return SR_EINVAL;
   return lbs_bwd_launch(lbs_jac_bwd_kernel, a, Abar, transbar, partials, stream, ybar, Jbar, pbar);
 }
 
 extern "C" int sr_lbs_fwd(const sr_lbs_args* a, void* stream) {
-  if (!a || a->P < 0 || a->nframes <= 0 || a->D <= 0 || a->H <= 0 || a->W <= 0) return SR_EINVAL;
+  if (!lbs_shape_ok(a)) return SR_EINVAL;
   if (a->P == 0) return SR_OK;
-  if (!a->p || !a->A || !a->trans || !a->vol || !a->y || ((uintptr_t)a->vol & 15)) return SR_EINVAL;
-  if (!a->batch_inds && a->points_per_frame <= 0) return SR_EINVAL;
+  if (!lbs_points_ok(a) || !a->trans || !a->y) return SR_EINVAL;
   if (a->jac && a->tp) return SR_EINVAL;   // the analytic Jacobian assumes weights are looked up at p itself
   const int grid = sr_stream_grid(a->P, 256);
   if (a->jac) hipLaunchKernelGGL(lbs_fwd_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, *a);
@@ -406,14 +423,9 @@ extern "C" int sr_lbs_fwd(const sr_lbs_args* a, void* stream) {
 // Reverse of sr_lbs_fwd (weights looked up at p itself).  Abar [nframes,24,12] and transbar [nframes,3] are WRITTEN (no zero fill
 // needed); any of pbar / Abar / transbar may be NULL.  `partials`: sr_lbs_bwd_workspace_floats(P, nframes) floats of scratch.
 extern "C" int sr_lbs_bwd(const sr_lbs_args* a, const float* ybar, float* pbar, float* Abar, float* transbar, float* partials, void* stream) {
-  if (!a || a->P < 0 || a->nframes <= 0 || a->nframes > 32 || a->D <= 0 || a->H <= 0 || a->W <= 0) return SR_EINVAL;
-  if (a->P == 0) {
-    if (Abar && hipMemsetAsync(Abar, 0, sizeof(float) * a->nframes * NJ * 12, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
-    if (transbar && hipMemsetAsync(transbar, 0, sizeof(float) * a->nframes * 3, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
-    return SR_OK;
-  }
-  if (!a->p || !a->A || !a->vol || !ybar || a->tp || ((uintptr_t)a->vol & 15) || !partials) return SR_EINVAL;
-  if (!a->batch_inds && a->points_per_frame <= 0) return SR_EINVAL;
+  if (!lbs_shape_ok(a) || a->nframes > 32) return SR_EINVAL;
+  if (a->P == 0) return lbs_bwd_no_points(a, Abar, transbar, stream);
+  if (!lbs_points_ok(a) || !ybar || a->tp || !partials) return SR_EINVAL;
   return lbs_bwd_launch(lbs_bwd_kernel, a, Abar, transbar, partials, stream, ybar, pbar);
 }
 
@@ -428,7 +440,6 @@ namespace {
 struct Dual {
   float v, d[3];
 };
-__device__ __forceinline__ Dual mk(float v) { return Dual{v, {0.f, 0.f, 0.f}}; }
 __device__ __forceinline__ Dual operator+(Dual a, Dual b) { return Dual{a.v + b.v, {a.d[0] + b.d[0], a.d[1] + b.d[1], a.d[2] + b.d[2]}}; }
 __device__ __forceinline__ Dual operator-(Dual a, Dual b) { return Dual{a.v - b.v, {a.d[0] - b.d[0], a.d[1] - b.d[1], a.d[2] - b.d[2]}}; }
 __device__ __forceinline__ Dual operator*(Dual a, Dual b) {
@@ -438,46 +449,10 @@ __device__ __forceinline__ Dual operator/(Dual a, Dual b) {
   const float iv = 1.f / b.v, q = a.v * iv;
   return Dual{q, {(a.d[0] - q * b.d[0]) * iv, (a.d[1] - q * b.d[1]) * iv, (a.d[2] - q * b.d[2]) * iv}};
 }
-__device__ __forceinline__ Dual dsqrt(Dual a) { const float s = sqrtf(a.v), h = 0.5f / s; return Dual{s, {a.d[0] * h, a.d[1] * h, a.d[2] * h}}; }
-__device__ __forceinline__ Dual dsin(Dual a) { const float s = sinf(a.v), c = cosf(a.v); return Dual{s, {a.d[0] * c, a.d[1] * c, a.d[2] * c}}; }
-__device__ __forceinline__ Dual dcos(Dual a) { const float s = sinf(a.v), c = cosf(a.v); return Dual{c, {-a.d[0] * s, -a.d[1] * s, -a.d[2] * s}}; }
-
-template <typename S>
-struct Ops;
-template <>
-struct Ops<float> {
-  static __device__ __forceinline__ float c(float v) { return v; }
-  static __device__ __forceinline__ float sq(float a) { return sqrtf(a); }
-  static __device__ __forceinline__ float sn(float a) { return sinf(a); }
-  static __device__ __forceinline__ float cs(float a) { return cosf(a); }
-};
-template <>
-struct Ops<Dual> {
-  static __device__ __forceinline__ Dual c(float v) { return mk(v); }
-  static __device__ __forceinline__ Dual sq(Dual a) { return dsqrt(a); }
-  static __device__ __forceinline__ Dual sn(Dual a) { return dsin(a); }
-  static __device__ __forceinline__ Dual cs(Dual a) { return dcos(a); }
-};
-
-template <typename S>
-__device__ __forceinline__ void rodrigues(S tx, S ty, S tz, S (&R)[9]) {
-  using O = Ops<S>;
-  const S e = O::c(1e-8f);
-  const S ax = tx + e, ay = ty + e, az = tz + e;
-  const S angle = O::sq(ax * ax + ay * ay + az * az);
-  const S nx = tx / angle, ny = ty / angle, nz = tz / angle;
-  const S half = angle * O::c(0.5f);
-  const S qw0 = O::cs(half), sh = O::sn(half);
-  const S qx0 = sh * nx, qy0 = sh * ny, qz0 = sh * nz;
-  const S qn = O::sq(qw0 * qw0 + qx0 * qx0 + qy0 * qy0 + qz0 * qz0);
-  const S w = qw0 / qn, x = qx0 / qn, y = qy0 / qn, z = qz0 / qn;
-  const S w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-  const S wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-  const S two = O::c(2.f);
-  R[0] = w2 + x2 - y2 - z2; R[1] = two * xy - two * wz; R[2] = two * wy + two * xz;
-  R[3] = two * wz + two * xy; R[4] = w2 - x2 + y2 - z2; R[5] = two * yz - two * wx;
-  R[6] = two * xz - two * wy; R[7] = two * wx + two * yz; R[8] = w2 - x2 - y2 + z2;
-}
+__device__ __forceinline__ Dual rot_sqrt(Dual a) { const float s = sqrtf(a.v), h = 0.5f / s; return Dual{s, {a.d[0] * h, a.d[1] * h, a.d[2] * h}}; }
+__device__ __forceinline__ Dual rot_sin(Dual a) { const float s = sinf(a.v), c = cosf(a.v); return Dual{s, {a.d[0] * c, a.d[1] * c, a.d[2] * c}}; }
+__device__ __forceinline__ Dual rot_cos(Dual a) { const float s = sinf(a.v), c = cosf(a.v); return Dual{c, {-a.d[0] * s, -a.d[1] * s, -a.d[2] * s}}; }
+using srrot::rodrigues;
 
 struct ChainConst {
   float rel[24 * 3];      // J_i - J_parent (J_0 for the root)

@@ -13,6 +13,7 @@
 //     unrolled 24 x 12 blend with the vertex's weights in registers.
 // No atomics anywhere: two calls give identical bits.
 #include "sr_common.h"
+#include "rot_device.h"
 
 #define SMPL_NJ 24
 #define SMPL_NPOSE 207                    // 23 x 9
@@ -90,23 +91,6 @@ extern "C" int sr_smpl_regress(const float* x, const float* reg, int32_t B, int6
 }
 
 // ------------------------------------------------------------------------------------------------ pose stage
-__device__ __forceinline__ void smpl_rodrigues(const float* __restrict__ th, float* R) {
-  const float x = th[0], y = th[1], z = th[2];
-  const float ex = x + 1e-8f, ey = y + 1e-8f, ez = z + 1e-8f;
-  const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-  const float nx = x / angle, ny = y / angle, nz = z / angle;
-  const float half = angle * 0.5f;
-  const float cw = cosf(half), sn = sinf(half);
-  float qw = cw, qx = sn * nx, qy = sn * ny, qz = sn * nz;
-  const float qn = sqrtf(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw /= qn; qx /= qn; qy /= qn; qz /= qn;
-  const float w2 = qw * qw, x2 = qx * qx, y2 = qy * qy, z2 = qz * qz;
-  const float wx = qw * qx, wy = qw * qy, wz = qw * qz, xy = qx * qy, xz = qx * qz, yz = qy * qz;
-  R[0] = w2 + x2 - y2 - z2; R[1] = 2.f * xy - 2.f * wz;   R[2] = 2.f * wy + 2.f * xz;
-  R[3] = 2.f * wz + 2.f * xy;   R[4] = w2 - x2 + y2 - z2; R[5] = 2.f * yz - 2.f * wx;
-  R[6] = 2.f * xz - 2.f * wy;   R[7] = 2.f * wx + 2.f * yz;   R[8] = w2 - x2 - y2 + z2;
-}
-
 __global__ __launch_bounds__(SR_WAVE) void smpl_pose_kernel(const float* __restrict__ theta, float* Rs, const float* __restrict__ J, smpl_parents parents,
                                                             int B, float* __restrict__ feature, float* __restrict__ Jt, float* A) {
   const int b = blockIdx.x * SR_WAVE + threadIdx.x;
@@ -118,7 +102,8 @@ __global__ __launch_bounds__(SR_WAVE) void smpl_pose_kernel(const float* __restr
   for (int i = 0; i < SMPL_NJ; ++i) {
     float R[9];
     if (theta) {
-      smpl_rodrigues(theta + ((int64_t)b * SMPL_NJ + i) * 3, R);
+      const float* th = theta + ((int64_t)b * SMPL_NJ + i) * 3;
+      srrot::rodrigues<float>(th[0], th[1], th[2], R);
 #pragma unroll
       for (int e = 0; e < 9; ++e) Rb[i * 9 + e] = R[e];
     } else {

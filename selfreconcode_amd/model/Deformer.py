@@ -1,12 +1,16 @@
 """Non-rigid deformation field -- drop-in for model/Deformer.py (CompositeDeformer :10-20,
 MLPTranslator :22-76, LBSkinner :86-233)."""
+import ctypes
 import os
 
 import numpy as np
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
+from .. import _lib
 from .Embedder import embed_rows
+from ..MCAcc.grid_sampler_mine import GridSamplerMine3dFunction
 from ..mlp_engine import MLPSpec, mlp_apply, pad_cols, pad4, pack_linear
 from ..utils.utils import resolve_band_weights
 
@@ -130,12 +134,6 @@ def getTranslatorNet(device, conf):
 
 # ------------------------------------------------------------------------------------------------
 # SMPL linear-blend skinning on a sampled weight volume (model/Deformer.py:86-233)
-import ctypes  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-from .. import _lib  # noqa: E402
-from ..MCAcc.grid_sampler_mine import GridSamplerMine3dFunction  # noqa: E402
-
-
 def batch_rodrigues(theta):
     """axis-angle [M,3] -> R [M,3,3] through the half-angle quaternion, with the reference's
     `+1e-8` inside the norm only (smpl_pytorch/util.py:35-78)."""
@@ -279,19 +277,25 @@ class LBSkinner(nn.Module):
             a.bmin[i], a.bmax[i] = box[0][i], box[1][i]
         return A12, vol
 
+    def _lbs_args(self, flat, A, trans, batch_inds, ppf, tp=None):
+        """SrLbsArgs, but for the forward's outputs, for contiguous flat points [P,3] (weights looked up at tp, if given) of the frames
+        batch_inds, or else ppf points per frame -> the struct and the tensors to hold until the launch is enqueued."""
+        a = _lib.SrLbsArgs()
+        keep = self.fill_lbs_fields(a, A, trans)
+        a.p, a.tp, a.P = _lib.ptr(flat), _lib.ptr(tp), flat.shape[0]
+        a.batch_inds, a.points_per_frame = _lib.ptr(batch_inds), ppf
+        return a, keep
+
     def fused(self, ps, A, trans, batch_inds=None, with_jac=False, tps=None):
         """No-autograd fused kernel: y (and dy/dp) for flat points [P,3] (batch_inds) or [N,V,3]."""
         flat = ps.reshape(-1, 3).contiguous()
         P = flat.shape[0]
-        a = _lib.SrLbsArgs()
         tr = trans.contiguous()
-        keep = self.fill_lbs_fields(a, A, tr)                       # noqa: F841 (held until the launch below is enqueued)
+        tp = None if tps is None else tps.reshape(-1, 3).contiguous()
+        ppf = 0 if batch_inds is not None else (ps.shape[1] if ps.dim() == 3 else P)
+        a, keep = self._lbs_args(flat, A, tr, batch_inds, ppf, tp)  # noqa: F841 (held until the launch below is enqueued)
         y = torch.empty_like(flat)
         jac = torch.empty((P, 3, 3), device=flat.device) if with_jac else None
-        tp = None if tps is None else tps.reshape(-1, 3).contiguous()
-        a.p, a.tp, a.P = _lib.ptr(flat), _lib.ptr(tp), P
-        a.batch_inds = _lib.ptr(batch_inds)
-        a.points_per_frame = 0 if batch_inds is not None else (ps.shape[1] if ps.dim() == 3 else P)
         a.y, a.jac = _lib.ptr(y), _lib.ptr(jac)
         _lib.launch("sr_lbs_fwd", flat, ctypes.byref(a))
         return y.view(ps.shape), jac
@@ -332,19 +336,28 @@ class LBSkinner(nn.Module):
         T = torch.gather(Tall, 1, batch_inds.view(-1, 1, 1).expand(-1, 1, 12)).view(-1, 3, 4)
         return (T[..., :3] @ p.unsqueeze(-1)).squeeze(-1) + T[..., 3] + trans[batch_inds]
 
-    def fused_backward(self, flat, A, batch_inds, ppf, ybar, need_p, need_A, need_t):
-        P = flat.shape[0]
-        a = _lib.SrLbsArgs()
-        keep = self.fill_lbs_fields(a, A, None)                     # noqa: F841 (the backward kernels do not read trans)
-        a.p, a.tp, a.P = _lib.ptr(flat), 0, P
-        a.batch_inds, a.points_per_frame = _lib.ptr(batch_inds), ppf
-        yb = ybar.contiguous().float()
+    def fused_backward(self, flat, A, batch_inds, ppf, ybar, need_p, need_A, need_t, Jbar=None):
+        """The reverse of fused() for the cotangent ybar (sr_lbs_bwd), or of fused(with_jac=True) for ybar (or None) and Jbar [P,3,3]
+        (sr_lbs_jac_bwd) -> (pbar [P,3], Abar [N,24,12], tbar [N,3]), each None unless needed; no ybar, no tbar."""
+        N, dev = A.shape[0], flat.device
+        a, keep = self._lbs_args(flat, A, None, batch_inds, ppf)    # noqa: F841 (the backward kernels do not read trans)
+        cots = [None if ybar is None else ybar.contiguous().float()] + ([] if Jbar is None else [Jbar.contiguous().float()])
         pbar = torch.empty_like(flat) if need_p else None
-        Abar = torch.empty((A.shape[0], 24, 12), device=flat.device) if need_A else None            # written, not accumulated
-        tbar = torch.empty((A.shape[0], 3), device=flat.device) if need_t else None
-        part = _lib.workspace("sr_lbs_bwd_workspace_floats", P, A.shape[0], device=flat.device, dtype=torch.float32)
-        _lib.launch("sr_lbs_bwd", flat, ctypes.byref(a), yb, pbar, Abar, tbar, part)
+        Abar = torch.empty((N, 24, 12), device=dev) if need_A else None                             # written, not accumulated
+        tbar = torch.empty((N, 3), device=dev) if (need_t and ybar is not None) else None
+        part = _lib.workspace("sr_lbs_bwd_workspace_floats", flat.shape[0], N, device=dev, dtype=torch.float32)
+        _lib.launch("sr_lbs_bwd" if Jbar is None else "sr_lbs_jac_bwd", flat, ctypes.byref(a), *cots, pbar, Abar, tbar, part)
         return pbar, Abar, tbar
+
+
+def _frame_major(flat, A, batch_inds):
+    """flat points [P,3] as LBSkinner.fused takes them: as they are with batch indices, [N,V,3] without"""
+    return flat if batch_inds is not None else flat.view(A.shape[0], -1, 3)
+
+
+def _cotangent_4x4(Abar):
+    """Abar [N,24,12] of the backward kernels (or None) as the cotangent of A [N,24,4,4]: the bottom row of a transform has none"""
+    return None if Abar is None else F.pad(Abar.view(-1, 24, 3, 4), (0, 0, 0, 1))
 
 
 class _PosedChain(torch.autograd.Function):
@@ -382,7 +395,7 @@ class _FusedLBS(torch.autograd.Function):
     @staticmethod
     def forward(ctx, skin, flat, A, trans, batch_inds, ppf):
         flat = flat.contiguous()
-        y, _ = skin.fused(flat if batch_inds is not None else flat.view(A.shape[0], -1, 3), A, trans, batch_inds, False, None)
+        y, _ = skin.fused(_frame_major(flat, A, batch_inds), A, trans, batch_inds, False, None)
         ctx.skin, ctx.ppf = skin, ppf
         ctx.save_for_backward(flat, A, trans, batch_inds)
         return y.reshape(-1, 3)
@@ -393,16 +406,14 @@ class _FusedLBS(torch.autograd.Function):
         skin = ctx.skin
         need_p, need_A, need_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
         if torch.is_grad_enabled():
-            ps = flat if batch_inds is not None else flat.view(A.shape[0], -1, 3)
+            ps = _frame_major(flat, A, batch_inds)
             y2 = skin._composite(ps, ps, A, trans, batch_inds).reshape(-1, 3)
             ins = [t for t, n in ((flat, need_p), (A, need_A), (trans, need_t)) if n]
             gs = list(torch.autograd.grad(y2, ins, ybar, create_graph=True, allow_unused=True))
             out = [gs.pop(0) if n else None for n in (need_p, need_A, need_t)]
             return None, out[0], out[1], out[2], None, None
         pbar, Abar, tbar = skin.fused_backward(flat, A, batch_inds, ctx.ppf, ybar, need_p, need_A, need_t)
-        if Abar is not None:
-            Abar = torch.nn.functional.pad(Abar.view(A.shape[0], 24, 3, 4), (0, 0, 0, 1))
-        return None, pbar, Abar, tbar, None, None
+        return None, pbar, _cotangent_4x4(Abar), tbar, None, None
 
 
 class _LBSValueJacobian(torch.autograd.Function):
@@ -413,7 +424,7 @@ class _LBSValueJacobian(torch.autograd.Function):
     @staticmethod
     def forward(ctx, skin, q, A, trans, batch_inds, ppf):
         flat = q.reshape(-1, 3).contiguous().float()
-        y, J = skin.fused(flat if batch_inds is not None else flat.view(A.shape[0], -1, 3), A, trans, batch_inds, True, None)
+        y, J = skin.fused(_frame_major(flat, A, batch_inds), A, trans, batch_inds, True, None)
         ctx.skin, ctx.ppf = skin, ppf
         ctx.save_for_backward(flat, A, batch_inds)
         ctx.set_materialize_grads(False)
@@ -426,21 +437,9 @@ class _LBSValueJacobian(torch.autograd.Function):
         if ybar is None and Jbar is None:
             return (None,) * 6
         need_q, need_A, need_t = ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.needs_input_grad[3]
-        P = flat.shape[0]
-        a = _lib.SrLbsArgs()
-        keep = skin.fill_lbs_fields(a, A, None)                     # noqa: F841 (as in fused_backward)
-        a.p, a.tp, a.P = _lib.ptr(flat), 0, P
-        a.batch_inds, a.points_per_frame = _lib.ptr(batch_inds), ctx.ppf
-        yb = None if ybar is None else ybar.contiguous().float()
-        Jb = torch.zeros((P, 3, 3), device=flat.device) if Jbar is None else Jbar.contiguous().float()
-        qbar = torch.empty_like(flat) if need_q else None
-        Abar = torch.empty((A.shape[0], 24, 12), device=flat.device) if need_A else None            # written, not accumulated
-        tbar = torch.empty((A.shape[0], 3), device=flat.device) if (need_t and yb is not None) else None
-        part = _lib.workspace("sr_lbs_bwd_workspace_floats", P, A.shape[0], device=flat.device, dtype=torch.float32)
-        _lib.launch("sr_lbs_jac_bwd", flat, ctypes.byref(a), yb, Jb, qbar, Abar, tbar, part)
-        if Abar is not None:
-            Abar = torch.nn.functional.pad(Abar.view(A.shape[0], 24, 3, 4), (0, 0, 0, 1))
-        return None, qbar, Abar, tbar, None, None
+        Jb = torch.zeros((flat.shape[0], 3, 3), device=flat.device) if Jbar is None else Jbar
+        qbar, Abar, tbar = skin.fused_backward(flat, A, batch_inds, ctx.ppf, ybar, need_q, need_A, need_t, Jb)
+        return None, qbar, _cotangent_4x4(Abar), tbar, None, None
 
 
 def deformer_value_jacobian(deformer, ps, defconds, batch_inds, ratio):

@@ -7,6 +7,7 @@ Tolerances are the project's own for these quantities (test_lbs_jacobian_backwar
 test_kinematic_chain_kernel_vs_oracle).  The Python wrappers allocate their outputs with torch.empty; `_poison` hands the allocator
 NaN-filled blocks of the same sizes just before (best effort), and every output is checked to be finite in full."""
 import functools
+import hashlib
 
 import numpy as np
 import pytest
@@ -403,3 +404,46 @@ def test_kinematic_chain_against_float64(B, cot):
     if B > 2:                                                        # posedSkeleton takes a whole sequence: the joints are G's translations
         J = _skin().posedSkeleton([poses.detach(), torch.zeros(B, 3, device=DEV)])
         _close(J, ref.newJ, "posed joints", **CHAIN_TOL)
+
+
+# ------------------------------------------------------------------------------------------------ f. the recorded bits
+# The smallest cases that reach each launch path: frames staged in LDS, 256-thread backward blocks, a workgroup of one point and
+# several frame passes per wave (3 frames); transforms read from global memory in the forward (9); 64-thread backward blocks, a
+# ragged last wave and frames without points (15).
+PIN_CASES = [(3, 257, "interleaved"), (9, 257, "interleaved"), (15, 255, "empty")]
+PIN_CHAIN_B = 33
+
+
+def lbs_path_digests():
+    """name -> SHA-256 (as 32 uint8), in a fixed order, of the bytes of every output of the LBS kernels on PIN_CASES and of the kinematic chain, forward and
+    backward with both cotangents, at PIN_CHAIN_B poses.  oracle/gen_lbs_paths_golden.py records what this returns."""
+    out = {}
+
+    def put(name, t):
+        out[name] = torch.from_numpy(np.frombuffer(hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).digest(), np.uint8).copy())
+
+    for N, P, order in PIN_CASES:
+        c, tag = _case(P, N, order), f"n{N}_"
+        for name, t in zip(("fwd_jac_y", "fwd_jac_J"), _forward(c, True)):
+            put(tag + name, t)
+        put(tag + "fwd_y", _forward(c, False)[0])
+        for name, t in zip(("bwd_pbar", "bwd_Abar", "bwd_transbar"), _bwd(c)):
+            put(tag + name, t)
+        for name, t in zip(("jac_y", "jac_J", "jac_pbar", "jac_Abar", "jac_transbar"), _jac_bwd(c)):
+            put(tag + name, t)
+    B = PIN_CHAIN_B
+    poses = R.chain_poses(B).to(DEV).requires_grad_(True)
+    G, A = _skin().posed_chain(poses)
+    posebar, = torch.autograd.grad([A, G], poses, [fx.det_tensor((B, 24, 4, 4), 62, 1.0).to(DEV), fx.det_tensor((B, 24, 4, 4), 63, 1.0).to(DEV)])
+    put("chain_G", G); put("chain_A", A); put("chain_posebar", posebar)
+    return out
+
+
+def test_every_launch_path_gives_the_recorded_bits(golden):
+    """Pins the kernels bit for bit on the paths that the float64 tests above hold to a tolerance.  tests/golden/lbs_paths.npz holds the
+    digests that oracle/gen_lbs_paths_golden.py recorded with the kernels as they were before csrc/rot_device.h existed; a change that
+    means to keep the bits does not record it again."""
+    g, out = golden("lbs_paths")["digests"], lbs_path_digests()
+    assert g.shape == (len(out), 32) and len(out) == 11 * len(PIN_CASES) + 3
+    for want, (k, v) in zip(g, out.items()):
+        assert torch.equal(v, want), k
