@@ -584,6 +584,31 @@ int sr_chart_uv(const float* verts, int64_t V, const int64_t* faces, int64_t F, 
 int sr_uv_overlap_count(const float* vt, const int64_t* ft, int64_t Vt, int64_t F, int32_t R, double eps, int32_t* count, int64_t* total,
                         void* stream);
 
+/* Drawing the textured template (csrc/texrender.hip): a mip-mapped UV shader on the fragments of sr_rasterize_meshes.  The semantics
+ * are this package's own: stated here, restated in float64 by the tests, unpinned.
+ *   Mip buffer: float4 texels, levels concatenated; level 0 has side R, level l + 1 side (R_l + 1) / 2, the last level side 1 (L
+ *     levels, R <= 32768); a level starts where the one before ends, so every texel is 16-byte aligned when the buffer is.
+ *   sr_texture_mips: texture [R,R,3] float32, or uint8 when is_u8 (a byte x is x / 255.f, IEEE division); valid [R,R] uint8, null = all
+ *     valid.  Level 0 texel = (rgb w, w), w = 1 on a valid texel and 0 elsewhere.  Texel (r, c) of level l + 1 = the sum of the
+ *     in-range texels of {2r, 2r + 1} x {2c, 2c + 1} of level l, divided by their number (1, 2 or 4).  One launch per level.
+ *   sr_texture_face_lod: lod [N,F] per image and face from xy_pix [N,V,2] (pixels), faces [F,3], vt [Vt,2], ft [F,3]: with J the
+ *     Jacobian of the affine map pixel -> uv through the three corners, rho = R max(|J column x|, |J column y|) (Euclidean lengths,
+ *     texels per pixel) and lod = clamp(log2(rho) + bias, 0, L - 1).  A face with an index outside [0, V) / [0, Vt), or a screen
+ *     triangle with |det| < 1e-12, gets L - 1.  L must be the level count of R.
+ *   sr_shade_textured: pix_to_face [N,H,W] (packed n F + f), bary [N,H,W,3] (perspective-correct) -> rgba [N,H,W,4], 16-byte aligned,
+ *     and coverage [N,H,W] (nullable).  Covered pixel: uv = sum_k b_k vt[ft[f][k]]; on level l the sample point is x = u R_l - 0.5,
+ *     y = (1 - v) R_l - 0.5 (sr_uv_rasterize's texel centres), four clamp-to-edge taps with bilinear weights, on the levels
+ *     floor(lod) and min(floor(lod) + 1, L - 1) blended by lod - floor(lod) (lod [N,F] read at the packed index) -> (P, w); rgba =
+ *     (P / w, 1) where w > 0, (host_hole[3], 1) otherwise; coverage = w.  Uncovered pixel (p < 0, p >= N F, or an ft index outside
+ *     [0, Vt)): rgba = (bg_image [N,H,W,3] if given, else host_background[3]; 0), coverage 0, and the texture is not read.  No
+ *     atomics: two runs give identical bits. */
+int sr_texture_mips(const void* texture, int32_t is_u8, const uint8_t* valid, int32_t R, float* mips, void* stream);
+int sr_texture_face_lod(const float* xy_pix, const int64_t* faces, const float* vt, const int64_t* ft, int64_t N, int64_t V, int64_t F,
+                        int64_t Vt, int32_t R, float bias, int32_t L, float* lod, void* stream);
+int sr_shade_textured(const int64_t* pix_to_face, const float* bary, int64_t N, int64_t F, int32_t H, int32_t W, const int64_t* ft,
+                      const float* vt, int64_t Vt, const float* mips, int32_t R, int32_t L, const float* lod, const float* host_background,
+                      const float* host_hole, const float* bg_image, float* rgba, float* coverage, void* stream);
+
 /* Skinning-weight field of a body mesh (csrc/lbsw.hip): compute_lbswField + smooth_weights of model/Deformer.py:235-284.
  *   sr_lbsw_knn_blend: field [nj,D,H,W] (channel-major, W fastest) over the box [bmin, bmax] (host float[3] each).  Voxel (w, h, d) has
  *     centre ((w + 1/2) / W) (bmax - bmin) + bmin per axis, or (w / (W - 1)) ... with align_corners (every size >= 2 then).  Its value

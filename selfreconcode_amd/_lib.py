@@ -247,6 +247,10 @@ SIGNATURES = {
     "sr_texture_resolve": [_i64, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_texture_fill_workspace_bytes": [ctypes.c_int32],
     "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_texture_mips": [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp],
+    "sr_texture_face_lod": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp],
+    "sr_shade_textured": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
+                          _vp, _vp, _vp, _vp],
     "sr_meshprep_bounds": [_vp, _i64, _vp, _vp],
     "sr_meshprep_cell_keys": [_vp, _i64, _vp, ctypes.c_float, _i64, _i64, _i64, _vp, _vp],
     "sr_meshprep_cell_mean": [_vp, _i64, _vp, _vp, _i64, _vp, _vp],

@@ -317,6 +317,12 @@ class OptimNetwork(nn.Module):
         from ..texture import bake_texture
         return bake_texture(self, verts, faces, vt, ft, views, ratio, **kwargs)
 
+    def render_textured(self, avatar, batches, out_root, **kwargs):
+        """The render stage for a TexturedAvatar (the baked template): textured frames, their errors and a turntable under `out_root`:
+        see render.export_textured."""
+        from ..render import export_textured
+        return export_textured(self, avatar, batches, out_root, **kwargs)
+
     def _shaded_previews(self, TmpVs, Tmpfs, ratio, frame_ids, defV, frags, gts):
         """imgs / def1imgs of the reference's infer (network.py:306-337): HardPhongShader with pytorch3d 0.4.0's defaults (ops.shade_phong).
         imgs: the posed template `defV` as the frame cameras rasterised it into `frags`, light at (0, 1, 0); with `gts`: RGB only, and

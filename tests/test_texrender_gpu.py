@@ -1,0 +1,319 @@
+"""The textured renderer's kernels (csrc/texrender.hip through render_ops / render) against the float64 restatement of
+tests/_texrender_ref.py, on synthetic fragments (random pix_to_face and barycentrics, no rasteriser in front), then the module on a
+two-triangle quad and a folder round trip.
+
+Bounds.  Mips: 8 x 2^-24 relative per level (sums of at most four non-negative terms), level 0 bit-equal.  Face lod: 1e-4 absolute (the
+2 x 2 determinant of a triangle whose smallest angle is >= 10 degrees carries <= 3 x 2^-24 / sin 10 deg ~ 1e-6 relative).  Shade, with the
+kernel's own lod handed to the restatement: coverage, and colours where the restatement's coverage is >= 0.25, within (16 + 8 R) x 2^-24
+(the sample position u R - 0.5 carries ~ R 2^-24 texels of rounding against texel differences of at most 1; P and w are sums of
+non-negative terms, so P / w does not amplify it); background, hole and alpha bit-equal."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _texrender_ref as ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+EPS = 2.0 ** -24
+MIN_COVERAGE = 0.25
+LEFT_OUT_CAP = 0.05
+
+
+def _gpu_levels(mips):
+    from selfreconcode_amd.render_ops import mip_layout
+    sides, offsets = mip_layout(mips.R)
+    buf = mips.buffer.cpu().numpy()
+    assert mips.L == len(sides) and buf.shape == (offsets[-1] + 1, 4) and buf.dtype == np.float32
+    return [buf[o:o + s * s].reshape(s, s, 4) for s, o in zip(sides, offsets)]
+
+
+# ------------------------------------------------------------------ mips
+@pytest.mark.parametrize("with_valid", [False, True])
+@pytest.mark.parametrize("dtype", ["float32", "uint8"])
+@pytest.mark.parametrize("R", [1, 2, 5, 64])
+def test_mips_vs_restatement(R, dtype, with_valid):
+    from selfreconcode_amd.render_ops import texture_mips
+    rng = np.random.default_rng(100 + R)
+    tex = rng.integers(0, 256, (R, R, 3), dtype=np.uint8) if dtype == "uint8" else rng.random((R, R, 3), dtype=np.float32)
+    valid = (rng.random((R, R)) < 0.7) if with_valid else None
+    mips = texture_mips(torch.from_numpy(tex).to(DEV), None if valid is None else torch.from_numpy(valid).to(DEV))
+    got, want = _gpu_levels(mips), ref.mips(tex, valid)
+    assert [g.shape for g in got] == [w.shape for w in want] and want[-1].shape[0] == 1
+    assert np.array_equal(got[0].astype(np.float64), want[0])                                   # level 0: bit for bit
+    worst = 0.
+    for g, w in zip(got, want):
+        assert (g[w == 0.] == 0.).all()
+        err = np.abs(g.astype(np.float64) - w)[w != 0.] / w[w != 0.]
+        worst = max(worst, float(err.max()) if err.size else 0.)
+    print(f"R = {R}, {dtype}, valid {with_valid}: largest relative mip error {worst:.3e}, bound {8 * EPS:.3e}")
+    assert worst <= 8 * EPS, f"largest relative mip error {worst:.3e} > {8 * EPS:.3e}"
+    again = texture_mips(torch.from_numpy(tex).to(DEV), None if valid is None else torch.from_numpy(valid).to(DEV))
+    assert torch.equal(mips.buffer, again.buffer)
+
+
+# ------------------------------------------------------------------ face lod
+def _triangles(rng, count, min_angle=12.):
+    """[count,3,2] triangles inside the unit disc whose smallest angle is >= min_angle degrees (the bound's 10 with a margin for the
+    float32 rounding of the coordinates)."""
+    out = []
+    while len(out) < count:
+        p = rng.uniform(-1., 1., (3, 2))
+        if (np.linalg.norm(p, axis=1) > 1.).any():
+            continue
+        ang = []
+        for k in range(3):
+            a, b = p[(k + 1) % 3] - p[k], p[(k + 2) % 3] - p[k]
+            ang.append(np.degrees(np.arccos(np.clip(a @ b / (np.linalg.norm(a) * np.linalg.norm(b)), -1., 1.))))
+        if min(ang) >= min_angle:
+            out.append(p)
+    return np.stack(out)
+
+
+def _lod_case():
+    """N = 2 images of F = 64 disjoint triangles (V = Vt = 3 F), R = 64 (L = 7).  The screen triangles span 2^-3 .. 2^8 pixels against
+    3 .. 25 texels in UV, so lod falls below 0, in between and above L - 1; face 5 is degenerate on screen, face 9 has a UV index
+    out of range."""
+    rng = np.random.default_rng(21)
+    N, F, R = 2, 64, 64
+    uv_size = rng.uniform(0.05, 0.4, (F, 1, 1))
+    vt = (0.5 + (rng.uniform(-1., 1., (F, 1, 2)) * (0.5 - uv_size) + _triangles(rng, F) * uv_size)).reshape(3 * F, 2).astype(np.float32)
+    px_size = 2. ** rng.uniform(-3., 8., (N, F, 1, 1))
+    xy = (256. + rng.uniform(-1., 1., (N, F, 1, 2)) * (256. - px_size) + _triangles(rng, N * F).reshape(N, F, 3, 2) * px_size)
+    xy = xy.reshape(N, 3 * F, 2).astype(np.float32)
+    assert 0. <= vt.min() and vt.max() <= 1. and 0. <= xy.min() and xy.max() <= 512.
+    faces = np.arange(3 * F, dtype=np.int64).reshape(F, 3)
+    ft = faces.copy()
+    xy[:, 3 * 5 + 2] = xy[:, 3 * 5 + 1]
+    ft[9, 1] = 3 * F
+    return xy, faces, vt, ft, R
+
+
+@pytest.mark.parametrize("bias", [0., 0.75])
+def test_face_lod_vs_restatement(bias):
+    from selfreconcode_amd.render_ops import TextureMips, mip_layout, texture_face_lod
+    xy, faces, vt, ft, R = _lod_case()
+    sides, offsets = mip_layout(R)
+    L = len(sides)
+    mips = TextureMips(torch.zeros((offsets[-1] + 1, 4), device=DEV), R, L)
+    want = ref.face_lod(xy, faces, vt, ft, R, bias, L)
+    normal = np.ones(want.shape[1], bool)
+    normal[[5, 9]] = False
+    assert (want[:, ~normal] == L - 1).all()
+    w = want[:, normal]
+    assert (w == 0.).sum() >= 5 and (w == L - 1).sum() >= 5 and ((w > 0.) & (w < L - 1) & (w != np.floor(w))).sum() >= 30
+    t = [torch.from_numpy(a).to(DEV) for a in (xy, faces, vt, ft)]
+    got = texture_face_lod(*t, mips, bias)
+    assert got.shape == want.shape and got.dtype == torch.float32
+    g = got.cpu().numpy().astype(np.float64)
+    assert (g[:, ~normal] == L - 1).all()
+    err = float(np.abs(g - want).max())
+    print(f"bias {bias}: largest lod error {err:.3e}, bound 1e-4")
+    assert err <= 1e-4, f"largest lod error {err:.3e} > 1e-4"
+    assert torch.equal(got, texture_face_lod(*t, mips, bias))
+
+
+# ------------------------------------------------------------------ shade
+class _Frags:
+    def __init__(self, p2f, bary):
+        self.pix_to_face, self.bary_coords = p2f.unsqueeze(-1), bary.unsqueeze(3)
+
+
+@functools.lru_cache(maxsize=None)
+def _shade_case(R, N, S, valid_mode, seed):
+    """Synthetic fragments of N images of S x S over F = 8 faces and an R x R texture, and the restatement's answer for them, computed
+    once.  pix_to_face holds -1, indices of every image (n F + f on any pixel), indices >= N F, and face 3 whose UV index is out of
+    range; face 6's UV corners lie outside [0, 1] (clamp to edge); lod holds 0, L - 1, the integers between and fractions."""
+    rng = np.random.default_rng(seed)
+    F = 8
+    sides = ref.layout(R)[0]
+    L = len(sides)
+    tex = rng.random((R, R, 3), dtype=np.float32)
+    valid = {'all': None, 'none': np.zeros((R, R), bool), 'random': rng.random((R, R)) < 0.7}[valid_mode]
+    vt = rng.random((3 * F, 2)).astype(np.float32)
+    vt[18:21] = [[-0.3, 0.5], [1.3, -0.2], [0.4, 1.35]]
+    ft = np.arange(3 * F, dtype=np.int64).reshape(F, 3)
+    ft[1] = [4, 0, 7]                                                                  # (a face may share UV vertices with others)
+    ft[3, 2] = 3 * F
+    p2f = rng.integers(0, N * F, (N, S, S)).astype(np.int64)
+    kind = rng.random((N, S, S))
+    p2f[kind < 0.10] = -1
+    p2f[(kind >= 0.10) & (kind < 0.13)] = N * F
+    p2f[(kind >= 0.13) & (kind < 0.15)] = N * F + 5
+    p2f[(kind >= 0.15) & (kind < 0.16)] = -7
+    bary = rng.dirichlet(np.ones(3), (N, S, S)).astype(np.float32)
+    lod = rng.uniform(0., L - 1., (N, F)).astype(np.float32)
+    lod.reshape(-1)[:4] = [0., L - 1., float((L - 1) // 2), float(max(L - 2, 0))]
+    bg_image = rng.random((N, S, S, 3), dtype=np.float32)
+    levels = ref.mips(tex, valid)
+    want = {bg: ref.shade(p2f, bary, ft, vt, levels, lod, (0.9, 0.8, 0.1), (0.2, 0.3, 0.7), bg_image if bg else None) for bg in (False, True)}
+    for a in (tex, vt, ft, p2f, bary, lod, bg_image):
+        a.setflags(write=False)
+    return dict(tex=tex, valid=valid, vt=vt, ft=ft, p2f=p2f, bary=bary, lod=lod, bg_image=bg_image, want=want, L=L, F=F)
+
+
+def _run_shade(case, bg):
+    from selfreconcode_amd.render_ops import shade_textured, texture_mips
+    d = lambda a: torch.from_numpy(np.array(a)).to(DEV)
+    mips = texture_mips(d(case['tex']), None if case['valid'] is None else d(case['valid']))
+    frags = _Frags(d(case['p2f']), d(case['bary']))
+    return shade_textured(frags, d(case['ft']), d(case['vt']), mips, d(case['lod']), background=(0.9, 0.8, 0.1), hole=(0.2, 0.3, 0.7),
+                          bg_image=d(case['bg_image']) if bg else None, return_coverage=True)
+
+
+def _check_shade(case, bg, R, rgba, cov):
+    """Compares one run with the restatement -> (largest colour error, largest coverage error)."""
+    want_rgba, want_cov, covered = case['want'][bg]
+    tol = (16 + 8 * R) * EPS
+    p2f, N, F = case['p2f'], case['p2f'].shape[0], case['F']
+    assert (p2f == -1).any() and (p2f >= N * F).any() and ((p2f >= F) & (p2f < N * F))[0].any() and ((p2f % F == 3) & (p2f >= 0) & (p2f < N * F) & ~covered).any()
+    assert covered.sum() > 0.6 * covered.size
+    compared = covered & (want_cov >= MIN_COVERAGE)
+    holes = covered & (want_cov == 0.)
+    if case['valid'] is None or case['valid'].any():
+        left_out = 1. - compared.sum() / covered.sum()
+        assert left_out <= LEFT_OUT_CAP, f"{left_out:.3%} of the covered pixels have coverage < {MIN_COVERAGE} in the restatement"
+    else:
+        assert holes.sum() == covered.sum()
+    got, gcov = rgba.cpu().numpy(), cov.cpu().numpy()
+    assert got.dtype == np.float32 and got.shape == want_rgba.shape and gcov.shape == want_cov.shape
+    assert np.array_equal(got[..., 3].astype(np.float64), want_rgba[..., 3])                               # alpha: bit for bit
+    assert np.array_equal(got[~covered].astype(np.float64), want_rgba[~covered]) and (gcov[~covered] == 0.).all()
+    assert np.array_equal(got[holes].astype(np.float64), want_rgba[holes]) and (gcov[holes] == 0.).all()
+    cov_err = float(np.abs(gcov - want_cov).max())
+    col_err = float(np.abs(got[..., :3] - want_rgba[..., :3])[compared].max()) if compared.any() else 0.
+    print(f"R = {R}, {N} x {p2f.shape[1]}^2, bg_image {bg}: largest colour error {col_err:.3e}, coverage error {cov_err:.3e}, bound {tol:.3e}")
+    assert cov_err <= tol, f"largest coverage error {cov_err:.3e} > {tol:.3e} (R = {R})"
+    assert col_err <= tol, f"largest colour error {col_err:.3e} > {tol:.3e} (R = {R})"
+    return col_err, cov_err
+
+
+@pytest.mark.parametrize("bg", [False, True])
+@pytest.mark.parametrize("R,valid_mode", [(1, 'all'), (5, 'all'), (64, 'random')])
+def test_shade_vs_restatement(R, valid_mode, bg):
+    case = _shade_case(R, 2, 16, valid_mode, 40 + R)
+    lod = case['lod'].reshape(-1)
+    assert (lod == 0.).any() and (lod == case['L'] - 1).any() and (R == 1 or ((lod != np.floor(lod)).any() and (lod == np.floor(lod)).sum() >= 3))
+    assert case['vt'][18:21].min() < 0. and case['vt'][18:21].max() > 1.
+    _check_shade(case, bg, R, *_run_shade(case, bg))
+
+
+@pytest.mark.parametrize("R", [1, 5])
+def test_shade_all_invalid_texture_gives_the_hole_colour(R):
+    case = _shade_case(R, 2, 16, 'none', 50 + R)
+    rgba, cov = _run_shade(case, False)
+    _check_shade(case, False, R, rgba, cov)
+    covered = torch.from_numpy(case['want'][False][2]).to(DEV)
+    assert covered.any() and (rgba[covered] == torch.tensor([0.2, 0.3, 0.7, 1.], device=DEV)).all() and float(cov.abs().max()) == 0.
+
+
+def test_shade_beyond_one_grid_pass_and_twice():
+    """N H W = 559 872 pixels > 2048 blocks x 256 threads: the grid-stride loop takes a second pass; two runs give identical bits."""
+    case = _shade_case(64, 3, 432, 'random', 77)
+    assert case['p2f'].size > 2048 * 256
+    rgba, cov = _run_shade(case, True)
+    _check_shade(case, True, 64, rgba, cov)
+    rgba2, cov2 = _run_shade(case, True)
+    assert torch.equal(rgba, rgba2) and torch.equal(cov, cov2)
+
+
+def test_shade_refuses_mismatched_shapes():
+    from selfreconcode_amd.render_ops import shade_textured, texture_face_lod, texture_mips
+    case = _shade_case(5, 2, 16, 'all', 45)
+    d = lambda a: torch.from_numpy(np.array(a)).to(DEV)
+    mips = texture_mips(d(case['tex']))
+    frags = _Frags(d(case['p2f']), d(case['bary']))
+    with pytest.raises(ValueError):
+        shade_textured(frags, d(case['ft']), d(case['vt']), mips, d(case['lod'])[:, :5])
+    with pytest.raises(ValueError):
+        shade_textured(frags, d(case['ft']), d(case['vt']), mips, d(case['lod']), bg_image=d(case['bg_image'])[:1])
+    with pytest.raises(ValueError):
+        shade_textured(frags, d(case['ft']), d(case['vt']), mips._replace(R=6), d(case['lod']))
+    with pytest.raises(ValueError):
+        texture_mips(d(case['tex'])[:, :4])
+    with pytest.raises(ValueError):
+        texture_face_lod(torch.zeros(2, 24, 2, device=DEV), d(case['ft'])[:5], d(case['vt']), d(case['ft']), mips)
+    with pytest.raises(RuntimeError):
+        shade_textured(frags, d(case['ft']), d(case['vt']).cpu(), mips, d(case['lod']))
+
+
+# ------------------------------------------------------------------ the module
+def _camera(S, f=100.):
+    from selfreconcode_amd.model.CameraMine import RectifiedPerspectiveCameras
+    Rm = torch.tensor([[-1., 0., 0.], [0., 1., 0.], [0., 0., -1.]])
+    return RectifiedPerspectiveCameras(torch.tensor([[f, f]]), torch.tensor([[S / 2. + 0.3, S / 2. - 0.2]]), Rm.view(1, 3, 3),
+                                       torch.tensor([[0.01, -0.02, 2.4]]), image_size=[(S, S)]).to(DEV)
+
+
+def _quad():
+    verts = np.array([[-0.3, -0.28, 0.02], [0.31, -0.3, -0.03], [0.3, 0.29, 0.05], [-0.29, 0.3, 0.]], np.float32)
+    faces = np.array([[0, 1, 2], [0, 2, 3]], np.int64)
+    vt = np.array([[0.05, 0.1], [0.95, 0.08], [0.9, 0.93], [0.07, 0.9], [0.5, 0.5]], np.float32)
+    ft = np.array([[0, 1, 2], [0, 2, 3]], np.int64)
+    return verts, faces, vt, ft
+
+
+def test_textured_avatar_render_equals_the_composed_restatement():
+    from selfreconcode_amd.render import TexturedAvatar
+    from selfreconcode_amd.render_ops import texture_face_lod
+    S, R = 32, 64
+    rng = np.random.default_rng(8)
+    verts, faces, vt, ft = _quad()
+    tex = rng.random((R, R, 3), dtype=np.float32)
+    d = lambda a: torch.from_numpy(a).to(DEV)
+    avatar = TexturedAvatar(d(verts), d(faces), d(vt), d(ft), d(tex))
+    cam = _camera(S)
+    defV = torch.stack([d(verts), d(verts) * 0.6 + torch.tensor([0.1, 0.05, 0.2], device=DEV)])
+    rgba, frags, cov = avatar.render(defV, cam, S, S, background=(0., 0.25, 1.))
+    p2f, bary = frags.pix_to_face[..., 0].cpu().numpy(), frags.bary_coords[..., 0, :].cpu().numpy()
+    assert rgba.shape == (2, S, S, 4) and cov.shape == (2, S, S) and ((p2f >= 0).sum((1, 2)) > 100).all() and (p2f < 0).sum() > 100
+    xy_pix, _ = cam.project(defV)
+    lod = texture_face_lod(xy_pix, avatar.faces, avatar.vt, avatar.ft, avatar.mips)
+    want_lod = ref.face_lod(xy_pix.cpu().numpy(), faces, vt, ft, R, 0., avatar.mips.L)
+    assert np.abs(lod.cpu().numpy() - want_lod).max() <= 1e-4 and ((want_lod > 0.) & (want_lod < avatar.mips.L - 1)).all()
+    want_rgba, want_cov, covered = ref.shade(p2f, bary, ft, vt, ref.mips(tex), lod.cpu().numpy(), (0., 0.25, 1.))
+    tol = (16 + 8 * R) * EPS
+    got = rgba.cpu().numpy()
+    assert np.array_equal(covered, p2f >= 0) and np.array_equal(got[~covered].astype(np.float64), want_rgba[~covered])
+    assert np.array_equal(got[..., 3].astype(np.float64), want_rgba[..., 3])
+    err = float(np.abs(got - want_rgba)[covered].max())
+    assert err <= tol and float(np.abs(cov.cpu().numpy() - want_cov).max()) <= tol, f"largest colour error {err:.3e} > {tol:.3e}"
+    with pytest.raises(ValueError):
+        avatar.render(defV[:, :3], cam, S, S)
+
+
+def _dilate_ref(mask, k):
+    R = mask.shape[0]
+    out = np.zeros_like(mask)
+    for i in range(R):
+        for j in range(R):
+            out[i, j] = mask[max(i - k // 2, 0):min(i - k // 2 + k - 1, R - 1) + 1, max(j - k // 2, 0):min(j - k // 2 + k - 1, R - 1) + 1].any()
+    return out
+
+
+@pytest.mark.parametrize("R", [20, 30])                       # int(0.1 R) = 2 (the window is not symmetric), 3
+def test_from_folder_round_trips(tmp_path, R):
+    from selfreconcode_amd.infer_export import write_png
+    from selfreconcode_amd.render import TexturedAvatar
+    from selfreconcode_amd.render_ops import texture_mips
+    from selfreconcode_amd.texture import write_obj_uv
+    rng = np.random.default_rng(9)
+    verts, faces, vt, ft = _quad()
+    tex = rng.integers(0, 256, (R, R, 3), dtype=np.uint8)
+    mask = np.zeros((R, R), bool)
+    mask[R // 3:R // 2, 5:9] = True
+    mask[R - 1, 0] = mask[3, R - 2] = True
+    write_obj_uv(os.path.join(tmp_path, 'uvmap.obj'), verts, faces, vt, ft)
+    write_png(os.path.join(tmp_path, 'texture.png'), tex)
+    write_png(os.path.join(tmp_path, 'tex_mask.png'), np.uint8(mask) * 255)
+    avatar = TexturedAvatar.from_folder(str(tmp_path), DEV)
+    for got, want in ((avatar.verts, verts), (avatar.faces, faces), (avatar.vt, vt), (avatar.ft, ft)):
+        assert got.is_cuda and np.array_equal(got.cpu().numpy(), want)
+    valid = _dilate_ref(mask, int(0.1 * R))
+    assert valid.sum() > mask.sum() and not valid.all()
+    want = texture_mips(torch.from_numpy(tex).to(DEV), torch.from_numpy(valid).to(DEV))
+    assert (avatar.mips.R, avatar.mips.L) == (R, want.L) and torch.equal(avatar.mips.buffer, want.buffer)
+    assert np.array_equal(_gpu_levels(avatar.mips)[0][..., 3] == 1., valid)
