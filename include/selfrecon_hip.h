@@ -723,6 +723,30 @@ struct sr_log_slots_s {
 typedef struct sr_log_slots_s sr_log_slots;
 int sr_log_row(const sr_log_slots* slots_by_value, int32_t n, float* ring, int32_t ring_rows, int32_t ld, int64_t row, void* stream);
 
+/* Motion-JPEG encoder (csrc/mjpeg.hip): baseline sequential JPEG (SOF0), 8 bit, YCbCr (JFIF full range) 4:2:0, of B frames
+ * rgb [B,H,W,3] uint8 -- the entropy-coded bytes only; the host writes the header segments and EOI around them.  With R = ceil(H / 16)
+ * MCU rows of M = ceil(W / 16) MCUs (the picture padded by repeating its last column and row), one restart interval is one MCU row.
+ * All arithmetic is integer: two calls give identical bytes.
+ *   sr_jpeg_transform: coef [B, R M, 6, 64] int16 = the quantised DCT coefficients of each MCU's blocks Y00 Y01 Y10 Y11 Cb Cr in zigzag
+ *     order; qtab [2,64] uint16 are the luminance and chrominance divisors (1..255), in zigzag order as DQT lists them.
+ *   sr_jpeg_entropy: codes every interval with huff [4,256] = (code | length << 16) of the DC luminance, DC chrominance, AC luminance
+ *     and AC chrominance tables, indexed by category / (run << 4 | category); DC prediction restarts with each interval and its last
+ *     byte is padded with 1s.  rowbuf receives interval i's bytes, every 0xFF followed by 0x00, at i * 12 M SR_JPEG_BLOCK_BYTES
+ *     (i = b R + r) and row_len [B R] their count.  `bits` is scratch of bits_dwords dwords, 128-byte aligned, zeroed by the call:
+ *     B R intervals of (6 M SR_JPEG_BLOCK_BYTES / 4 rounded up to a multiple of 32) dwords.
+ *   sr_jpeg_gather: out = the frames' scan data one after the other, frame b at offsets[b] .. offsets[b + 1] (offsets [B+1] int64):
+ *     its intervals in order with RSTm, m = r mod 8, behind interval r < R - 1.  row_start [B R] int64 is scratch.
+ * SR_JPEG_BLOCK_BYTES bounds the code of one block before stuffing for every input (a DC code of at most 22 bits and 63 AC codes of at
+ * most 26), so the buffers' sizes are functions of (B, H, W) alone: SR_ENOSPC if bits_dwords is less than the B R strides above, rowbuf_bytes < 12 B R M
+ * SR_JPEG_BLOCK_BYTES or out_bytes < B (12 R M SR_JPEG_BLOCK_BYTES + 2 (R - 1)), and nothing is launched.  SR_EINVAL: a NULL
+ * pointer, B, H or W outside [1, 65535], coef not 16-byte or bits not 128-byte aligned. */
+#define SR_JPEG_BLOCK_BYTES 208
+int sr_jpeg_transform(const uint8_t* rgb, int32_t B, int32_t H, int32_t W, const uint16_t* qtab, int16_t* coef, void* stream);
+int sr_jpeg_entropy(const int16_t* coef, int32_t B, int32_t H, int32_t W, const uint32_t* huff, uint32_t* bits, int64_t bits_dwords,
+                    uint8_t* rowbuf, int64_t rowbuf_bytes, uint32_t* row_len, void* stream);
+int sr_jpeg_gather(const uint8_t* rowbuf, const uint32_t* row_len, int32_t B, int32_t H, int32_t W, int64_t* row_start, uint8_t* out,
+                   int64_t out_bytes, int64_t* offsets, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,15 @@
 """The inference driver: the reference's infer.py over infer_export.export_frames.
 
     python -m selfreconcode_amd.infer --gpu-ids 0 --rec-root <capture folder>/result [--frames N] [--nColor] [--C]
+                                      [--video [--fps F] [--video-quality Q] [--nI]]
 
 Reads rec_root/config.conf, opens the capture folder rec_root/.. in order (shuffle off, nothing learnable), loads rec_root/latest.pth,
-extracts the template with discretizeSDF(ratio, None, 0.) and writes what infer_export lists under rec_root.  `--nV` is accepted;
-videos are not written either way, and the command says so once.  `--nI` cannot be honoured for the same reason (the
-reference refuses --nV --nI together): the images are what this command writes.
+extracts the template with discretizeSDF(ratio, None, 0.) and writes what infer_export lists under rec_root.
+
+`--video` adds meshs/video.avi, def1meshs/video.avi and (unless --nColor) colors/video.avi: Motion-JPEG encoded on the GPU (video.py,
+DESIGN 3.17) at --fps (30) and --video-quality (90), the stand-in for the reference's video.mp4.  Without it no video is
+written and the command says so once, with or without `--nV`; `--video --nV` contradict each other and are refused.  `--nI` (no PNGs)
+is honoured with --video and refused without it, as the reference refuses --nV --nI: something has to be written.
 """
 import argparse
 import os.path as osp
@@ -29,7 +33,24 @@ def build_parser():
     parser.add_argument('--nI', action='store_true', help='not save image')
     parser.add_argument('--C', action='store_true', help='overlay on gtimg')
     parser.add_argument('--nColor', action='store_true', help='not render images')
+    parser.add_argument('--video', action='store_true', help='write video.avi (Motion-JPEG) next to the images')
+    parser.add_argument('--fps', default=30., type=float, metavar='F', help='frame rate of the videos')
+    parser.add_argument('--video-quality', default=90, type=int, metavar='Q', help='JPEG quality of the videos, 1..100')
     return parser
+
+
+def parse_args(parser, argv):
+    """The arguments, or the parser's error exit for combinations that leave nothing to write or contradict each other."""
+    args = parser.parse_args(argv)
+    if args.rec_root is None:
+        parser.error('--rec-root is required')
+    if args.video and args.nV:
+        parser.error('--video and --nV contradict each other')
+    if args.nI and not args.video:
+        parser.error('--nI: the images are all this command writes (videos are not written, see --nV)')
+    if args.video and not (1 <= args.video_quality <= 100 and args.fps > 0.):
+        parser.error('--video-quality must lie in 1..100 and --fps must be positive')
+    return args
 
 
 def limited(dataloader, batch_size, frames, out=None, no_color=False):
@@ -62,26 +83,25 @@ def load_network(rec_root, device="cuda:0", batch_size=1, out=print, resolutions
     return optNet, dataset, dataloader
 
 
-def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overlay=False, out=print, resolutions=None):
-    """-> (maskE, TmpVs, Tmpfs, optNet).  `resolutions`: the extraction pyramid instead of infer.py's (small scenes)."""
+def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overlay=False, out=print, resolutions=None, video=False, images=True,
+          fps=30., quality=90):
+    """-> (maskE, TmpVs, Tmpfs, optNet).  `resolutions`: the extraction pyramid instead of infer.py's (small scenes); video, images, fps,
+    quality: see infer_export.export_frames."""
     from .infer_export import export_frames
     optNet, dataset, dataloader = load_network(rec_root, device, batch_size, out, resolutions)
     TmpVs, Tmpfs = optNet.discretizeSDF(RATIO, None, 0.)
-    maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, RATIO, color=color, overlay=overlay)
+    maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, RATIO, color=color, overlay=overlay,
+                          video=video, images=images, fps=fps, quality=quality)
     out('done')
     return maskE, TmpVs, Tmpfs, optNet
 
 
 def main(argv=None, out=print, resolutions=None):
-    parser = build_parser()
-    args = parser.parse_args(argv)
-    if args.rec_root is None:
-        parser.error('--rec-root is required')
-    if args.nI:
-        parser.error('--nI: the images are all this command writes (videos are not written, see --nV)')
-    out('videos (meshs/video.mp4, def1meshs/video.mp4, colors/video.mp4) are not written' + ('' if args.nV else '; pass --nV to say so'))
+    args = parse_args(build_parser(), argv)
+    if not args.video:
+        out('videos (meshs/video.mp4, def1meshs/video.mp4, colors/video.mp4) are not written' + ('' if args.nV else '; pass --nV to say so'))
     infer(args.rec_root, torch.device('cuda', args.gpu_ids[0]), args.batch_size, args.frames, color=not args.nColor, overlay=args.C, out=out,
-          resolutions=resolutions)
+          resolutions=resolutions, video=args.video, images=not args.nI, fps=args.fps, quality=args.video_quality)
     return 0
 
 

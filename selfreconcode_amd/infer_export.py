@@ -8,7 +8,11 @@
     out_root/errors.txt            the per-frame mask error 1 - IoU, in the reference's layout
 
 PNG pixels are the ones cv2.imwrite writes for the reference's arrays (it takes BGR): file RGB = img[..., :3] for the previews
-(written as img[:, :, [2, 1, 0]]) and color[..., ::-1] for the colour image (written as is).  Videos (--nV) are not written.
+(written as img[:, :, [2, 1, 0]]) and color[..., ::-1] for the colour image (written as is).
+
+With `video=True` each of the three folders also receives `video.avi`, a Motion-JPEG AVI (video.py) of exactly the
+pixels its PNGs hold, one frame per visited frame in the order visited: what stands in for the reference's `video.mp4`.
+`images=False` leaves the PNGs out (the reference's --nI); meshs/<fid>.npy is written either way, as in the reference.
 """
 import os
 import struct
@@ -64,11 +68,44 @@ def _frame_count(dataset):
     return len(dataset) if hasattr(dataset, "__len__") else int(dataset.frame_num)
 
 
-def export_frames(net, TmpVs, Tmpfs, batches, out_root, ratio, color=True, overlay=False):
+class FrameVideo:
+    """`path` as a Motion-JPEG AVI of the uint8 RGB frames handed to add(): a frame that only exists on the host is uploaded, a batch
+    is encoded on the GPU (video.JpegEncoder) and appended.  Encoder and file are made at the first frame, whose size they take."""
+
+    def __init__(self, path, device, fps=30., quality=90):
+        self.path, self.device, self.fps, self.quality = path, torch.device(device), float(fps), quality
+        self.encoder = self.writer = None
+
+    def add(self, frames):
+        """frames [B,H,W,3] uint8: a GPU tensor, or anything np.ascontiguousarray takes."""
+        from .video import JpegEncoder, MjpegWriter
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8))
+        frames = frames.to(self.device)
+        if self.encoder is None:
+            H, W = frames.shape[1:3]
+            self.encoder = JpegEncoder(H, W, self.quality, self.device, max_batch=frames.shape[0])
+            self.writer = MjpegWriter(self.path, W, H, self.fps)
+        for jpeg in self.encoder.encode(frames):
+            self.writer.write(jpeg)
+
+    def close(self):
+        if self.writer is not None:
+            self.writer.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def export_frames(net, TmpVs, Tmpfs, batches, out_root, ratio, color=True, overlay=False, video=False, images=True, fps=30., quality=90):
     """infer.py's loop over `batches` -- (frame_ids, outs) as the reference's dataloader yields them, outs['mask'] [B,H,W] and
     outs['img'] [B,H,W,3] in [-1, 1] (BGR) -- writing the files listed in the module docstring under `out_root`.  color=False is
-    --nColor (no colour pass, no colors/*.png), overlay=True is --C (backgrounds from the input images).  Returns the per-frame mask
-    errors written to errors.txt (-1: frame not visited)."""
+    --nColor (no colour pass, no colors/*.png), overlay=True is --C (backgrounds from the input images); video / images / fps / quality: the module docstring's
+    video.avi files and --nI.  Returns the per-frame mask errors written to errors.txt (-1: frame not visited)."""
     device = TmpVs.device
     ds = net.dataset
     os.makedirs(out_root, exist_ok=True)
@@ -78,6 +115,8 @@ def export_frames(net, TmpVs, Tmpfs, batches, out_root, ratio, color=True, overl
     maskE = -1. * np.ones((_frame_count(ds),))
     previous = net.shaded_previews
     net.shaded_previews = True
+    videos = {sub: FrameVideo(os.path.join(out_root, sub, "video.avi"), device, fps, quality)
+              for sub in (("meshs", "def1meshs", "colors") if color else ("meshs", "def1meshs"))} if video else {}
     try:
         for frame_ids, outs in batches:
             frame_ids = torch.as_tensor(frame_ids).long().to(device)
@@ -88,13 +127,21 @@ def export_frames(net, TmpVs, Tmpfs, batches, out_root, ratio, color=True, overl
             fids = frame_ids.cpu().numpy().reshape(-1)
             for fid, img, def1img, defV in zip(fids, imgs, def1imgs, defVs):
                 np.save(os.path.join(out_root, "meshs", "%d.npy" % fid), defV.reshape(-1, 3))
-                write_png(os.path.join(out_root, "meshs", "%d.png" % fid), img[:, :, :3])
-                write_png(os.path.join(out_root, "def1meshs", "%d.png" % fid), def1img[:, :, :3])
-            if colors is not None:
+                if images:
+                    write_png(os.path.join(out_root, "meshs", "%d.png" % fid), img[:, :, :3])
+                    write_png(os.path.join(out_root, "def1meshs", "%d.png" % fid), def1img[:, :, :3])
+            if colors is not None and images:
                 for fid, c in zip(fids, colors):
                     write_png(os.path.join(out_root, "colors", "%d.png" % fid), c[:, :, ::-1])
+            if video:
+                videos["meshs"].add(np.stack([img[:, :, :3] for img in imgs]))
+                videos["def1meshs"].add(np.stack([img[:, :, :3] for img in def1imgs]))
+                if colors is not None:
+                    videos["colors"].add(np.stack([c[:, :, ::-1] for c in colors]))
             maskE[fids] = gts['maskE']
     finally:
         net.shaded_previews = previous
+        for v in videos.values():
+            v.close()
     write_errors(os.path.join(out_root, "errors.txt"), maskE)
     return maskE

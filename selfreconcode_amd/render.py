@@ -1,7 +1,7 @@
 """Drawing the textured avatar: the step after `texture` (train, infer, texture, render).
 
     python -m selfreconcode_amd.render --gpu-ids 0 --rec-root <capture folder>/result [--frames N] [--batch-size B] [--turntable K]
-                                       [--turntable-frame F] [--C] [--lod-bias b]
+                                       [--turntable-frame F] [--C] [--lod-bias b] [--video [--fps F] [--video-quality Q]]
 
 Reads rec_root/template/{uvmap.obj, texture.png, tex_mask.png} (what the texture command leaves), poses the UV-mapped template with the
 trained deformer as the bake posed it, rasterises it under the dataset's camera and shades it with the mip-mapped UV shader of
@@ -14,9 +14,13 @@ csrc/texrender.hip (this package's own semantics, unpinned).  Wr
     rec_root/turntable/<k>.png     with --turntable K: the posed body of one frame turned about the vertical axis through its centre
                                    by 2 pi k / K, under that frame's camera, on white (0.png is that frame's textured/<fid>.png)
 
+    rec_root/textured/video.avi    with --video: the textured frames in the order visited, Motion-JPEG encoded on the GPU (video.py)
+    rec_root/turntable/video.avi   with --video and --turntable K: the K views, one turn
+
 and nothing outside those two folders.
 """
 import argparse
+import contextlib
 import math
 import os
 
@@ -126,40 +130,56 @@ def _u8(rgb):
     return torch.clamp(rgb * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
 
 
-def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, turntable_frame=None, ratio=None, lod_bias=0.):
+def _u8_device(rgb):
+    """_u8's bytes, left on the GPU (the float -> uint8 conversion truncates on both sides)."""
+    return torch.clamp(rgb * 255., min=0., max=255.).to(torch.uint8)
+
+
+def _film(video, path, device, fps, quality):
+    """The FrameVideo at `path` as a context (closed on the way out), or a context of None without `video`."""
+    from .infer_export import FrameVideo
+    return FrameVideo(path, device, fps, quality) if video else contextlib.nullcontext()
+
+
+def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, turntable_frame=None, ratio=None, lod_bias=0., video=False,
+                    fps=30., quality=90):
     """Draws the avatar for `batches` -- (frame_ids, outs) as the dataloader yields them, outs['img'] [B,H,W,3] in [-1, 1] (BGR) and
     outs['mask'] [B,H,W] -- and writes textured/<fid>.png, textured/errors.txt and turntable/<k>.png (k < turntable) under `out_root`,
     as the module docstring lists them.  `turntable_frame`: the frame whose pose is turned (default: the first visited one).
+    video=True adds textured/video.avi and turntable/video.avi: the PNGs' pixels, in the order written, at `fps` and JPEG `quality`.
     Returns {fid: (l1, psnr, mask error)}."""
     device = avatar.verts.device
     folder = os.path.join(out_root, 'textured')
     os.makedirs(folder, exist_ok=True)
     errors, turn = {}, None
-    for frame_ids, outs in batches:
-        fids = torch.as_tensor(frame_ids).long().to(device).reshape(-1)
-        N = fids.numel()
-        cameras, H, W = net._cameras(N, device)
-        image = (outs['img'].to(device).float().flip(-1) + 1.) * 0.5                       # B, G, R in [-1, 1] -> R, G, B in [0, 1]
-        gtM = outs['mask'].to(device).float()
-        if tuple(image.shape) != (N, H, W, 3) or tuple(gtM.shape) != (N, H, W):
-            raise ValueError(f"export_textured: images {tuple(image.shape)} / masks {tuple(gtM.shape)} for the dataset's {H} x {W} camera")
-        defV = pose(net, avatar, fids, ratio)
-        rgba, frags, coverage = avatar.render(defV, cameras, H, W, lod_bias=lod_bias, bg_image=image.contiguous() if overlay else None)
-        rgb = rgba[..., :3]
-        covered = frags.pix_to_face[..., 0] >= 0
-        sil = covered.float()
-        maskE = 1. - (sil * gtM).view(N, -1).sum(1) / (sil + gtM - sil * gtM).abs().view(N, -1).sum(1)
-        use = (covered & (gtM > 0.5) & (coverage >= MIN_COVERAGE)).float()[..., None]
-        n = (3. * use.view(N, -1).sum(1)).clamp(min=1.)
-        diff = (rgb.clamp(0., 1.) - image) * use
-        l1 = diff.abs().view(N, -1).sum(1) / n
-        psnr = 10. * torch.log10(1. / (diff.square().view(N, -1).sum(1) / n).clamp(min=PSNR_FLOOR))
-        pixels = _u8(rgb)
-        for i, fid in enumerate(fids.tolist()):
-            write_png(os.path.join(folder, '%d.png' % fid), pixels[i])
-            errors[fid] = (float(l1[i]), float(psnr[i]), float(maskE[i]))
-            if turn is None and (turntable_frame is None or fid == int(turntable_frame)):
-                turn = (fid, defV[i])
+    with _film(video, os.path.join(folder, 'video.avi'), device, fps, quality) as film:
+        for frame_ids, outs in batches:
+            fids = torch.as_tensor(frame_ids).long().to(device).reshape(-1)
+            N = fids.numel()
+            cameras, H, W = net._cameras(N, device)
+            image = (outs['img'].to(device).float().flip(-1) + 1.) * 0.5                       # B, G, R in [-1, 1] -> R, G, B in [0, 1]
+            gtM = outs['mask'].to(device).float()
+            if tuple(image.shape) != (N, H, W, 3) or tuple(gtM.shape) != (N, H, W):
+                raise ValueError(f"export_textured: images {tuple(image.shape)} / masks {tuple(gtM.shape)} for the dataset's {H} x {W} camera")
+            defV = pose(net, avatar, fids, ratio)
+            rgba, frags, coverage = avatar.render(defV, cameras, H, W, lod_bias=lod_bias, bg_image=image.contiguous() if overlay else None)
+            rgb = rgba[..., :3]
+            covered = frags.pix_to_face[..., 0] >= 0
+            sil = covered.float()
+            maskE = 1. - (sil * gtM).view(N, -1).sum(1) / (sil + gtM - sil * gtM).abs().view(N, -1).sum(1)
+            use = (covered & (gtM > 0.5) & (coverage >= MIN_COVERAGE)).float()[..., None]
+            n = (3. * use.view(N, -1).sum(1)).clamp(min=1.)
+            diff = (rgb.clamp(0., 1.) - image) * use
+            l1 = diff.abs().view(N, -1).sum(1) / n
+            psnr = 10. * torch.log10(1. / (diff.square().view(N, -1).sum(1) / n).clamp(min=PSNR_FLOOR))
+            pixels = _u8(rgb)
+            if film is not None:
+                film.add(_u8_device(rgb))
+            for i, fid in enumerate(fids.tolist()):
+                write_png(os.path.join(folder, '%d.png' % fid), pixels[i])
+                errors[fid] = (float(l1[i]), float(psnr[i]), float(maskE[i]))
+                if turn is None and (turntable_frame is None or fid == int(turntable_frame)):
+                    turn = (fid, defV[i])
     if not errors:
         raise ValueError("export_textured: no frames")
     with open(os.path.join(folder, 'errors.txt'), 'w') as fh:
@@ -172,12 +192,16 @@ def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, 
             turn = (int(turntable_frame), pose(net, avatar, [int(turntable_frame)], ratio)[0])
         os.makedirs(os.path.join(out_root, 'turntable'), exist_ok=True)
         views = turntable_vertices(turn[1], int(turntable))
-        for k0 in range(0, int(turntable), TURNTABLE_BATCH):
-            chunk = views[k0:k0 + TURNTABLE_BATCH]
-            cameras, H, W = net._cameras(chunk.shape[0], device)
-            pixels = _u8(avatar.render(chunk, cameras, H, W, lod_bias=lod_bias)[0][..., :3])
-            for i in range(chunk.shape[0]):
-                write_png(os.path.join(out_root, 'turntable', '%d.png' % (k0 + i)), pixels[i])
+        with _film(video, os.path.join(out_root, 'turntable', 'video.avi'), device, fps, quality) as film:
+            for k0 in range(0, int(turntable), TURNTABLE_BATCH):
+                chunk = views[k0:k0 + TURNTABLE_BATCH]
+                cameras, H, W = net._cameras(chunk.shape[0], device)
+                rgb = avatar.render(chunk, cameras, H, W, lod_bias=lod_bias)[0][..., :3]
+                pixels = _u8(rgb)
+                if film is not None:
+                    film.add(_u8_device(rgb))
+                for i in range(chunk.shape[0]):
+                    write_png(os.path.join(out_root, 'turntable', '%d.png' % (k0 + i)), pixels[i])
     return errors
 
 
@@ -191,6 +215,9 @@ def build_parser():
     parser.add_argument('--turntable-frame', default=None, type=int, metavar='F', help='the frame the turntable turns (default: the first one rendered)')
     parser.add_argument('--C', action='store_true', help='overlay on gtimg')
     parser.add_argument('--lod-bias', default=0., type=float, metavar='b', help='added to every level of detail (negative: sharper)')
+    parser.add_argument('--video', action='store_true', help='write textured/video.avi and turntable/video.avi (Motion-JPEG)')
+    parser.add_argument('--fps', default=30., type=float, metavar='F', help='frame rate of the videos')
+    parser.add_argument('--video-quality', default=90, type=int, metavar='Q', help='JPEG quality of the videos, 1..100')
     return parser
 
 
@@ -202,6 +229,8 @@ def main(argv=None, out=print, resolutions=None):
     args = parser.parse_args(argv)
     if args.rec_root is None:
         parser.error('--rec-root is required')
+    if args.video and not (1 <= args.video_quality <= 100 and args.fps > 0.):
+        parser.error('--video-quality must lie in 1..100 and --fps must be positive')
     folder = os.path.join(args.rec_root, 'template')
     for name in ('uvmap.obj', 'texture.png', 'tex_mask.png'):
         if not os.path.isfile(os.path.join(folder, name)):
@@ -213,7 +242,8 @@ def main(argv=None, out=print, resolutions=None):
         parser.error('--turntable-frame %d: the capture has frames 0 .. %d' % (args.turntable_frame, dataset.frame_num - 1))
     avatar = TexturedAvatar.from_folder(folder, device)
     errors = export_textured(net, avatar, limited(dataloader, args.batch_size, args.frames), args.rec_root, overlay=args.C,
-                             turntable=args.turntable, turntable_frame=args.turntable_frame, lod_bias=args.lod_bias)
+                             turntable=args.turntable, turntable_frame=args.turntable_frame, lod_bias=args.lod_bias,
+                             video=args.video, fps=args.fps, quality=args.video_quality)
     mean = np.mean(np.asarray(list(errors.values()), np.float64), axis=0)
     out('textured: %d frames, mean l1 %.4f, psnr %.2f, mask %.4f; wrote %s' % (len(errors), mean[0], mean[1], mean[2],
                                                                                os.path.join(args.rec_root, 'textured')))
