@@ -747,6 +747,33 @@ int sr_jpeg_entropy(const int16_t* coef, int32_t B, int32_t H, int32_t W, const 
 int sr_jpeg_gather(const uint8_t* rowbuf, const uint32_t* row_len, int32_t B, int32_t H, int32_t W, int64_t* row_start, uint8_t* out,
                    int64_t out_bytes, int64_t* offsets, void* stream);
 
+/* Surface-distance evaluation (csrc/surfdist.hip): exact point-to-mesh distance through a uniform grid, and a stratified surface
+ * sampler.  The semantics are this package's own: stated here, restated in float64 by the tests, unpinned.
+ *   tri [F,12] float32, 16-byte aligned: the corners a, b, c of every face and three floats of padding.  F < 2^31.
+ *   Grid: lo [3] on the device, cell > 0, (nx, ny, nz) with at most 2^24 cells; the coordinate of x on an axis is floor((x - lo) / cell)
+ *     in float32 (IEEE subtraction and division), clamped to [0, n - 1]; a cell's key is (k ny + j) nx + i.
+ *   sr_surfdist_face_cells: count [F] = the number of cells the box of face f overlaps (the product of its three coordinate ranges).
+ *   sr_surfdist_emit_pairs: key [pairs] / pair_face [pairs]: face f writes its cells in ascending key from offset[f] on (offset = the
+ *     exclusive cumulative sum of count, pairs = its total); nothing is written at or beyond `pairs`.
+ *   sr_surfdist_query: per point the float32 distance to the mesh as a set of closed triangles, the face that attains it (the lowest
+ *     index among equal float32 squared distances) and the closest point on that face.  cell_start [cells + 1] int64 / cell_faces [pairs]
+ *     int32: the faces of every cell.  The search visits Chebyshev rings of cells round the point's (clamped) cell and stops when the
+ *     best squared distance is below (1 - 2^-14)^2 times a lower bound of everything unvisited, or nothing is left; at most
+ *     max(nx, ny, nz) rings.  A point with a NaN or Inf coordinate gets dist = NaN, face = -1, closest = NaN without any search.
+ *   sr_surfdist_brute: the same outputs from a loop over all faces, with the same distance function and tie rule: bit-identical.
+ *   sr_mesh_sample: n samples of the surface: sample i lies at r = (i + xi) / n cum_area[F - 1] (double) of the cumulative face areas
+ *     cum_area [F] float64 -- the first face with cum_area > r -- with barycentrics (1 - sqrt u, sqrt u (1 - v), sqrt u v); xi, u, v =
+ *     (splitmix64(3 i + {0, 1, 2} + seed 0x9E3779B97F4A7C15) >> 11) 2^-53.  points [n,3], face [n], normals [n,3] (unit, of the face).
+ * SR_EINVAL: a NULL pointer, a count <= 0, F >= 2^31 - 1, tri not 16-byte aligned, cell <= 0 or more than 2^24 cells. */
+int sr_surfdist_face_cells(const float* tri, int64_t F, const float* lo, float cell, int32_t nx, int32_t ny, int32_t nz, int64_t* count, void* stream);
+int sr_surfdist_emit_pairs(const float* tri, int64_t F, const float* lo, float cell, int32_t nx, int32_t ny, int32_t nz, const int64_t* offset,
+                           int64_t pairs, int64_t* key, int32_t* pair_face, void* stream);
+int sr_surfdist_query(const float* points, int64_t P, const float* tri, int64_t F, const float* lo, float cell, int32_t nx, int32_t ny, int32_t nz,
+                      const int64_t* cell_start, const int32_t* cell_faces, int64_t pairs, float* dist, int64_t* face, float* closest, void* stream);
+int sr_surfdist_brute(const float* points, int64_t P, const float* tri, int64_t F, float* dist, int64_t* face, float* closest, void* stream);
+int sr_mesh_sample(const float* tri, const double* cum_area, int64_t F, int64_t n, int64_t seed, float* points, int64_t* face, float* normals,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,187 @@
+"""Geometry evaluation on the GPU: point-to-mesh distance, Chamfer, point-to-surface (P2S), normal consistency and F-score between two
+triangle meshes (csrc/surfdist.hip, surfdist_ops.py).
+
+    python -m selfreconcode_amd.evaluate --gpu-ids 0 --pred A.ply --gt B.ply [--samples N] [--seed S] [--tau t ...] [--out FILE.json]
+    python -m selfreconcode_amd.evaluate --gpu-ids 0 --rec-root R --gt-root G [--frames N] [--samples N] [--seed S] [--tau t ...]
+
+Mesh-pair mode prints the metrics of two files.  Folder mode compares every posed mesh `R/meshs/<fid>.npy` of an `infer` run (faces
+from `R/tmp.ply`) with `G/<fid>.ply` or `G/<fid>.obj` and writes `R/geometry_errors.txt` and `R/geometry_errors.json`.  No alignment
+and no scaling is applied: both meshes are taken in the coordinates they are given.  Out of scope: signed distance, rigid / ICP
+alignment, quads.
+"""
+import argparse
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import surfdist_ops as sd
+from .mesh_io import read_mesh, read_ply
+
+
+def _directed(src, dst, samples, seed):
+    """samples of mesh index `src` against mesh index `dst`: (dist [n], dot of the sample's and the closest face's normal [n])."""
+    pts, _, nrm = sd._sample(src.tri, src.cum_area, samples, seed)
+    dist, face, _ = sd.closest_point(pts, dst)
+    return dist, (nrm * dst.face_normals()[face]).sum(1)
+
+
+def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=()):
+    """Distances between the surfaces of pred = (verts [V,3], faces [F,3]) and gt, GPU tensors, as a dict of Python floats.
+
+    `samples` points are drawn on each surface (surfdist_ops.sample_surface: area-weighted, stratified; pred with `seed`, gt with
+    `seed + 1`) and each is given its exact distance to the other mesh (closest_point).  Per direction, `pred_to_gt` and `gt_to_pred`:
+    `mean`, `rms`, `max` of those distances.  `chamfer` = (mean pred_to_gt + mean gt_to_pred) / 2: the L1 Chamfer distance, of
+    distances and not of squared distances.  `p2s` = mean gt_to_pred, the direction the paper reports.  `normal_consistency` = the mean
+    over both directions of the dot product between the sample's face normal and the unit normal of the closest face (signed; 0 for a
+    closest face without area).  `fscore@tau` for every tau: 2 P R / (P + R) with P the share of pred_to_gt < tau and R the share of
+    gt_to_pred < tau (0 when both are 0).  Reductions are torch's on fixed shapes, in double; two calls give identical numbers; the
+    results come to the host in one copy (the two index builds read their sizes on the way).  No alignment or scaling."""
+    _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
+    samples = int(samples)
+    if samples <= 0:
+        raise ValueError(f"samples > 0 expected, got {samples}")
+    a, b = sd.MeshIndex.build(pred[0], pred[1]), sd.MeshIndex.build(gt[0], gt[1])
+    for name, m in (("pred", a), ("gt", b)):
+        if not m.area > 0:
+            raise ValueError(f"surface_metrics: the {name} mesh has no area")
+    d_ab, n_ab = _directed(a, b, samples, seed)
+    d_ba, n_ba = _directed(b, a, samples, seed + 1)
+    names, vals = [], []
+    for name, d in (("pred_to_gt", d_ab.double()), ("gt_to_pred", d_ba.double())):
+        names += [(name, "mean"), (name, "rms"), (name, "max")]
+        vals += [d.mean(), (d * d).mean().sqrt(), d.max()]
+    names.append("normal_consistency")
+    vals.append(0.5 * (n_ab.double().mean() + n_ba.double().mean()))
+    taus = [float(t) for t in taus]
+    for t in taus:
+        names += [("P", t), ("R", t)]
+        vals += [(d_ab < t).sum().double(), (d_ba < t).sum().double()]                 # (counts: the shares are divided on the host)
+    host = torch.stack(vals).cpu().tolist()
+    out, pr = {"pred_to_gt": {}, "gt_to_pred": {}}, {}
+    for name, v in zip(names, host):
+        if name == "normal_consistency":
+            out[name] = v
+        elif name[0] in ("P", "R"):
+            pr[name] = v
+        else:
+            out[name[0]][name[1]] = v
+    out["chamfer"] = 0.5 * (out["pred_to_gt"]["mean"] + out["gt_to_pred"]["mean"])
+    out["p2s"] = out["gt_to_pred"]["mean"]
+    for t in taus:
+        p, r = pr[("P", t)] / samples, pr[("R", t)] / samples
+        out[f"fscore@{t:g}"] = 2. * p * r / (p + r) if p + r > 0 else 0.
+    return out
+
+
+def vertex_to_surface(verts, gt):
+    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh."""
+    _lib.require_gpu(verts, gt[0], gt[1])
+    return sd.closest_point(verts, sd.MeshIndex.build(gt[0], gt[1]))[0]
+
+
+def _to_device(mesh, device):
+    return torch.from_numpy(np.asarray(mesh[0], np.float32)).to(device), torch.from_numpy(np.asarray(mesh[1], np.int64)).to(device)
+
+
+def write_geometry_errors(path, fids, chamfer, p2s):
+    """geometry_errors.txt in the layout of infer's errors.txt: one line per frame, then mean / max / min and the ten worst frames (as
+    positions in the list of compared frames, like `maxinds` there) of each column."""
+    with open(path, "w") as ff:
+        ff.write("      chamfer p2s\n")
+        for fid, c, p in zip(fids, chamfer, p2s):
+            ff.write("%4s: %.6f %.6f\n" % (fid, c, p))
+        for name, col in (("chamfer", np.asarray(chamfer, np.float64)), ("p2s", np.asarray(p2s, np.float64))):
+            ff.write("%s mean: %.6f, max: %.6f, min: %.6f, maxinds:" % (name, col.mean(), col.max(), col.min()))
+            for ind in (-col).argsort()[:10]:
+                ff.write("%d " % ind)
+            ff.write("\n")
+
+
+def _frame_ids(folder):
+    fids = [os.path.splitext(f)[0] for f in os.listdir(folder) if f.endswith(".npy")]
+    return sorted(fids, key=lambda s: (0, int(s), s) if s.lstrip("-").isdigit() else (1, 0, s))
+
+
+def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, seed=0, taus=(), out=print):
+    """Folder mode (see the module text).  -> dict(frames: {fid: metrics}, skipped: [fid], summary)."""
+    _, faces = read_ply(os.path.join(rec_root, "tmp.ply"))
+    faces_d = torch.from_numpy(faces).to(device)
+    fids = _frame_ids(os.path.join(rec_root, "meshs"))
+    if frames is not None:
+        fids = fids[:int(frames)]
+    per, skipped = {}, []
+    for fid in fids:
+        gt_file = next((p for p in (os.path.join(gt_root, fid + ext) for ext in (".ply", ".obj")) if os.path.isfile(p)), None)
+        if gt_file is None:
+            skipped.append(fid)
+            continue
+        verts = torch.from_numpy(np.load(os.path.join(rec_root, "meshs", fid + ".npy")).astype(np.float32).reshape(-1, 3)).to(device)
+        per[fid] = surface_metrics((verts, faces_d), _to_device(read_mesh(gt_file), device), samples, seed, taus)
+        out("%4s: chamfer %.6f p2s %.6f" % (fid, per[fid]["chamfer"], per[fid]["p2s"]))
+    out("%d frames compared, %d skipped (no ground-truth file)" % (len(per), len(skipped)))
+    if not per:
+        raise ValueError(f"evaluate: no frame of {rec_root}/meshs has a ground-truth file in {gt_root}")
+    order = list(per)
+    chamfer, p2s = [per[f]["chamfer"] for f in order], [per[f]["p2s"] for f in order]
+    write_geometry_errors(os.path.join(rec_root, "geometry_errors.txt"), order, chamfer, p2s)
+    result = {"frames": per, "skipped": skipped,
+              "summary": {"chamfer_mean": float(np.mean(chamfer)), "chamfer_max": float(np.max(chamfer)), "p2s_mean": float(np.mean(p2s)),
+                          "p2s_max": float(np.max(p2s)), "samples": int(samples), "seed": int(seed)}}
+    with open(os.path.join(rec_root, "geometry_errors.json"), "w") as fh:
+        json.dump(result, fh, indent=1)
+    return result
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(prog="python -m selfreconcode_amd.evaluate",
+                                     description="Chamfer / P2S / normal consistency / F-score between triangle meshes on the GPU.  No alignment "
+                                                 "and no scaling is applied: both meshes are taken in the coordinates they are given.")
+    parser.add_argument("--gpu-ids", nargs="+", type=int, metavar="IDs", default=[0], help="gpu ids (the first is used)")
+    parser.add_argument("--pred", default=None, metavar="A", help="mesh-pair mode: the predicted mesh (.ply / .obj)")
+    parser.add_argument("--gt", default=None, metavar="B", help="mesh-pair mode: the ground-truth mesh (.ply / .obj)")
+    parser.add_argument("--rec-root", default=None, metavar="R", help="folder mode: a result folder of infer (tmp.ply, meshs/<fid>.npy)")
+    parser.add_argument("--gt-root", default=None, metavar="G", help="folder mode: the folder of <fid>.ply / <fid>.obj ground-truth meshes")
+    parser.add_argument("--frames", default=None, type=int, metavar="N", help="folder mode: only the first N frames")
+    parser.add_argument("--samples", default=1_000_000, type=int, metavar="N", help="surface samples per direction")
+    parser.add_argument("--seed", default=0, type=int, metavar="S", help="seed of the sampler")
+    parser.add_argument("--tau", nargs="*", type=float, default=[], metavar="t", help="F-score thresholds, in the meshes' units")
+    parser.add_argument("--out", default=None, metavar="FILE.json", help="mesh-pair mode: also write the metrics here")
+    return parser
+
+
+def parse_args(argv=None):
+    """The arguments, refused (SystemExit) unless exactly one of the two modes is given in full."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    pair, folder = (args.pred, args.gt), (args.rec_root, args.gt_root)
+    if any(pair) and any(folder):
+        parser.error("give either --pred / --gt or --rec-root / --gt-root, not both")
+    if not any(pair) and not any(folder):
+        parser.error("give --pred A --gt B (mesh-pair mode) or --rec-root R --gt-root G (folder mode)")
+    if any(pair) and not all(pair):
+        parser.error("mesh-pair mode needs both --pred and --gt")
+    if any(folder) and not all(folder):
+        parser.error("folder mode needs both --rec-root and --gt-root")
+    if args.samples <= 0:
+        parser.error("--samples must be positive")
+    return args
+
+
+def main(argv=None, out=print):
+    args = parse_args(argv)
+    device = torch.device("cuda", args.gpu_ids[0])
+    if args.pred:
+        m = surface_metrics(_to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device), args.samples, args.seed, args.tau)
+        out(json.dumps(m))
+        if args.out:
+            with open(args.out, "w") as fh:
+                json.dump(m, fh, indent=1)
+        return m
+    return evaluate_folder(args.rec_root, args.gt_root, device, args.frames, args.samples, args.seed, args.tau, out)
+
+
+if __name__ == "__main__":
+    main()
