@@ -264,7 +264,8 @@ extern "C" {
 int sr_refine_init(const sr_refine_args* a, void* stream) {
   const int rc = check_args(a);
   if (rc != SR_OK) return rc;
-  if (!a->p0 || !a->rays || !a->batch_inds || !a->unit) { if (a->P > 0) return SR_EINVAL; }
+  if (!a->live) return SR_EINVAL;                                    // P == 0 still zeroes the counts: the kernel writes live[0..times+2]
+  if (!a->p0 ||!a->rays || !a->batch_inds || !a->unit) { if (a->P > 0) return SR_EINVAL; }
   if ((a->a0 != nullptr) != (a->a0d != nullptr)) return SR_EINVAL;
   if (a->a0 && (!a->w_sdf || !a->w_def || (a->E > 0 && !a->conds))) return SR_EINVAL;
   const int64_t n = a->P > a->times + 3 ? a->P : a->times + 3;
