@@ -774,6 +774,35 @@ int sr_surfdist_brute(const float* points, int64_t P, const float* tri, int64_t 
 int sr_mesh_sample(const float* tri, const double* cum_area, int64_t F, int64_t n, int64_t seed, float* points, int64_t* face, float* normals,
                    void* stream);
 
+/* Point-to-plane ICP of surface samples against a mesh (csrc/icp.hip; DESIGN.md 3.19, this package's own semantics): the two launches of
+ * one iteration.  The mesh, the grid and their refusals are sr_surfdist_query's.
+ *   state [SR_ICP_STATE] float64 on the device: M (3 x 3, row major), t (3), the done flag at SR_ICP_DONE (0 or 1), then the number of
+ *     solves that ran live; T(p) = M p + t.  (ox, oy, oz), rho > 0: the frame the system is normalised in (centre and half diagonal of
+ *     the target's box).
+ *   sr_icp_accumulate: for every sample p of points [S,3]: q = fl32(((M0 px + M1 py) + M2 pz) + t) per row, in double; (d, f, c) =
+ *     sr_surfdist_query's triple of q; n = the unit normal of face f in double (0 without area); the pair is kept when q is finite and
+ *     d <= max_dist.  With x = (q - o) / rho, w = [x cross n, n, n.x, n.(q - c) / rho] (8 numbers), a block adds w_j w_l (j <= l, row
+ *     major: 36), 1 and d^2 over its kept pairs and writes them as its row of partial [blocks, SR_ICP_COLS] (the last two columns are
+ *     0).  blocks must be min(ceil(S / 256), SR_ICP_MAX_BLOCKS).  With the done flag set nothing is written, unless `measure` is not 0.
+ *   sr_icp_solve (one wave): the column sums of partial over the blocks in ascending order; the first 7 x 7 of them scaled to a unit
+ *     diagonal and solved for xi = (omega, tau, sigma) by Cholesky in double -- sigma is 0 unless `scale`; an unknown whose column
+ *     has a mean square <= 2^-46 or whose pivot is below 2^-20 is set to 0 and leaves the system --; M <- (1 + sigma) exp(omega) M,
+ *     t <- o + (1 + sigma) exp(omega) (t - o) + rho tau; done <- max |xi| < tol.  Row `it` of history [iters, SR_ICP_HISTORY]: kept
+ *     pairs, the rms of their d (before this update), max |xi|, rank, sqrt(|M|_F^2 / 3), done.  With the done flag set on entry the
+ *     state is left alone and the row repeats row it - 1 with done = 1.
+ * SR_EINVAL: a NULL pointer, S <= 0, tri not 16-byte aligned, a bad grid, rho <= 0, max_dist < 0 or NaN, a wrong block count,
+ * iters <= 0, `it` outside [0, iters). */
+#define SR_ICP_MAX_BLOCKS 1024
+#define SR_ICP_COLS 40
+#define SR_ICP_HISTORY 6
+#define SR_ICP_STATE 16
+#define SR_ICP_DONE 12
+int sr_icp_accumulate(const float* points, int64_t S, const float* tri, int64_t F, const float* lo, float cell, int32_t nx, int32_t ny, int32_t nz,
+                      const int64_t* cell_start, const int32_t* cell_faces, int64_t pairs, const double* state, double ox, double oy, double oz,
+                      double rho, float max_dist, int32_t measure, double* partial, int32_t blocks, void* stream);
+int sr_icp_solve(const double* partial, int32_t blocks, double ox, double oy, double oz, double rho, int32_t scale, double tol, int32_t it,
+                 int32_t iters, double* state, double* history, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,11 +3,14 @@ triangle meshes (csrc/surfdist.hip, surfdist_ops.py).
 
     python -m selfreconcode_amd.evaluate --gpu-ids 0 --pred A.ply --gt B.ply [--samples N] [--seed S] [--tau t ...] [--out FILE.json]
     python -m selfreconcode_amd.evaluate --gpu-ids 0 --rec-root R --gt-root G [--frames N] [--samples N] [--seed S] [--tau t ...]
+    ... [--align {none,rigid,similarity}] [--align-samples N] [--align-iters K] [--align-max-dist d] [--align-shared]
 
 Mesh-pair mode prints the metrics of two files.  Folder mode compares every posed mesh `R/meshs/<fid>.npy` of an `infer` run (faces
-from `R/tmp.ply`) with `G/<fid>.ply` or `G/<fid>.obj` and writes `R/geometry_errors.txt` and `R/geometry_errors.json`.  No alignment
-and no scaling is applied: both meshes are taken in the coordinates they are given.  Out of scope: signed distance, rigid / ICP
-alignment, quads.
+from `R/tmp.ply`) with `G/<fid>.ply` or `G/<fid>.obj` and writes `R/geometry_errors.txt` and `R/geometry_errors.json`.  By default no
+alignment and no scaling is applied: both meshes are taken in the coordinates they are given.  `--align rigid` / `--align similarity`
+first takes the predicted mesh onto the ground truth by point-to-plane ICP (align.py; local: it starts from matched
+centroids), per frame, or with `--align-shared` once on the first compared frame for all of them (a constant camera-frame offset).
+Out of scope: signed distance, global registration, quads.
 """
 import argparse
 import json
@@ -17,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import align as al
 from . import surfdist_ops as sd
 from .mesh_io import read_mesh, read_ply
 
@@ -28,7 +32,23 @@ def _directed(src, dst, samples, seed):
     return dist, (nrm * dst.face_normals()[face]).sum(1)
 
 
-def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=()):
+ALIGN_MODES = ("rigid", "similarity")
+
+
+def _alignment(pred, index, align, align_opts):
+    """The Alignment `align` asks for: "rigid" / "similarity" estimate it (pred = (verts, faces) against the MeshIndex of gt, with
+    `align_opts` as keywords of align.icp_align), an Alignment is taken as it is."""
+    if isinstance(align, al.Alignment):
+        return align
+    if align not in ALIGN_MODES:
+        raise ValueError(f"align must be None, 'rigid', 'similarity' or an Alignment, got {align!r}")
+    opts = dict(align_opts or {})
+    if "scale" in opts:
+        raise ValueError("align_opts: `scale` is what `align` decides")
+    return al.icp_index(pred, index, scale=align == "similarity", **opts)
+
+
+def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, align_opts=None):
     """Distances between the surfaces of pred = (verts [V,3], faces [F,3]) and gt, GPU tensors, as a dict of Python floats.
 
     `samples` points are drawn on each surface (surfdist_ops.sample_surface: area-weighted, stratified; pred with `seed`, gt with
@@ -38,12 +58,22 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=()):
     over both directions of the dot product between the sample's face normal and the unit normal of the closest face (signed; 0 for a
     closest face without area).  `fscore@tau` for every tau: 2 P R / (P + R) with P the share of pred_to_gt < tau and R the share of
     gt_to_pred < tau (0 when both are 0).  Reductions are torch's on fixed shapes, in double; two calls give identical numbers; the
-    results come to the host in one copy (the two index builds read their sizes on the way).  No alignment or scaling."""
+    results come to the host in one copy (the two index builds read their sizes on the way).
+
+    `align` = None: no alignment or scaling.  "rigid" / "similarity": pred is first taken onto gt by align.icp_align (keywords in
+    `align_opts`: samples, seed, iters, max_dist, tol, init), its vertices are replaced by Alignment.apply of them, and `alignment`
+    in the result carries matrix, scale, iterations, converged, rank, rms_before and rms_after.  An Alignment is applied as it is."""
     _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
     samples = int(samples)
     if samples <= 0:
         raise ValueError(f"samples > 0 expected, got {samples}")
-    a, b = sd.MeshIndex.build(pred[0], pred[1]), sd.MeshIndex.build(gt[0], gt[1])
+    found = None
+    if align is None:
+        a, b = sd.MeshIndex.build(pred[0], pred[1]), sd.MeshIndex.build(gt[0], gt[1])
+    else:
+        b = sd.MeshIndex.build(gt[0], gt[1])
+        found = _alignment(pred, b, align, align_opts)
+        a = sd.MeshIndex.build(found.apply(pred[0]), pred[1])
     for name, m in (("pred", a), ("gt", b)):
         if not m.area > 0:
             raise ValueError(f"surface_metrics: the {name} mesh has no area")
@@ -73,13 +103,21 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=()):
     for t in taus:
         p, r = pr[("P", t)] / samples, pr[("R", t)] / samples
         out[f"fscore@{t:g}"] = 2. * p * r / (p + r) if p + r > 0 else 0.
+    if found is not None:
+        out["alignment"] = found.summary()
     return out
 
 
-def vertex_to_surface(verts, gt):
-    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh."""
+def vertex_to_surface(verts, gt, align=None, align_opts=None, faces=None):
+    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh.  `align`
+    as in surface_metrics; "rigid" / "similarity" need the `faces` [F,3] of verts, whose surface is what gets aligned."""
     _lib.require_gpu(verts, gt[0], gt[1])
-    return sd.closest_point(verts, sd.MeshIndex.build(gt[0], gt[1]))[0]
+    index = sd.MeshIndex.build(gt[0], gt[1])
+    if align is not None:
+        if faces is None and not isinstance(align, al.Alignment):
+            raise ValueError("vertex_to_surface: estimating an alignment needs the faces of verts")
+        verts = _alignment((verts, faces), index, align, align_opts).apply(verts)
+    return sd.closest_point(verts, index)[0]
 
 
 def _to_device(mesh, device):
@@ -105,8 +143,10 @@ def _frame_ids(folder):
     return sorted(fids, key=lambda s: (0, int(s), s) if s.lstrip("-").isdigit() else (1, 0, s))
 
 
-def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, seed=0, taus=(), out=print):
-    """Folder mode (see the module text).  -> dict(frames: {fid: metrics}, skipped: [fid], summary)."""
+def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, seed=0, taus=(), out=print, align=None, align_opts=None,
+                    align_shared=False):
+    """Folder mode (see the module text).  -> dict(frames: {fid: metrics}, skipped: [fid], summary).  With `align_shared` the
+    alignment is estimated on the first compared frame and applied to every frame."""
     _, faces = read_ply(os.path.join(rec_root, "tmp.ply"))
     faces_d = torch.from_numpy(faces).to(device)
     fids = _frame_ids(os.path.join(rec_root, "meshs"))
@@ -119,7 +159,13 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
             skipped.append(fid)
             continue
         verts = torch.from_numpy(np.load(os.path.join(rec_root, "meshs", fid + ".npy")).astype(np.float32).reshape(-1, 3)).to(device)
-        per[fid] = surface_metrics((verts, faces_d), _to_device(read_mesh(gt_file), device), samples, seed, taus)
+        pred, gt = (verts, faces_d), _to_device(read_mesh(gt_file), device)
+        if align is None:
+            per[fid] = surface_metrics(pred, gt, samples, seed, taus)
+        else:
+            if align_shared and not isinstance(align, al.Alignment):
+                align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
+            per[fid] = surface_metrics(pred, gt, samples, seed, taus, align, align_opts)
         out("%4s: chamfer %.6f p2s %.6f" % (fid, per[fid]["chamfer"], per[fid]["p2s"]))
     out("%d frames compared, %d skipped (no ground-truth file)" % (len(per), len(skipped)))
     if not per:
@@ -138,7 +184,8 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
 def build_parser():
     parser = argparse.ArgumentParser(prog="python -m selfreconcode_amd.evaluate",
                                      description="Chamfer / P2S / normal consistency / F-score between triangle meshes on the GPU.  No alignment "
-                                                 "and no scaling is applied: both meshes are taken in the coordinates they are given.")
+                                                 "and no scaling is applied by default: both meshes are taken in the coordinates they are given.  "
+                                                 "--align first takes the predicted mesh onto the ground truth by point-to-plane ICP.")
     parser.add_argument("--gpu-ids", nargs="+", type=int, metavar="IDs", default=[0], help="gpu ids (the first is used)")
     parser.add_argument("--pred", default=None, metavar="A", help="mesh-pair mode: the predicted mesh (.ply / .obj)")
     parser.add_argument("--gt", default=None, metavar="B", help="mesh-pair mode: the ground-truth mesh (.ply / .obj)")
@@ -149,6 +196,13 @@ def build_parser():
     parser.add_argument("--seed", default=0, type=int, metavar="S", help="seed of the sampler")
     parser.add_argument("--tau", nargs="*", type=float, default=[], metavar="t", help="F-score thresholds, in the meshes' units")
     parser.add_argument("--out", default=None, metavar="FILE.json", help="mesh-pair mode: also write the metrics here")
+    parser.add_argument("--align", default="none", choices=("none",) + ALIGN_MODES,
+                        help="align the predicted mesh onto the ground truth first: rigid, or similarity (with a scale); ICP from matched centroids")
+    parser.add_argument("--align-samples", default=100_000, type=int, metavar="N", help="surface samples of the predicted mesh the alignment uses")
+    parser.add_argument("--align-iters", default=30, type=int, metavar="K", help="ICP iterations launched (they stop updating once converged)")
+    parser.add_argument("--align-max-dist", default=None, type=float, metavar="d", help="only pairs within this distance take part (default: all)")
+    parser.add_argument("--align-shared", action="store_true",
+                        help="folder mode: estimate the alignment on the first compared frame and use it for every frame (default: per frame)")
     return parser
 
 
@@ -167,20 +221,36 @@ def parse_args(argv=None):
         parser.error("folder mode needs both --rec-root and --gt-root")
     if args.samples <= 0:
         parser.error("--samples must be positive")
+    if args.align_samples <= 0 or args.align_iters <= 0:
+        parser.error("--align-samples and --align-iters must be positive")
+    if args.align_max_dist is not None and not args.align_max_dist >= 0:
+        parser.error("--align-max-dist must not be negative")
+    if args.align_shared and (args.align == "none" or not all(folder)):
+        parser.error("--align-shared needs folder mode and --align rigid or similarity")
     return args
+
+
+def _align_args(args):
+    """(align, align_opts) of surface_metrics from the parsed arguments."""
+    if args.align == "none":
+        return None, None
+    return args.align, {"samples": args.align_samples, "seed": args.seed, "iters": args.align_iters, "max_dist": args.align_max_dist}
 
 
 def main(argv=None, out=print):
     args = parse_args(argv)
     device = torch.device("cuda", args.gpu_ids[0])
+    align, align_opts = _align_args(args)
     if args.pred:
-        m = surface_metrics(_to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device), args.samples, args.seed, args.tau)
+        m = surface_metrics(_to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device), args.samples, args.seed, args.tau,
+                            align, align_opts)
         out(json.dumps(m))
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(m, fh, indent=1)
         return m
-    return evaluate_folder(args.rec_root, args.gt_root, device, args.frames, args.samples, args.seed, args.tau, out)
+    return evaluate_folder(args.rec_root, args.gt_root, device, args.frames, args.samples, args.seed, args.tau, out, align, align_opts,
+                           args.align_shared)
 
 
 if __name__ == "__main__":
