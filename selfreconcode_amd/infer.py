@@ -17,10 +17,11 @@ import os.path as osp
 import torch
 
 from .config import load_config
+from .posed import FULL_RATIO
+from .video import add_video_arguments, check_video_arguments
 
 # infer.py:47-53
 RESOLUTIONS = [(14 + 1, 20 + 1, 8 + 1), (28 + 1, 40 + 1, 16 + 1), (56 + 1, 80 + 1, 32 + 1), (112 + 1, 160 + 1, 64 + 1), (224 + 1, 320 + 1, 128 + 1)]
-RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
 
 
 def build_parser():
@@ -33,9 +34,7 @@ def build_parser():
     parser.add_argument('--nI', action='store_true', help='not save image')
     parser.add_argument('--C', action='store_true', help='overlay on gtimg')
     parser.add_argument('--nColor', action='store_true', help='not render images')
-    parser.add_argument('--video', action='store_true', help='write video.avi (Motion-JPEG) next to the images')
-    parser.add_argument('--fps', default=30., type=float, metavar='F', help='frame rate of the videos')
-    parser.add_argument('--video-quality', default=90, type=int, metavar='Q', help='JPEG quality of the videos, 1..100')
+    add_video_arguments(parser)
     return parser
 
 
@@ -48,8 +47,7 @@ def parse_args(parser, argv):
         parser.error('--video and --nV contradict each other')
     if args.nI and not args.video:
         parser.error('--nI: the images are all this command writes (videos are not written, see --nV)')
-    if args.video and not (1 <= args.video_quality <= 100 and args.fps > 0.):
-        parser.error('--video-quality must lie in 1..100 and --fps must be positive')
+    check_video_arguments(parser, args)
     return args
 
 
@@ -89,8 +87,8 @@ def infer(rec_root, device="cuda:0", batch_size=1, frames=-1, color=True, overla
     quality: see infer_export.export_frames."""
     from .infer_export import export_frames
     optNet, dataset, dataloader = load_network(rec_root, device, batch_size, out, resolutions)
-    TmpVs, Tmpfs = optNet.discretizeSDF(RATIO, None, 0.)
-    maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, RATIO, color=color, overlay=overlay,
+    TmpVs, Tmpfs = optNet.discretizeSDF(FULL_RATIO, None, 0.)
+    maskE = export_frames(optNet, TmpVs, Tmpfs, limited(dataloader, batch_size, frames, out, not color), rec_root, FULL_RATIO, color=color, overlay=overlay,
                           video=video, images=images, fps=fps, quality=quality)
     out('done')
     return maskE, TmpVs, Tmpfs, optNet

@@ -21,6 +21,9 @@ import zlib
 import numpy as np
 import torch
 
+from .mesh_io import write_ply
+from .video import FrameVideo
+
 
 def write_png(path, img):
     """8-bit PNG of a uint8 array [H,W] (grey), [H,W,3] (RGB) or [H,W,4] (RGBA), filter 0 on every row; standard library only."""
@@ -36,17 +39,6 @@ def write_png(path, img):
     with open(path, "wb") as fh:
         fh.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0))
                  + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
-
-
-def write_ply(path, verts, faces):
-    """ASCII PLY of a triangle mesh (verts [V,3] float, faces [F,3] int)."""
-    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
-    with open(path, "w") as fh:
-        fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
-        fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
-        fh.writelines("3 %d %d %d\n" % tuple(t) for t in f.tolist())
 
 
 def write_errors(path, maskE):
@@ -66,39 +58,6 @@ def write_errors(path, maskE):
 
 def _frame_count(dataset):
     return len(dataset) if hasattr(dataset, "__len__") else int(dataset.frame_num)
-
-
-class FrameVideo:
-    """`path` as a Motion-JPEG AVI of the uint8 RGB frames handed to add(): a frame that only exists on the host is uploaded, a batch
-    is encoded on the GPU (video.JpegEncoder) and appended.  Encoder and file are made at the first frame, whose size they take."""
-
-    def __init__(self, path, device, fps=30., quality=90):
-        self.path, self.device, self.fps, self.quality = path, torch.device(device), float(fps), quality
-        self.encoder = self.writer = None
-
-    def add(self, frames):
-        """frames [B,H,W,3] uint8: a GPU tensor, or anything np.ascontiguousarray takes."""
-        from .video import JpegEncoder, MjpegWriter
-        if not isinstance(frames, torch.Tensor):
-            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8))
-        frames = frames.to(self.device)
-        if self.encoder is None:
-            H, W = frames.shape[1:3]
-            self.encoder = JpegEncoder(H, W, self.quality, self.device, max_batch=frames.shape[0])
-            self.writer = MjpegWriter(self.path, W, H, self.fps)
-        for jpeg in self.encoder.encode(frames):
-            self.writer.write(jpeg)
-
-    def close(self):
-        if self.writer is not None:
-            self.writer.close()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 def export_frames(net, TmpVs, Tmpfs, batches, out_root, ratio, color=True, overlay=False, video=False, images=True, fps=30., quality=90):

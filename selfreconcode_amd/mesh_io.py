@@ -1,10 +1,10 @@
-"""Readers for the triangle meshes the evaluation compares (evaluate.py): PLY (ASCII and binary little-endian) and OBJ.  Standard
-library and numpy only.  The writer of `tmp.ply` is infer_export.write_ply."""
+"""Every mesh file of the package, on the standard library and numpy: PLY read (ASCII, binary little-endian) and written (ASCII), OBJ
+geometry as the evaluation takes it from anywhere (read_obj) and template/uvmap.obj, the OBJ with texture coordinates of the texture and
+render stages (read_obj_uv / write_obj_uv).  The OBJ readers stay two parsers: one streams, counts a negative index back from the vertices
+read so far and checks no range; the other counts from all `v` / `vt` lines, checks both ranges and demands a texture index."""
 import os
 
 import numpy as np
-
-from .infer_export import write_ply  # noqa: F401  (the writer that goes with read_ply)
 
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2", "uint16": "u2",
               "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4", "double": "f8", "float64": "f8"}
@@ -118,6 +118,17 @@ def read_ply(path):
     return verts, faces
 
 
+def write_ply(path, verts, faces):
+    """ASCII PLY of a triangle mesh (verts [V,3] float, faces [F,3] int)."""
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    with open(path, "w") as fh:
+        fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
+        fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+        fh.writelines("3 %d %d %d\n" % tuple(t) for t in f.tolist())
+
+
 def read_obj(path):
     """(verts [V,3] float64, faces [F,3] int64, 0-based) of a Wavefront OBJ: `v x y z ...` and `f` lines with corners `a`, `a/b`,
     `a//c` or `a/b/c`; a negative index counts back from the vertices read so far.  Everything else is skipped.  ValueError for a
@@ -141,6 +152,52 @@ def read_obj(path):
                     tri.append(i - 1 if i > 0 else len(verts) + i)
                 faces.append(tri)
     return np.asarray(verts, np.float64).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+
+
+def _obj_index(tok, n, what, line):
+    i = int(tok)
+    i = i - 1 if i > 0 else n + i
+    if not 0 <= i < n:
+        raise ValueError(f"{what} index {tok} out of range in '{line}'")
+    return i
+
+
+def read_obj_uv(path):
+    """(verts [V,3] float32, faces [F,3] int64, vt [Vt,2] float32, ft [F,3] int64) of a Wavefront OBJ with `v`, `vt` and triangular
+    `f a/b[/c]` lines (what template/uvmap.obj holds).  Faces with more than three corners or without texture indices raise."""
+    with open(path) as fh:
+        rows = [(ln.strip(), ln.split()) for ln in fh]
+    v = [[float(x) for x in tok[1:4]] for _, tok in rows if tok[:1] == ["v"]]
+    vt = [[float(x) for x in tok[1:3]] for _, tok in rows if tok[:1] == ["vt"]]
+    f, ft = [], []
+    for ln, tok in rows:
+        if tok[:1] != ["f"]:
+            continue
+        if len(tok) != 4:
+            raise ValueError(f"{path}: only triangles are supported, got '{ln}'")
+        a, b = [], []
+        for corner in tok[1:]:
+            parts = corner.split("/")
+            if len(parts) < 2 or not parts[1]:
+                raise ValueError(f"{path}: face corner without a texture index in '{ln}'")
+            a.append(_obj_index(parts[0], len(v), "vertex", ln)); b.append(_obj_index(parts[1], len(vt), "texture", ln))
+        f.append(a); ft.append(b)
+    if not v or not f or not vt:
+        raise ValueError(f"{path}: no vertices, texture coordinates or faces")
+    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3), np.asarray(vt, np.float32).reshape(-1, 2),
+            np.asarray(ft, np.int64).reshape(-1, 3))
+
+
+def write_obj_uv(path, verts, faces, vt, ft):
+    """The OBJ `read_obj_uv` reads: `v x y z`, `vt u v`, `f a/ta b/tb c/tc` (1-based)."""
+    v = np.asarray(verts, np.float32).reshape(-1, 3); t = np.asarray(vt, np.float32).reshape(-1, 2)
+    f = np.asarray(faces, np.int64).reshape(-1, 3); g = np.asarray(ft, np.int64).reshape(-1, 3)
+    if f.shape != g.shape:
+        raise ValueError(f"faces {f.shape} and ft {g.shape} must correspond one to one")
+    with open(path, "w") as fh:
+        fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+        fh.writelines("vt %.9g %.9g\n" % tuple(p) for p in t.tolist())
+        fh.writelines("f %d/%d %d/%d %d/%d\n" % (a[0] + 1, b[0] + 1, a[1] + 1, b[1] + 1, a[2] + 1, b[2] + 1) for a, b in zip(f.tolist(), g.tolist()))
 
 
 def read_mesh(path):

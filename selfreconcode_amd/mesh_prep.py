@@ -193,7 +193,8 @@ def prepare_template(net, out_root, ratio=None, target_faces=20000, resolution=1
 
     20000 faces is a default, not a measured optimum: at 1680^2 texels with about half of the atlas covered it leaves some 70 texels
     per face."""
-    from .texture import FULL_RATIO, write_obj_uv
+    from .mesh_io import write_obj_uv
+    from .posed import FULL_RATIO
     if TmpVs is None or Tmpfs is None:
         TmpVs, Tmpfs = net.discretizeSDF(ratio or FULL_RATIO, None, 0.)
     mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces)

@@ -31,6 +31,7 @@ from .. import step_ops
 from ..ext import MCGpu
 from ..ext.FastMinv import Fast3x3Minv
 from ..ops import singular_values_3x3, points_silhouette, rasterize_meshes, shade_phong, vertex_adjacency, vertex_normals
+from ..posed import mask_iou_error, pose_template, rasterize_posed, to_u8
 from ..utils import utils as U
 from ..utils.FindSurfacePs import FindSurfacePs, OptimizeSurfacePs
 from .CameraMine import RectifiedPerspectiveCameras
@@ -242,12 +243,9 @@ class OptimNetwork(nn.Module):
         cameras, H, W = self._cameras(N, device)
         if self.angThred is None:
             self.angThred = cameras.angThreshold(0.5)
+        defTmpVs, defconds, rendcond = pose_template(self, TmpVs, frame_ids, ratio)
+        frags, _ = rasterize_posed(defTmpVs, Tmpfs, cameras, H, W)
         with torch.no_grad():
-            poses, trans, d_cond, rendcond = [t.detach() for t in self.dataset.get_grad_parameters(frame_ids, device)]
-            defconds = [d_cond, [poses, trans]]
-            defTmpVs = self.deformer(TmpVs[None, :, :].expand(N, -1, 3), defconds, ratio=ratio)
-            xy, z = cameras.project_ndc(defTmpVs)
-            frags = rasterize_meshes(xy, z, Tmpfs, H, W)
             batch_inds, row_inds, col_inds, initTmpPs, _ = FindSurfacePs(TmpVs, Tmpfs, frags)
             rays = cameras.view_rays(torch.stack([col_inds, row_inds, torch.ones_like(col_inds)], dim=-1).float())
             cam_pos = cameras.cam_pos().detach()
@@ -286,31 +284,23 @@ class OptimNetwork(nn.Module):
             out = self.render_frames(frame_ids, ratio, TmpVs=TmpVs.detach(), Tmpfs=Tmpfs, chunk=10000, dthreshold=1.e-4, times=30, with_normals=False)
             masks, defV, frags = out['mask'], out['def_verts'], out['frags']
         else:
-            device = frame_ids.device
-            N = frame_ids.numel()
-            cameras, H, W = self._cameras(N, device)
-            with torch.no_grad():
-                poses, trans, d_cond, _ = [t.detach() for t in self.dataset.get_grad_parameters(frame_ids, device)]
-                defV = self.deformer(TmpVs.detach()[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio)
-                xy, z = cameras.project_ndc(defV)
-                frags = rasterize_meshes(xy, z, Tmpfs, H, W)
-                masks = (frags.pix_to_face[..., 0] >= 0).float()
-        N = masks.shape[0]
+            defV = pose_template(self, TmpVs, frame_ids, ratio)[0]
+            frags, _ = rasterize_posed(defV, Tmpfs, *self._cameras(frame_ids.numel(), frame_ids.device))
+            masks = (frags.pix_to_face[..., 0] >= 0).float()
         if gts:
-            gtMs = gts['mask'].to(masks.device)
-            gts['maskE'] = (1. - (masks * gtMs).view(N, -1).sum(1) / (masks + gtMs - masks * gtMs).abs().view(N, -1).sum(1)).cpu().numpy()
+            gts['maskE'] = mask_iou_error(masks, gts['mask'].to(masks.device)).cpu().numpy()
         defMeshVs = defV.detach().cpu().numpy()
         imgs = def1imgs = None
         if self.shaded_previews:
             imgs, def1imgs = self._shaded_previews(TmpVs.detach(), Tmpfs, ratio, frame_ids, defV.detach(), frags, gts)
         if not with_color:
             return None, imgs, def1imgs, defMeshVs
-        colors = torch.clamp((out['img'] / 2. + 0.5) * 255., min=0., max=255.)
+        colors = to_u8(out['img'] / 2. + 0.5)
         covered = masks > 0.
-        colors[~covered] = 255.
+        colors[~covered] = 255
         if gts and 'image' in gts:
-            colors[~covered] = gts['image'].to(colors.device)[~covered][:, :3] * 255.
-        return colors.cpu().numpy().astype(np.uint8), imgs, def1imgs, defMeshVs
+            colors[~covered] = to_u8(gts['image'].to(colors.device)[~covered][:, :3])
+        return colors.cpu().numpy(), imgs, def1imgs, defMeshVs
 
     def bake_texture(self, verts, faces, vt, ft, views, ratio=None, **kwargs):
         """The texture stage (texture_mesh_prepare.py + texture_mesh_extract.py) for a UV-mapped template: see texture.bake_texture."""
@@ -343,17 +333,16 @@ class OptimNetwork(nn.Module):
                 if 'image' in gts:
                     bg = frags.pix_to_face[..., 0] < 0
                     imgs[bg] = gts['image'].to(device)[bg][:, [2, 1, 0]]
-            imgs = torch.clamp(imgs * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
+            imgs = to_u8(imgs).cpu().numpy()
             d_cond = self.dataset.get_grad_parameters(frame_ids, device)[2].detach()
             canVs = self.deformer.defs[0](TmpVs[None, :, :].expand(N, -1, 3), d_cond, ratio=ratio)
             focals, princeple_ps = [t.detach() for t in self.dataset.get_camera_parameters(N, device)[:2]]
             newT = self.dataset.trans.detach().mean(0).to(device)
             R = torch.tensor([[-1., 0., 0.], [0., 1., 0.], [0., 0., -1.]], device=device)
             front = RectifiedPerspectiveCameras(focals, princeple_ps, R.expand(N, 3, 3), newT.expand(N, 3), image_size=[(W, H)])
-            xy, z = front.project_ndc(canVs)
             light = torch.stack([newT.new_zeros(()), newT.new_ones(()), newT[2]])
-            def1imgs = shade_phong(canVs, vertex_normals(canVs, Tmpfs, adj), Tmpfs, rasterize_meshes(xy, z, Tmpfs, H, W), front.cam_pos(), light)
-            def1imgs = torch.clamp(def1imgs * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
+            def1imgs = shade_phong(canVs, vertex_normals(canVs, Tmpfs, adj), Tmpfs, rasterize_posed(canVs, Tmpfs, front, H, W)[0], front.cam_pos(), light)
+            def1imgs = to_u8(def1imgs).cpu().numpy()
         return imgs, def1imgs
 
     def _cameras(self, N, device):

@@ -28,10 +28,11 @@ import numpy as np
 import torch
 
 from .infer_export import write_png
-from .ops import rasterize_meshes
+from .mesh_io import read_obj_uv
+from .posed import mask_iou_error, pose_template, rasterize_posed, to_u8
 from .render_ops import shade_textured, texture_face_lod, texture_mips
+from .video import FrameVideo, add_video_arguments, check_video_arguments
 
-FULL_RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
 MIN_COVERAGE = 0.25                  # a colour divided by less atlas coverage than this is left out of the image error
 PSNR_FLOOR = 1e-10                   # mean squared error floor: an exact match (or no compared pixel) reads 100 dB, not inf
 TURNTABLE_BATCH = 8
@@ -58,7 +59,6 @@ class TexturedAvatar:
         """The avatar the texture command left in `template_dir`: uvmap.obj, texture.png and tex_mask.png.  `valid` is tex_mask dilated
         as texture_ops.fill dilates it (a square window of int(0.1 R) texels, cv2.dilate's anchor): the region texture.png is filled in."""
         from PIL import Image
-        from .texture import read_obj_uv
         v, f, vt, ft = read_obj_uv(os.path.join(template_dir, 'uvmap.obj'))
         tex = np.asarray(Image.open(os.path.join(template_dir, 'texture.png')).convert('RGB'))
         mask = np.asarray(Image.open(os.path.join(template_dir, 'tex_mask.png')).convert('L'))
@@ -70,15 +70,13 @@ class TexturedAvatar:
                    torch.from_numpy(ft).to(device), torch.from_numpy(tex.copy()).to(device), valid)
 
     def render(self, def_verts, cameras, H, W, lod_bias=0., **shade_kwargs):
-        """def_verts [N,V,3] (the posed template) under `cameras`: project -> rasterize_meshes -> face lod -> shade_textured.
+        """def_verts [N,V,3] (the posed template) under `cameras`: posed.rasterize_posed -> face lod -> shade_textured.
         -> (rgba [N,H,W,4], frags, coverage [N,H,W]); `shade_kwargs`: background, hole, bg_image."""
         defV = def_verts.detach().contiguous().float()
         if defV.dim() != 3 or tuple(defV.shape[1:]) != tuple(self.verts.shape):
             raise ValueError(f"render: def_verts {tuple(def_verts.shape)} for a template of {self.verts.shape[0]} vertices")
+        frags, xy_pix = rasterize_posed(defV, self.faces, cameras, H, W, pixels=True)
         with torch.no_grad():
-            xy_ndc, z = cameras.project_ndc(defV)
-            frags = rasterize_meshes(xy_ndc, z, self.faces, H, W)
-            xy_pix, _ = cameras.project(defV)
             lod = texture_face_lod(xy_pix, self.faces, self.vt, self.ft, self.mips, lod_bias)
             rgba, coverage = shade_textured(frags, self.ft, self.vt, self.mips, lod, return_coverage=True, **shade_kwargs)
         return rgba, frags, coverage
@@ -102,12 +100,7 @@ def _dilate_square(mask, k):
 def pose(net, avatar, frame_ids, ratio=None):
     """The avatar's vertices posed for `frame_ids` by the trained deformer, as the texture bake poses them (all ratios 1 unless `ratio`
     is given) -> [N,V,3]."""
-    device = avatar.verts.device
-    fids = torch.as_tensor(frame_ids).long().to(device).reshape(-1)
-    N = fids.numel()
-    with torch.no_grad():
-        poses, trans, d_cond, _ = [t.detach() for t in net.dataset.get_grad_parameters(fids, device)]
-        return net.deformer(avatar.verts[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio or FULL_RATIO).detach().contiguous()
+    return pose_template(net, avatar.verts, torch.as_tensor(frame_ids).long().to(avatar.verts.device).reshape(-1), ratio)[0]
 
 
 def turntable_vertices(def_verts, K):
@@ -126,19 +119,8 @@ def turntable_vertices(def_verts, K):
     return torch.stack(out)
 
 
-def _u8(rgb):
-    return torch.clamp(rgb * 255., min=0., max=255.).cpu().numpy().astype(np.uint8)
-
-
-def _u8_device(rgb):
-    """_u8's bytes, left on the GPU (the float -> uint8 conversion truncates on both sides)."""
-    return torch.clamp(rgb * 255., min=0., max=255.).to(torch.uint8)
-
-
 def _film(video, path, device, fps, quality):
-    """The FrameVideo at `path` as a context (closed on the way out), or a context of None without `video`."""
-    from .infer_export import FrameVideo
-    return FrameVideo(path, device, fps, quality) if video else contextlib.nullcontext()
+    return contextlib.closing(FrameVideo(path, device, fps, quality)) if video else contextlib.nullcontext()
 
 
 def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, turntable_frame=None, ratio=None, lod_bias=0., video=False,
@@ -165,16 +147,16 @@ def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, 
             rgba, frags, coverage = avatar.render(defV, cameras, H, W, lod_bias=lod_bias, bg_image=image.contiguous() if overlay else None)
             rgb = rgba[..., :3]
             covered = frags.pix_to_face[..., 0] >= 0
-            sil = covered.float()
-            maskE = 1. - (sil * gtM).view(N, -1).sum(1) / (sil + gtM - sil * gtM).abs().view(N, -1).sum(1)
+            maskE = mask_iou_error(covered.float(), gtM)
             use = (covered & (gtM > 0.5) & (coverage >= MIN_COVERAGE)).float()[..., None]
             n = (3. * use.view(N, -1).sum(1)).clamp(min=1.)
             diff = (rgb.clamp(0., 1.) - image) * use
             l1 = diff.abs().view(N, -1).sum(1) / n
             psnr = 10. * torch.log10(1. / (diff.square().view(N, -1).sum(1) / n).clamp(min=PSNR_FLOOR))
-            pixels = _u8(rgb)
+            pixels = to_u8(rgb)
             if film is not None:
-                film.add(_u8_device(rgb))
+                film.add(pixels)
+            pixels = pixels.cpu().numpy()
             for i, fid in enumerate(fids.tolist()):
                 write_png(os.path.join(folder, '%d.png' % fid), pixels[i])
                 errors[fid] = (float(l1[i]), float(psnr[i]), float(maskE[i]))
@@ -197,9 +179,10 @@ def export_textured(net, avatar, batches, out_root, overlay=False, turntable=0, 
                 chunk = views[k0:k0 + TURNTABLE_BATCH]
                 cameras, H, W = net._cameras(chunk.shape[0], device)
                 rgb = avatar.render(chunk, cameras, H, W, lod_bias=lod_bias)[0][..., :3]
-                pixels = _u8(rgb)
+                pixels = to_u8(rgb)
                 if film is not None:
-                    film.add(_u8_device(rgb))
+                    film.add(pixels)
+                pixels = pixels.cpu().numpy()
                 for i in range(chunk.shape[0]):
                     write_png(os.path.join(out_root, 'turntable', '%d.png' % (k0 + i)), pixels[i])
     return errors
@@ -215,9 +198,7 @@ def build_parser():
     parser.add_argument('--turntable-frame', default=None, type=int, metavar='F', help='the frame the turntable turns (default: the first one rendered)')
     parser.add_argument('--C', action='store_true', help='overlay on gtimg')
     parser.add_argument('--lod-bias', default=0., type=float, metavar='b', help='added to every level of detail (negative: sharper)')
-    parser.add_argument('--video', action='store_true', help='write textured/video.avi and turntable/video.avi (Motion-JPEG)')
-    parser.add_argument('--fps', default=30., type=float, metavar='F', help='frame rate of the videos')
-    parser.add_argument('--video-quality', default=90, type=int, metavar='Q', help='JPEG quality of the videos, 1..100')
+    add_video_arguments(parser, help='write textured/video.avi and turntable/video.avi (Motion-JPEG)')
     return parser
 
 
@@ -229,8 +210,7 @@ def main(argv=None, out=print, resolutions=None):
     args = parser.parse_args(argv)
     if args.rec_root is None:
         parser.error('--rec-root is required')
-    if args.video and not (1 <= args.video_quality <= 100 and args.fps > 0.):
-        parser.error('--video-quality must lie in 1..100 and --fps must be positive')
+    check_video_arguments(parser, args)
     folder = os.path.join(args.rec_root, 'template')
     for name in ('uvmap.obj', 'texture.png', 'tex_mask.png'):
         if not os.path.isfile(os.path.join(folder, name)):

@@ -34,10 +34,10 @@ import numpy as np
 import torch
 
 from .infer_export import write_png
-from .ops import rasterize_meshes, vertex_adjacency, vertex_normals
+from .mesh_io import read_obj_uv
+from .ops import vertex_adjacency, vertex_normals
+from .posed import pose_template, rasterize_posed, to_u8
 from .texture_ops import TextureAccumulator, face_visibility, fill, uv_texel_map, view_alpha
-
-FULL_RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
 
 BakedTexture = namedtuple("BakedTexture", "tex_mask mask_final count view_id tex_median texture fids def_verts")
 
@@ -45,59 +45,6 @@ BakedTexture = namedtuple("BakedTexture", "tex_mask mask_final count view_id tex
 def texture_frames(frame_num, num=120):
     """The frame ids texture_mesh_prepare.py:81 bakes from: `num` ids spread over `frame_num` frames."""
     return np.ceil(np.arange(int(num)) * int(frame_num) * 1. / int(num)).astype(np.int64)
-
-
-def _obj_index(tok, n, what, line):
-    i = int(tok)
-    i = i - 1 if i > 0 else n + i
-    if not 0 <= i < n:
-        raise ValueError(f"{what} index {tok} out of range in '{line}'")
-    return i
-
-
-def read_obj_uv(path):
-    """(verts [V,3] float32, faces [F,3] int64, vt [Vt,2] float32, ft [F,3] int64) of a Wavefront OBJ with `v`, `vt` and triangular
-    `f a/b[/c]` lines (what template/uvmap.obj holds).  Faces with more than three corners or without texture indices raise."""
-    v, vt, f, ft = [], [], [], []
-    with open(path) as fh:
-        lines = [ln.strip() for ln in fh]
-    for ln in lines:
-        tok = ln.split()
-        if not tok or tok[0] not in ("v", "vt", "f"):
-            continue
-        if tok[0] == "v":
-            v.append([float(x) for x in tok[1:4]])
-        elif tok[0] == "vt":
-            vt.append([float(x) for x in tok[1:3]])
-    for ln in lines:
-        tok = ln.split()
-        if not tok or tok[0] != "f":
-            continue
-        if len(tok) != 4:
-            raise ValueError(f"{path}: only triangles are supported, got '{ln}'")
-        a, b = [], []
-        for corner in tok[1:]:
-            parts = corner.split("/")
-            if len(parts) < 2 or not parts[1]:
-                raise ValueError(f"{path}: face corner without a texture index in '{ln}'")
-            a.append(_obj_index(parts[0], len(v), "vertex", ln)); b.append(_obj_index(parts[1], len(vt), "texture", ln))
-        f.append(a); ft.append(b)
-    if not v or not f or not vt:
-        raise ValueError(f"{path}: no vertices, texture coordinates or faces")
-    return (np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int64).reshape(-1, 3), np.asarray(vt, np.float32).reshape(-1, 2),
-            np.asarray(ft, np.int64).reshape(-1, 3))
-
-
-def write_obj_uv(path, verts, faces, vt, ft):
-    """The OBJ `read_obj_uv` reads: `v x y z`, `vt u v`, `f a/ta b/tb c/tc` (1-based)."""
-    v = np.asarray(verts, np.float32).reshape(-1, 3); t = np.asarray(vt, np.float32).reshape(-1, 2)
-    f = np.asarray(faces, np.int64).reshape(-1, 3); g = np.asarray(ft, np.int64).reshape(-1, 3)
-    if f.shape != g.shape:
-        raise ValueError(f"faces {f.shape} and ft {g.shape} must correspond one to one")
-    with open(path, "w") as fh:
-        fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
-        fh.writelines("vt %.9g %.9g\n" % tuple(p) for p in t.tolist())
-        fh.writelines("f %d/%d %d/%d %d/%d\n" % (a[0] + 1, b[0] + 1, a[1] + 1, b[1] + 1, a[2] + 1, b[2] + 1) for a, b in zip(f.tolist(), g.tolist()))
 
 
 def _bake_batch(net, acc, adj, verts, faces, ratio, batch):
@@ -109,12 +56,9 @@ def _bake_batch(net, acc, adj, verts, faces, ratio, batch):
     cameras, H, W = net._cameras(N, device)
     if tuple(images.shape) != (N, H, W, 3) or tuple(masks.shape) != (N, H, W):
         raise ValueError(f"bake_texture: images {tuple(images.shape)} / masks {tuple(masks.shape)} for the dataset's {H} x {W} camera")
+    defV = pose_template(net, verts, fids, ratio)[0]
+    frags, xy_pix = rasterize_posed(defV, faces, cameras, H, W, pixels=True)
     with torch.no_grad():
-        poses, trans, d_cond, _ = [t.detach() for t in net.dataset.get_grad_parameters(fids, device)]
-        defV = net.deformer(verts[None, :, :].expand(N, -1, 3), [d_cond, [poses, trans]], ratio=ratio).detach().contiguous()
-        xy_ndc, z = cameras.project_ndc(defV)
-        frags = rasterize_meshes(xy_ndc, z, faces, H, W)
-        xy_pix, _ = cameras.project(defV)
         alpha = view_alpha(defV, vertex_normals(defV, faces, adj), cameras.cam_pos().detach())
         visible = face_visibility(frags.pix_to_face[..., 0], faces, xy_pix, masks)
         acc.accumulate(fids, visible, alpha, xy_pix, images)
@@ -129,7 +73,6 @@ def bake_texture(net, verts, faces, vt, ft, views, ratio=None, resolution=1680, 
     mask_final [R,R] bool, count, view_id [R,R] int32, tex_median, texture [R,R,3] float32, fids [K], def_verts [K,V,3]."""
     from . import _lib
     _lib.require_gpu(verts, faces, vt, ft)
-    ratio = ratio or FULL_RATIO
     verts = verts.detach().contiguous().float()
     faces = faces.long().contiguous()
     if tuple(ft.shape) != tuple(faces.shape):
@@ -156,10 +99,6 @@ def bake_texture(net, verts, faces, vt, ft, views, ratio=None, resolution=1680, 
                         res.tex_median.cpu().numpy(), texture.cpu().numpy(), np.asarray(fids, np.int64), torch.cat(defVs).numpy())
 
 
-def _u8(x):
-    return np.uint8(np.clip(np.asarray(x, np.float32), 0., 1.) * 255)
-
-
 def export_texture(net, obj_path, views, out_root, ratio=None, resolution=1680, agg_num=50, normal_ang=68., check_num=5, device=None):
     """texture_mesh_prepare.py + texture_mesh_extract.py: reads the UV-mapped template `obj_path` (template/uvmap.obj), bakes it from
     `views` (see bake_texture) and writes tex_mask.png, mask_final.png, tex_median.png, texture.png, view_id.npy and tex_predata.npz under
@@ -169,10 +108,8 @@ def export_texture(net, obj_path, views, out_root, ratio=None, resolution=1680, 
     baked = bake_texture(net, torch.from_numpy(v).to(device), torch.from_numpy(f).to(device), torch.from_numpy(vt).to(device),
                          torch.from_numpy(ft).to(device), views, ratio, resolution, agg_num, normal_ang, check_num)
     os.makedirs(out_root, exist_ok=True)
-    write_png(os.path.join(out_root, "tex_mask.png"), _u8(baked.tex_mask))
-    write_png(os.path.join(out_root, "mask_final.png"), _u8(baked.mask_final))
-    write_png(os.path.join(out_root, "tex_median.png"), _u8(baked.tex_median))
-    write_png(os.path.join(out_root, "texture.png"), _u8(baked.texture))
+    for name in ("tex_mask", "mask_final", "tex_median", "texture"):                               # uint8(x 255) of the values clipped to [0, 1]
+        write_png(os.path.join(out_root, name + ".png"), to_u8(getattr(baked, name)).numpy())
     np.save(os.path.join(out_root, "view_id.npy"), baked.view_id)
     np.savez(os.path.join(out_root, "tex_predata.npz"), vt=vt, ft=ft, tmpvs=v, fs=f, defVs=baked.def_verts, fids=baked.fids)
     return baked

@@ -264,7 +264,7 @@ def train(data_root, conf, save_folder, device="cuda:0", model=None, sdf_model=N
     from . import mlp_engine
     from .MCAcc import Seg3dLossless
     from .dataset import getDatasetAndLoader
-    from .infer_export import write_ply
+    from .mesh_io import write_ply
     from .model import getOptNet
     from .optim import FusedAdam
     from .utils.checkpoint import load_model, save_model, set_hierarchical_config

@@ -6,10 +6,14 @@ writer on the standard library.
         for jpeg in enc.encode(frames_u8):          # frames_u8 [B,H,W,3] uint8 RGB on the GPU -> B stand-alone JFIF files
             avi.write(jpeg)
 
+`FrameVideo` is that pair behind one add() for batches of frames from the GPU or the host; `add_video_arguments` / `check_video_arguments`
+are the switches of the commands that write videos (infer, render).
+
 The reference writes `.mp4` (mp4v) through cv2; `.avi` with the MJPG codec is what stands in for it here.
 """
 import struct
 
+import numpy as np
 import torch
 
 from . import video_ops
@@ -144,6 +148,44 @@ class MjpegWriter:
     def __exit__(self, *exc):
         self.close()
         return False
+
+
+class FrameVideo:
+    """`path` as a Motion-JPEG AVI of the uint8 RGB frames handed to add(): a frame that only exists on the host is uploaded, a batch
+    is encoded on the GPU (JpegEncoder) and appended.  Encoder and file are made at the first frame, whose size they take."""
+
+    def __init__(self, path, device, fps=30., quality=90):
+        self.path, self.device, self.fps, self.quality = path, torch.device(device), float(fps), quality
+        self.encoder = self.writer = None
+
+    def add(self, frames):
+        """frames [B,H,W,3] uint8: a GPU tensor, or anything np.ascontiguousarray takes."""
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.from_numpy(np.ascontiguousarray(frames, dtype=np.uint8))
+        frames = frames.to(self.device)
+        if self.encoder is None:
+            H, W = frames.shape[1:3]
+            self.encoder = JpegEncoder(H, W, self.quality, self.device, max_batch=frames.shape[0])
+            self.writer = MjpegWriter(self.path, W, H, self.fps)
+        for jpeg in self.encoder.encode(frames):
+            self.writer.write(jpeg)
+
+    def close(self):
+        if self.writer is not None:
+            self.writer.close()
+
+
+def add_video_arguments(parser, help='write video.avi (Motion-JPEG) next to the images'):
+    """--video, --fps and --video-quality as every command that writes videos takes them; `help` is --video's."""
+    parser.add_argument('--video', action='store_true', help=help)
+    parser.add_argument('--fps', default=30., type=float, metavar='F', help='frame rate of the videos')
+    parser.add_argument('--video-quality', default=90, type=int, metavar='Q', help='JPEG quality of the videos, 1..100')
+
+
+def check_video_arguments(parser, args):
+    """The parser's error exit for a --video with a quality or a frame rate no video can have."""
+    if args.video and not (1 <= args.video_quality <= 100 and args.fps > 0.):
+        parser.error('--video-quality must lie in 1..100 and --fps must be positive')
 
 
 def encode_video(path, frames_u8, fps=30., quality=90):

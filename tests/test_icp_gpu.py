@@ -351,7 +351,7 @@ def test_surface_metrics_with_alignment():
 
 
 def _write_folder(tmp_path):
-    from selfreconcode_amd.infer_export import write_ply
+    from selfreconcode_amd.mesh_io import write_ply
     pred, gt, answer = _case("rigid", 8)
     rec, gtd = tmp_path / "result", tmp_path / "gt"
     os.makedirs(rec / "meshs")
@@ -366,7 +366,7 @@ def _write_folder(tmp_path):
 
 def test_command_with_alignment(tmp_path):
     from selfreconcode_amd import evaluate
-    from selfreconcode_amd.infer_export import write_ply
+    from selfreconcode_amd.mesh_io import write_ply
     pred, gt, answer = _case("similarity", 8)
     scale = float(np.abs(gt[0]).max())
     a, b, out = str(tmp_path / "a.ply"), str(tmp_path / "b.ply"), str(tmp_path / "m.json")

@@ -30,9 +30,9 @@ def direct(tmp_path_factory):
     """export_frames called directly, without and with colours, on a network put together as infer.py does it."""
     from selfreconcode_amd.config import load_config
     from selfreconcode_amd.dataset import getDatasetAndLoader
-    from selfreconcode_amd.infer import RATIO
     from selfreconcode_amd.infer_export import export_frames
     from selfreconcode_amd.model import getOptNet
+    from selfreconcode_amd.posed import FULL_RATIO as RATIO
     from selfreconcode_amd.utils.checkpoint import load_model
     root, first = ts.folder(tmp_path_factory)
     conf = load_config(os.path.join(first.save_root, 'config.conf'))

@@ -33,7 +33,7 @@ def test_png_round_trip_odd_sizes(tmp_path):
 
 
 def test_ply_parses_back(tmp_path):
-    from selfreconcode_amd.infer_export import write_ply
+    from selfreconcode_amd.mesh_io import write_ply
     rng = np.random.default_rng(3)
     v = rng.standard_normal((7, 3)).astype(np.float32)
     f = rng.integers(0, 7, (5, 3))

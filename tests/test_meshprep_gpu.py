@@ -252,7 +252,8 @@ def test_prepare_template_into_export_texture(tmp_path):
     import _texture_ref as tr
     from selfreconcode_amd.mesh_prep import prepare_template
     from selfreconcode_amd.synthetic import build_synthetic_scene
-    from selfreconcode_amd.texture import export_texture, read_obj_uv, texture_frames
+    from selfreconcode_amd.mesh_io import read_obj_uv
+    from selfreconcode_amd.texture import export_texture, texture_frames
     from selfreconcode_amd.texture_ops import uv_texel_map
     H = W = 96
     R = 256

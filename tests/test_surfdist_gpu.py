@@ -344,7 +344,7 @@ def test_surface_metrics_vs_restatement_and_closed_form():
 
 def test_command_mesh_pair_mode(tmp_path):
     from selfreconcode_amd import evaluate
-    from selfreconcode_amd.infer_export import write_ply
+    from selfreconcode_amd.mesh_io import write_ply
     from selfreconcode_amd.synthetic import icosphere
     v, f = [x.numpy() for x in icosphere(2)]
     a, b, out = str(tmp_path / "a.ply"), str(tmp_path / "b.ply"), str(tmp_path / "m.json")
@@ -360,7 +360,7 @@ def test_command_mesh_pair_mode(tmp_path):
 
 def test_command_folder_mode(tmp_path):
     from selfreconcode_amd import evaluate
-    from selfreconcode_amd.infer_export import write_ply
+    from selfreconcode_amd.mesh_io import write_ply
     from selfreconcode_amd.synthetic import icosphere
     v, f = [x.numpy() for x in icosphere(2)]
     rec, gt = tmp_path / "result", tmp_path / "gt"

@@ -299,7 +299,7 @@ def test_from_folder_round_trips(tmp_path, R):
     from selfreconcode_amd.infer_export import write_png
     from selfreconcode_amd.render import TexturedAvatar
     from selfreconcode_amd.render_ops import texture_mips
-    from selfreconcode_amd.texture import write_obj_uv
+    from selfreconcode_amd.mesh_io import write_obj_uv
     rng = np.random.default_rng(9)
     verts, faces, vt, ft = _quad()
     tex = rng.integers(0, 256, (R, R, 3), dtype=np.uint8)

@@ -35,7 +35,7 @@ def _snapshot(root, skip=None):
 
 def test_texture_command_makes_reuses_and_stays_in_its_folder(tmp_path_factory):
     from selfreconcode_amd import texture
-    from selfreconcode_amd.texture import read_obj_uv
+    from selfreconcode_amd.mesh_io import read_obj_uv
     capture, first = ts.folder(tmp_path_factory)
     rec_root = first.save_root
     folder = os.path.join(rec_root, 'template')

@@ -18,7 +18,7 @@ def test_texture_frames_formula(num, frame_num):
 
 def test_obj_round_trip_and_refusals(tmp_path):
     from selfreconcode_amd.synthetic import icosphere, per_face_atlas
-    from selfreconcode_amd.texture import read_obj_uv, write_obj_uv
+    from selfreconcode_amd.mesh_io import read_obj_uv, write_obj_uv
     v, f = icosphere(1)
     vt, ft = per_face_atlas(len(f), 256, 0.5)
     p = str(tmp_path / "uvmap.obj")

@@ -229,7 +229,8 @@ RATIO = {'sdfRatio': 1., 'deformerRatio': 1., 'renderRatio': 1.}
 
 def test_export_texture_files_and_reproducibility(tmp_path):
     from selfreconcode_amd.synthetic import build_synthetic_scene, per_face_atlas
-    from selfreconcode_amd.texture import export_texture, texture_frames, write_obj_uv
+    from selfreconcode_amd.mesh_io import write_obj_uv
+    from selfreconcode_amd.texture import export_texture, texture_frames
     H = W = 96
     R = 256
     torch.manual_seed(0)

@@ -50,7 +50,8 @@ def main():
     args = ap.parse_args()
     from selfreconcode_amd.ops import rasterize_meshes, vertex_adjacency, vertex_normals
     from selfreconcode_amd.synthetic import build_synthetic_scene, per_face_atlas
-    from selfreconcode_amd.texture import FULL_RATIO, bake_texture, texture_frames
+    from selfreconcode_amd.posed import FULL_RATIO
+    from selfreconcode_amd.texture import bake_texture, texture_frames
     from selfreconcode_amd.texture_ops import TextureAccumulator, face_visibility, fill, uv_texel_map, view_alpha
     dev = "cuda:0"
     K, R, H = args.views, args.resolution, args.image
