@@ -652,6 +652,41 @@ int sr_smpl_pose(const float* theta, float* Rs, const float* J, const int32_t* h
 int sr_smpl_skin(const float* rest, int64_t rest_batch_stride, const float* posedirs, const float* feature, const float* weights, const float* A,
                  int32_t B, int64_t nv, float* verts, void* stream);
 
+/* SMPL body model, backward, float32 (csrc/smpl_grad.hip): the adjoints of the four stages above, shapes and limits as there.  No float
+ * atomics; every sum has an order fixed by the shapes, so two calls give identical bits.  A g* argument is the cotangent of the
+ * tensor it names.
+ *   sr_smpl_regress_bwd: g_x [B,nv,3] = sum_k reg [nv,nk] g_out [B,nk,3] (nk <= 42); accumulate != 0 adds to g_x instead.
+ *   sr_smpl_shape_bwd:   g_beta [B,nbeta] = sum_e shapedirs [nbeta, nv*3] g_vshaped [B, nv*3], nbeta <= 32; `partial` holds
+ *     sr_smpl_shape_bwd_workspace_floats floats (one row per 2048 elements, added in ascending order by a second launch).
+ *   sr_smpl_skin_bwd:    from gV [B,nv,3]: g_rest [B,nv,3] = (sum_j w_vj R_j)^T gV (R_j: the 3x3 of A[b,j]), gA [B,24,12] (rows 0..2 of
+ *     each 4x4) = sum_v w_vj gV_v (x) [v_posed_v; 1] with v_posed recomputed as in sr_smpl_skin, and with posedirs
+ *     g_feature [B,207] = sum_{v,c} posedirs[p,v,c] g_rest[b,v,c] (posedirs, feature and g_feature all NULL: v_posed = rest).
+ *     `partial` holds sr_smpl_skin_bwd_workspace_floats floats: one row per batch item and 128 vertices, added in ascending order by
+ *     a second launch.  posedirs is read once per SR_SMPL_BATCH_TILE batch items.
+ *   sr_smpl_pose_bwd:    the reverse of sr_smpl_pose, from gA [B,24,12], gJ_transformed [B,24,3], g_feature [B,207] and gRs [B,24,3,3]
+ *     (each may be NULL = zero); Rs and A are sr_smpl_pose's outputs.  -> gJ [B,24,3], and g_theta [B,24,3] through the axis-angle
+ *     route as written (the +1e-8 included), or with theta NULL gRs_out [B,24,3,3]. */
+int sr_smpl_regress_bwd(const float* g_out, const float* reg, int32_t B, int64_t nv, int32_t nk, int32_t accumulate, float* g_x, void* stream);
+int64_t sr_smpl_shape_bwd_workspace_floats(int32_t B, int32_t nbeta, int64_t nv);
+int sr_smpl_shape_bwd(const float* shapedirs, const float* g_vshaped, int32_t B, int32_t nbeta, int64_t nv, float* partial, float* g_beta,
+                      void* stream);
+int64_t sr_smpl_skin_bwd_workspace_floats(int32_t B, int64_t nv);
+int sr_smpl_skin_bwd(const float* rest, int64_t rest_batch_stride, const float* posedirs, const float* feature, const float* weights,
+                     const float* A, const float* gV, int32_t B, int64_t nv, float* partial, float* g_rest, float* gA, float* g_feature,
+                     void* stream);
+int sr_smpl_pose_bwd(const float* theta, const float* Rs, const float* J, const float* A, const int32_t* host_parents, int32_t B,
+                     const float* gA, const float* gJ_transformed, const float* g_feature, const float* gRs, float* g_theta, float* gRs_out,
+                     float* gJ, void* stream);
+
+/* Keypoint data term of smpl_fit.py (csrc/smpl_grad.hip), value and gradient in one launch: for frame t < T and joint k < K <= 64,
+ * p = joints [T,K,3] + trans [T,3] is projected as RectifiedPerspectiveCameras.project does (pc = p R + T, x = cx - fx pc_x / pc_z,
+ * y = cy - fy pc_y / pc_z) and contributes (w_k c_tk)^2 sigma^2 r^2 / (sigma^2 + r^2), r the pixel distance to kp [T,K,3] = (x, y, c).
+ * A joint with c = 0 or a non-finite target contributes nothing; one with pc_z <= 0 contributes nothing and is counted in behind [T].
+ * host_camera: 16 HOST floats R [3,3], T [3], fx, fy, cx, cy (passed by value to the kernel).  -> energy [T], g_joints [T,K,3],
+ * g_trans [T,3] (the gradients of energy[t]); the sums over k run in ascending order. */
+int sr_keypoint_energy(const float* joints, const float* trans, const float* kp, const float* joint_weights, const float* host_camera,
+                       float sigma, int32_t T, int32_t K, float* energy, float* g_joints, float* g_trans, int32_t* behind, void* stream);
+
 /* Mesh regularisers of the template step (csrc/mesh_reg.hip): mesh_laplacian_smoothing(method='uniform'), mesh_edge_loss and
  * mesh_normal_consistency of pytorch3d 0.4.0 as model/network.py:655-670 calls them, restated, on one mesh of V vertices.
  * Topology, int32, built once per remesh by mesh_losses.MeshTopology: nbr_row [V+1] / nbr [2E] the neighbour CSR (ascending per row),

@@ -270,6 +270,13 @@ SIGNATURES = {
     "sr_smpl_regress": [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, _vp],
     "sr_smpl_pose": [_vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
     "sr_smpl_skin": [_vp, _i64, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp],
+    "sr_smpl_regress_bwd": [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
+    "sr_smpl_shape_bwd_workspace_floats": [ctypes.c_int32, ctypes.c_int32, _i64],
+    "sr_smpl_shape_bwd": [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _vp, _vp],
+    "sr_smpl_skin_bwd_workspace_floats": [ctypes.c_int32, _i64],
+    "sr_smpl_skin_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp, _vp, _vp, _vp],
+    "sr_smpl_pose_bwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sr_keypoint_energy": [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp],
     "sr_meshreg_workspace_bytes": [_i64, _i64],
     "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
     "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,
@@ -290,7 +297,8 @@ SIGNATURES = {
     "sr_icp_solve": [_vp, ctypes.c_int32] + [ctypes.c_double] * 4 + [ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
 }
 _RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64,
-            "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64, "sr_smpl_regress_workspace_floats": _i64}
+            "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64, "sr_smpl_regress_workspace_floats": _i64,
+            "sr_smpl_shape_bwd_workspace_floats": _i64, "sr_smpl_skin_bwd_workspace_floats": _i64}
 
 _fn = {}
 for _name, _args in SIGNATURES.items():

@@ -1,5 +1,5 @@
 // Axis-angle -> rotation matrix (row major) through the half-angle quaternion, +1e-8 inside the norm (smpl_pytorch/util.py:35-78), on a
-// scalar type S: float, or the forward-mode dual number of csrc/lbs.hip with its own rot_sqrt / rot_sin / rot_cos and S{constant}.
+// scalar type S: float, or the forward-mode dual number of rot_dual.h with its own rot_sqrt / rot_sin / rot_cos and S{constant}.
 #pragma once
 #include "sr_common.h"
 

@@ -279,6 +279,93 @@ def smpl_skin(rest, weights, A, posedirs=None, feature=None):
     return verts
 
 
+# ------------------------------------------------------------------ SMPL body model, backward (csrc/smpl_grad.hip)
+def smpl_regress_bwd(g_out, reg, out=None):
+    """g_x [B,nv,3] = sum_k reg [nv,nk] g_out [B,nk,3] (sr_smpl_regress_bwd); with `out` the sum is added to it and it is returned."""
+    _lib.require_gpu(g_out, reg, out)
+    B, (nv, nk) = g_out.shape[0], reg.shape
+    _smpl_f32(g_out, (B, nk, 3), "joint cotangent"); _smpl_f32(reg, (nv, nk), "regressor")
+    if out is None:
+        g_x, accumulate = torch.empty((B, nv, 3), dtype=torch.float32, device=g_out.device), 0
+    else:
+        g_x, accumulate = _smpl_f32(out, (B, nv, 3), "accumulated cotangent"), 1
+    _lib.launch("sr_smpl_regress_bwd", g_out, g_out, reg, B, nv, nk, accumulate, g_x)
+    return g_x
+
+
+def smpl_shape_bwd(shapedirs, g_vshaped):
+    """g_beta [B,nbeta] = sum_e shapedirs [nbeta, nv*3] g_vshaped [B,nv,3] in a fixed order (sr_smpl_shape_bwd)."""
+    _lib.require_gpu(shapedirs, g_vshaped)
+    nbeta, (B, nv) = shapedirs.shape[0], g_vshaped.shape[:2]
+    _smpl_f32(shapedirs, (nbeta, 3 * nv), "shapedirs"); _smpl_f32(g_vshaped, (B, nv, 3), "v_shaped cotangent")
+    partial = _lib.workspace("sr_smpl_shape_bwd_workspace_floats", B, nbeta, nv, device=g_vshaped.device, dtype=torch.float32)
+    g_beta = torch.empty((B, nbeta), dtype=torch.float32, device=g_vshaped.device)
+    _lib.launch("sr_smpl_shape_bwd", g_vshaped, shapedirs, g_vshaped, B, nbeta, nv, partial, g_beta)
+    return g_beta
+
+
+def smpl_skin_bwd(rest, weights, A, gV, posedirs=None, feature=None):
+    """(g_rest [B,nv,3], gA [B,24,12], g_feature [B,207] or None) of smpl_skin's arguments from the cotangent gV [B,nv,3] of its
+    result (sr_smpl_skin_bwd).  g_rest is per batch item also when `rest` [nv,3] is shared: its cotangent is g_rest.sum(0)."""
+    _lib.require_gpu(rest, weights, A, gV, posedirs, feature)
+    B, nv = A.shape[0], weights.shape[0]
+    _smpl_f32(A, (B, SMPL_NJ, 4, 4), "A"); _smpl_f32(weights, (nv, SMPL_NJ), "weight"); _smpl_f32(gV, (B, nv, 3), "vertex cotangent")
+    if rest.dim() == 2:
+        _smpl_f32(rest, (nv, 3), "rest vertices"); stride = 0
+    else:
+        _smpl_f32(rest, (B, nv, 3), "rest vertices"); stride = 3 * nv
+    g_feature = None
+    if posedirs is not None:
+        _smpl_f32(posedirs, (SMPL_NPOSE, 3 * nv), "posedirs"); _smpl_f32(feature, (B, SMPL_NPOSE), "pose feature")
+        g_feature = torch.empty((B, SMPL_NPOSE), dtype=torch.float32, device=A.device)
+    partial = _lib.workspace("sr_smpl_skin_bwd_workspace_floats", B, nv, device=A.device, dtype=torch.float32)
+    g_rest = torch.empty((B, nv, 3), dtype=torch.float32, device=A.device)
+    gA = torch.empty((B, SMPL_NJ, 12), dtype=torch.float32, device=A.device)
+    _lib.launch("sr_smpl_skin_bwd", A, rest, stride, posedirs, feature, weights, A, gV, B, nv, partial, g_rest, gA, g_feature)
+    return g_rest, gA, g_feature
+
+
+def smpl_pose_bwd(Rs, J, A, parents, theta=None, gA=None, gJ_transformed=None, g_feature=None, gRs=None):
+    """(g_theta [B,24,3] -- or, with theta None (rotations were the input), gRs [B,24,3,3] -- and gJ [B,24,3]) of smpl_pose's arguments
+    from the cotangents of its results, each optional (sr_smpl_pose_bwd); Rs and A are smpl_pose's results."""
+    _lib.require_gpu(Rs, J, A, theta, gA, gJ_transformed, g_feature, gRs)
+    B, dev = J.shape[0], J.device
+    _smpl_f32(J, (B, SMPL_NJ, 3), "J"); _smpl_f32(Rs, (B, SMPL_NJ, 3, 3), "Rs"); _smpl_f32(A, (B, SMPL_NJ, 4, 4), "A")
+    for t, shape, name in ((theta, (B, SMPL_NJ, 3), "theta"), (gA, (B, SMPL_NJ, 12), "gA"), (gJ_transformed, (B, SMPL_NJ, 3), "gJ_transformed"),
+                           (g_feature, (B, SMPL_NPOSE), "g_feature"), (gRs, (B, SMPL_NJ, 3, 3), "gRs")):
+        if t is not None:
+            _smpl_f32(t, shape, name)
+    pa = (ctypes.c_int32 * SMPL_NJ)(*[max(int(p), 0) for p in parents])
+    g_in = torch.empty((B, SMPL_NJ, 3) if theta is not None else (B, SMPL_NJ, 3, 3), dtype=torch.float32, device=dev)
+    gJ = torch.empty((B, SMPL_NJ, 3), dtype=torch.float32, device=dev)
+    _lib.launch("sr_smpl_pose_bwd", J, theta, Rs, J, A, pa, B, gA, gJ_transformed, g_feature, gRs, g_in if theta is not None else None,
+                None if theta is not None else g_in, gJ)
+    return g_in, gJ
+
+
+KEYPOINT_MAX = 64
+
+
+def keypoint_energy(joints, trans, kp, joint_weights, camera, sigma):
+    """(energy [T], g_joints [T,K,3], g_trans [T,3], behind [T] int32) of the robust reprojection term (sr_keypoint_energy): joints
+    [T,K,3] + trans [T,3] projected by `camera` = 16 host floats (R [3,3] row major, T [3], fx, fy, cx, cy) against kp [T,K,3] =
+    (x, y, confidence), weighted by joint_weights [K]; the gradients are those of energy[t]."""
+    _lib.require_gpu(joints, trans, kp, joint_weights)
+    T, K = joints.shape[:2]
+    _smpl_f32(joints, (T, K, 3), "joints"); _smpl_f32(trans, (T, 3), "trans"); _smpl_f32(kp, (T, K, 3), "keypoints")
+    _smpl_f32(joint_weights, (K,), "joint weights")
+    if len(camera) != 16:
+        raise ValueError("keypoint_energy: camera is 16 floats: R (9), T (3), fx, fy, cx, cy")
+    cam = (ctypes.c_float * 16)(*[float(c) for c in camera])
+    dev = joints.device
+    energy = torch.empty((T,), dtype=torch.float32, device=dev)
+    g_joints = torch.empty((T, K, 3), dtype=torch.float32, device=dev)
+    g_trans = torch.empty((T, 3), dtype=torch.float32, device=dev)
+    behind = torch.empty((T,), dtype=torch.int32, device=dev)
+    _lib.launch("sr_keypoint_energy", joints, joints, trans, kp, joint_weights, cam, float(sigma), T, K, energy, g_joints, g_trans, behind)
+    return energy, g_joints, g_trans, behind
+
+
 # ------------------------------------------------------------------ mesh regularisers of the template step (csrc/mesh_reg.hip)
 MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = 1, 2, 4
 
