@@ -687,6 +687,29 @@ int sr_smpl_pose_bwd(const float* theta, const float* Rs, const float* J, const 
 int sr_keypoint_energy(const float* joints, const float* trans, const float* kp, const float* joint_weights, const float* host_camera,
                        float sigma, int32_t T, int32_t K, float* energy, float* g_joints, float* g_trans, int32_t* behind, void* stream);
 
+/* Silhouette term of smpl_fit.py (csrc/silfit.hip).  No atomics; two calls give identical bits.
+ *   sr_edt:           d2 [F,H,W] int32 = the exact squared pixel distance of every pixel to the nearest non-zero pixel of mask [F,H,W]
+ *     uint8 in the same frame (0 on the mask); SR_EDT_EMPTY in every entry of a frame without one.  F <= 65535, H, W <= 8192.  Two launches.
+ *   sr_contour_flags: flags [F,H,W] uint8 = 1 where a mask pixel has a 4-neighbour inside the image that is background.
+ *   sr_silhouette_energy: for frame t < F the points [F,V,3] (world, translation included) are projected as in sr_keypoint_energy
+ *     (host_camera: the same 16 HOST floats); pixel (col, row) has its centre at x = col, y = row.
+ *       e_in[t]  = (1/V) sum_v rho(d(x, y)), rho(r) = sigma^2 r^2 / (sigma^2 + r^2), d the bilinear interpolation of sqrt(d2) in the cell
+ *         x0 = min(floor(x), W-2), y0 = min(floor(y), H-2); a vertex with pc_z <= 0, a non-finite pixel position or one outside
+ *         [0, W-1] x [0, H-1] contributes nothing and is counted in outside[t]; a frame whose d2 holds SR_EDT_EMPTY has e_in = 0.
+ *       e_cov[t] = (1/n) sum_{s<n} rho(max(0, min_v |c_ts - xy_tv| - margin)), n = min(counts[t], S), c = samples [F,S,2] int32 (x, y);
+ *         the minimum runs over the vertices in front of the camera with a finite pixel position, a tie goes to the lower index, a
+ *         sample without any such vertex contributes nothing; the match is held fixed in the gradient.
+ *     -> e_in [F], e_cov [F], outside [F] int32, g_points [2,F,V,3] (the gradients of e_in[t] and of e_cov[t]), and the work arrays
+ *     xy [F,V,2], valid [F,V] uint8 (0 behind / non-finite, 1 in front, 2 inside the image), vres [F,V,3] (a vertex's inside value and
+ *     its gradient in the pixel position), match [F,S] int32 (-1: none), sres [F,S,3] (a sample's residual value and its gradient at the
+ *     matched pixel).  H, W >= 2, S <= 65536.  Three launches: projection and inside term, match, gradient and sums. */
+#define SR_EDT_EMPTY 1073741824
+int sr_edt(const uint8_t* mask, int32_t F, int32_t H, int32_t W, int32_t* d2, void* stream);
+int sr_contour_flags(const uint8_t* mask, int32_t F, int32_t H, int32_t W, uint8_t* flags, void* stream);
+int sr_silhouette_energy(const float* points, const int32_t* d2, const int32_t* samples, const int32_t* counts, const float* host_camera,
+                         float sigma, float margin, int32_t F, int32_t V, int32_t S, int32_t H, int32_t W, float* xy, uint8_t* valid,
+                         float* vres, int32_t* match, float* sres, float* e_in, float* e_cov, int32_t* outside, float* g_points, void* stream);
+
 /* Mesh regularisers of the template step (csrc/mesh_reg.hip): mesh_laplacian_smoothing(method='uniform'), mesh_edge_loss and
  * mesh_normal_consistency of pytorch3d 0.4.0 as model/network.py:655-670 calls them, restated, on one mesh of V vertices.
  * Topology, int32, built once per remesh by mesh_losses.MeshTopology: nbr_row [V+1] / nbr [2E] the neighbour CSR (ascending per row),

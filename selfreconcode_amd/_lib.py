@@ -277,6 +277,9 @@ SIGNATURES = {
     "sr_smpl_skin_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp, _vp, _vp, _vp],
     "sr_smpl_pose_bwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "sr_keypoint_energy": [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp],
+    "sr_edt": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
+    "sr_contour_flags": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
+    "sr_silhouette_energy": [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float] + [ctypes.c_int32] * 5 + [_vp] * 10,
     "sr_meshreg_workspace_bytes": [_i64, _i64],
     "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
     "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,

@@ -98,6 +98,23 @@ def read_scene_folder(root):
             'mask': mask, 'poses': poses, 'trans': trans, 'shape': shape, 'gender': gender, 'video_segmented_index': split, 'camera': camera}
 
 
+def read_mask_folder(folder, stems):
+    """mask [F,H,W] uint8 0/1 from `folder`/<stem>.png for the image stems in frame order, by read_scene_folder's rule (any channel > 0,
+    8-bit, all of the first file's size) -- for fit_smpl, which needs the masks before the smpl_rec.npz that read_scene_folder demands
+    exists."""
+    names = [osp.join(str(folder), str(stem) + '.png') for stem in stems]
+    for p in names:
+        if not osp.isfile(p):
+            raise ValueError(f"{p}: the mask of frame {_stem(p)} is missing")
+    if not names:
+        raise ValueError(f"{folder}: no frames to read masks for")
+    H, W = _decode(names[0]).shape[:2]
+    mask = np.empty((len(names), H, W), np.uint8)
+    for i, p in enumerate(names):
+        mask[i] = (_decode(p, (H, W)) > 0).any(-1)
+    return mask
+
+
 def make_conds(conds_lens, frame_num):
     """The per-frame conditioning codes on the CPU (dataset.py:18-24): per entry of `conds_lens`, in dict order,
     ((0.1 randn(length, F // 5)) @ DCTSpace(F // 5, F)).T, drawn from torch's global generator and multiplied on the CPU, so that after

@@ -2,6 +2,7 @@
 
     python -m selfreconcode_amd.fit_smpl --gpu-ids 0 --data FOLDER --keypoints FILE_OR_DIR [--format cocoplus|coco18|body25]
         [--gender G] [--model-dir D] [--init smpl_rec.npz] [--force] [--out FILE]
+        [--masks [DIR]] [--sil-weights IN COV] [--sil-samples S] [--sil-margin M] [--sil-sigma SIGMA]
 
 Reads FOLDER/camera.npz and counts FOLDER/imgs as dataset.read_scene_folder does, takes the body model from getSMPL(gender, model_dir)
 and the keypoints from an `.npz` (`keypoints` [F,K,3]) or a folder of OpenPose `*_keypoints.json` files.  Writes FOLDER/smpl_rec.npz
@@ -9,6 +10,13 @@ and the keypoints from an `.npz` (`keypoints` [F,K,3]) or a folder of OpenPose `
 and FOLDER/smpl_fit.json (always in FOLDER, also when --out points elsewhere: it reports on the folder's frames): per frame the
 reprojection error and the number of joints behind the camera, then mean, max and the ten worst frames.  An existing output file is
 refused without --force.
+
+--masks adds the silhouette term of DESIGN 3.21 (smpl_fit.fit_sequence(masks=...)): DIR/<stem>.png per image, FOLDER/masks when no DIR
+is given, a pixel is mask where any channel is > 0 (dataset.read_mask_folder, read_scene_folder's rule).  --sil-weights sets l_in and
+l_cov of every silhouette round, --sil-samples, --sil-margin and --sil-sigma the entries of smpl_fit.DEFAULT_SILHOUETTE.  smpl_fit.json
+then also carries per frame sil_inside, sil_cover (pixels), sil_outside and mask_error (1 - IoU of the rasterised body against the
+mask; null when the image is not square or the model has no faces), and their means in the summary.  Without --masks every byte of
+both files and of the printed line is as before.
 """
 import argparse
 import glob
@@ -33,9 +41,20 @@ def parse_args(argv=None):
     parser.add_argument("--init", default=None, metavar="smpl_rec.npz", help="start from these poses / shape / trans instead of stages 0 and 1")
     parser.add_argument("--force", action="store_true", help="overwrite an existing output file")
     parser.add_argument("--out", default=None, metavar="FILE", help="the file to write (default FOLDER/smpl_rec.npz)")
+    parser.add_argument("--masks", nargs="?", const="", default=None, metavar="DIR", help="add the silhouette term; masks from DIR (default FOLDER/masks)")
+    parser.add_argument("--sil-weights", nargs=2, type=float, default=None, metavar=("IN", "COV"), help="weights of the inside and the coverage term")
+    parser.add_argument("--sil-samples", type=int, default=None, metavar="S", help="contour samples per frame")
+    parser.add_argument("--sil-margin", type=float, default=None, metavar="M", help="half the projected vertex spacing, in pixels")
+    parser.add_argument("--sil-sigma", type=float, default=None, metavar="SIGMA", help="scale of the silhouette term's robustifier, in pixels")
     args = parser.parse_args(argv)
     if not os.path.isdir(args.data):
         parser.error(f"--data {args.data}: not a folder")
+    if args.masks == "":
+        args.masks = os.path.join(args.data, "masks")
+    if args.masks is not None and not os.path.isdir(args.masks):
+        parser.error(f"--masks {args.masks}: not a folder")
+    if args.masks is None and any(v is not None for v in (args.sil_weights, args.sil_samples, args.sil_margin, args.sil_sigma)):
+        parser.error("--sil-weights, --sil-samples, --sil-margin and --sil-sigma need --masks")
     if not os.path.isfile(os.path.join(args.data, "camera.npz")):
         parser.error(f"--data {args.data}: no camera.npz")
     if not os.path.exists(args.keypoints):
@@ -45,15 +64,20 @@ def parse_args(argv=None):
     return args
 
 
-def count_frames(folder):
-    """The number of imgs/<i>.jpg|.png, which must count 0, 1, 2, ... as read_scene_folder demands."""
+def frame_stems(folder):
+    """The stems of imgs/<i>.jpg|.png in frame order; they must count 0, 1, 2, ... as read_scene_folder demands."""
     from .dataset.dataset import IMAGE_EXTENSIONS
     stems = [os.path.basename(p).split('.')[0] for ext in IMAGE_EXTENSIONS for p in glob.glob(os.path.join(folder, 'imgs', '*' + ext))]
     if not stems:
         raise ValueError(f"{os.path.join(folder, 'imgs')}: no .jpg or .png images")
     if sorted(int(s) for s in stems if s.isdigit()) != list(range(len(stems))):
         raise ValueError(f"{os.path.join(folder, 'imgs')}: image names must count 0, 1, 2, ... without gaps or repeats")
-    return len(stems)
+    return sorted(stems, key=int)
+
+
+def count_frames(folder):
+    """The number of imgs/<i>.jpg|.png, which must count 0, 1, 2, ... as read_scene_folder demands."""
+    return len(frame_stems(folder))
 
 
 def write_smpl_rec(path, result, force=False):
@@ -80,6 +104,14 @@ def write_report(path, result):
                           "worst_frames": [int(i) for i in worst], "start": int(result.get('start', 0)),
                           "energy_first": float(result['history'][0]) if len(result['history']) else None,
                           "energy_last": float(result['history'][-1]) if len(result['history']) else None}}
+    if 'sil_inside' in result:                                         # (the fit saw masks: the silhouette term's residuals)
+        err = result.get('mask_error')
+        for i, frame in enumerate(report["frames"]):
+            frame.update({"sil_inside": float(result['sil_inside'][i]), "sil_cover": float(result['sil_cover'][i]),
+                          "sil_outside": int(result['sil_outside'][i]), "mask_error": None if err is None else float(err[i])})
+        report["summary"].update({"sil_inside_mean": float(np.mean(result['sil_inside'])), "sil_cover_mean": float(np.mean(result['sil_cover'])),
+                                  "sil_outside_total": int(np.sum(result['sil_outside'])), "sil_empty": int(result['sil_empty']),
+                                  "mask_error_mean": None if err is None else float(np.mean(err))})
     with open(path, 'w') as fh:
         json.dump(report, fh, indent=1)
     return report
@@ -98,12 +130,23 @@ def main(argv=None, out=print):
     keypoints = smpl_fit.read_keypoints(args.keypoints, frames, args.format)
     device = torch.device("cuda", args.gpu_ids[0])
     smpl = getSMPL(args.gender, args.model_dir, differentiable=True).to(device)
-    result = smpl_fit.fit_sequence(smpl, keypoints, camera, init=args.init, gender=args.gender)
+    extra = {}
+    if args.masks is not None:
+        from .dataset.dataset import read_mask_folder
+        extra["masks"] = read_mask_folder(args.masks, frame_stems(args.data))
+        extra["silhouette"] = {k: v for k, v in (("samples", args.sil_samples), ("margin", args.sil_margin), ("sigma", args.sil_sigma)) if v is not None}
+        if args.sil_weights is not None:
+            extra["silhouette_stages"] = tuple(tuple(s[:5]) + tuple(args.sil_weights) for s in smpl_fit.DEFAULT_SILHOUETTE_STAGES)
+    result = smpl_fit.fit_sequence(smpl, keypoints, camera, init=args.init, gender=args.gender, **extra)
     write_smpl_rec(target, result, args.force)
     report = write_report(os.path.join(args.data, "smpl_fit.json"), result)
     s = report["summary"]
-    out(f"fit_smpl: {frames} frames -> {target}: reprojection mean {s['reproj_mean']:.2f} px, max {s['reproj_max']:.2f} px "
-        f"(frame {s['worst_frames'][0]}), {s['behind_total']} joints behind the camera")
+    line = (f"fit_smpl: {frames} frames -> {target}: reprojection mean {s['reproj_mean']:.2f} px, max {s['reproj_max']:.2f} px "
+            f"(frame {s['worst_frames'][0]}), {s['behind_total']} joints behind the camera")
+    if args.masks is not None:
+        line += (f"; silhouette inside {s['sil_inside_mean']:.2f} px, cover {s['sil_cover_mean']:.2f} px"
+                 + ("" if s['mask_error_mean'] is None else f", mask error {s['mask_error_mean']:.3f}") + f", {s['sil_empty']} empty masks")
+    out(line)
     return result
 
 

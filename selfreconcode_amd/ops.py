@@ -366,6 +366,75 @@ def keypoint_energy(joints, trans, kp, joint_weights, camera, sigma):
     return energy, g_joints, g_trans, behind
 
 
+# ------------------------------------------------------------------ silhouette term of smpl_fit.py (csrc/silfit.hip)
+EDT_EMPTY = 1 << 30                     # every entry of the squared distance field of a frame without a mask pixel
+EDT_MAX_DIM = 8192
+SIL_MAX_SAMPLES = 65536
+
+
+def _mask_u8(masks, name):
+    _lib.require_gpu(masks)
+    if masks.dim() != 3 or masks.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"{name}: masks are [F,H,W] uint8 or bool, got {masks.dtype} {tuple(masks.shape)}")
+    F, H, W = masks.shape
+    if F < 1 or H < 1 or W < 1 or H > EDT_MAX_DIM or W > EDT_MAX_DIM:
+        raise ValueError(f"{name}: masks {tuple(masks.shape)}: at least one frame and 1 <= H, W <= {EDT_MAX_DIM}")
+    masks = masks.detach().contiguous()
+    return masks.view(torch.uint8) if masks.dtype == torch.bool else masks
+
+
+def edt(masks):
+    """d2 [F,H,W] int32: the exact squared pixel distance to the nearest non-zero pixel of the same frame of masks [F,H,W] (uint8 or
+    bool), 0 on the mask; EDT_EMPTY everywhere in a frame without a mask pixel (sr_edt)."""
+    m = _mask_u8(masks, "edt")
+    F, H, W = m.shape
+    d2 = torch.empty((F, H, W), dtype=torch.int32, device=m.device)
+    _lib.launch("sr_edt", m, m, F, H, W, d2)
+    return d2
+
+
+def contour_flags(masks):
+    """flags [F,H,W] uint8: 1 where a mask pixel has a 4-neighbour inside the image that is background (sr_contour_flags)."""
+    m = _mask_u8(masks, "contour_flags")
+    F, H, W = m.shape
+    flags = torch.empty((F, H, W), dtype=torch.uint8, device=m.device)
+    _lib.launch("sr_contour_flags", m, m, F, H, W, flags)
+    return flags
+
+
+def silhouette_energy(points, d2, samples, counts, camera, sigma, margin):
+    """(e_in [F], e_cov [F], outside [F] int32, g_points [2,F,V,3], match [F,S] int32) of the silhouette term (sr_silhouette_energy):
+    points [F,V,3] float32 in the world, d2 [F,H,W] int32 (edt), samples [F,S,2] int32 (x, y) and counts [F] int32 the contour samples,
+    camera the 16 host floats of keypoint_energy.  g_points[0] is the gradient of e_in[t], g_points[1] that of e_cov[t]."""
+    _lib.require_gpu(points, d2, samples, counts)
+    F, V = points.shape[:2]
+    S = samples.shape[1] if samples.dim() == 3 else 0
+    _smpl_f32(points, (F, V, 3), "points")
+    if d2.dtype != torch.int32 or d2.dim() != 3 or d2.shape[0] != F or not d2.is_contiguous():
+        raise ValueError(f"silhouette_energy: d2 must be contiguous int32 [{F},H,W], got {d2.dtype} {tuple(d2.shape)}")
+    H, W = d2.shape[1:]
+    if H < 2 or W < 2 or H > EDT_MAX_DIM or W > EDT_MAX_DIM:
+        raise ValueError(f"silhouette_energy: the field is {H} x {W}: 2 <= H, W <= {EDT_MAX_DIM}")
+    if samples.dtype != torch.int32 or tuple(samples.shape) != (F, S, 2) or not samples.is_contiguous() or S < 1 or S > SIL_MAX_SAMPLES:
+        raise ValueError(f"silhouette_energy: samples must be contiguous int32 [{F},S,2] with 1 <= S <= {SIL_MAX_SAMPLES}, got {samples.dtype} {tuple(samples.shape)}")
+    if counts.dtype != torch.int32 or tuple(counts.shape) != (F,) or not counts.is_contiguous():
+        raise ValueError(f"silhouette_energy: counts must be contiguous int32 [{F}], got {counts.dtype} {tuple(counts.shape)}")
+    if len(camera) != 16:
+        raise ValueError("silhouette_energy: camera is 16 floats: R (9), T (3), fx, fy, cx, cy")
+    if not (sigma > 0 and margin >= 0):
+        raise ValueError(f"silhouette_energy: sigma {sigma} must be positive and margin {margin} non-negative")
+    cam = (ctypes.c_float * 16)(*[float(c) for c in camera])
+    dev = points.device
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)          # noqa: E731
+    xy, valid, vres = f32(F, V, 2), torch.empty((F, V), dtype=torch.uint8, device=dev), f32(F, V, 3)
+    match, sres = torch.empty((F, S), dtype=torch.int32, device=dev), f32(F, S, 3)
+    e_in, e_cov, outside = f32(F), f32(F), torch.empty((F,), dtype=torch.int32, device=dev)
+    g_points = f32(2, F, V, 3)
+    _lib.launch("sr_silhouette_energy", points, points, d2, samples, counts, cam, float(sigma), float(margin), F, V, S, H, W, xy, valid, vres, match,
+                sres, e_in, e_cov, outside, g_points)
+    return e_in, e_cov, outside, g_points, match
+
+
 # ------------------------------------------------------------------ mesh regularisers of the template step (csrc/mesh_reg.hip)
 MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = 1, 2, 4
 

@@ -14,11 +14,16 @@ Keypoints come in the order of the model's regressed joints (joint_type='cocoplu
 L ankle; 6-11 R wrist, R elbow, R shoulder, L shoulder, L elbow, L wrist; 12 neck, 13 head top; 14-18 nose, L eye, R eye, L ear, R ear.
 convert_keypoints maps the COCO-18 and BODY-25 detector layouts onto it (HMR's convention, written down from memory: no model file
 was at hand to check the tables against -- `joint_weights` lets a caller down-weight joints whose definition differs, the hips first).
+
+With `masks` the silhouette term of DESIGN 3.21 joins in further rounds after stage 2 (silhouette_stages): l_in sum_t e_in[t] +
+l_cov sum_t e_cov[t], the body's vertices against the exact distance field of the masks (distance_transform) and the masks' contour
+samples against the vertices (silhouette_field, silhouette_energy; csrc/silfit.hip).
 """
 import glob
 import json
 import os
 import re
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -40,6 +45,17 @@ KEYPOINT_COUNTS = {'cocoplus': 19, 'coco18': 18, 'body25': 25}
 # shape moves there), the others are the rounds of stage 2.  A documented default, not a tuned one.
 DEFAULT_STAGES = ((100, 0.05, 0., 0., 1000.), (150, 0.02, 100., 100., 1000.), (150, 0.01, 10., 10., 1000.), (200, 0.005, 1., 1., 100.))
 LAMBDA_3D = 1e4          # weight of the optional 3-D joint term: 0.01 units of error weigh like one pixel
+# The silhouette term.  sigma: a vertex 20 px off the mask already weighs like an outlier (the keypoints' 100 px would let
+# one stray limb outvote the contour); margin: half the spacing of the projected vertices -- SMPL's 6890 vertices on a body some 500 px
+# tall and 150 px wide lie about 3.3 px apart, a body further away or a coarser model needs its own value; samples: contour samples per
+# frame.  Documented defaults, not tuned ones.
+DEFAULT_SILHOUETTE = {'sigma': 20., 'margin': 2., 'samples': 1024}
+# (iterations, lr, l_theta, l_beta, l_s, l_in, l_cov): the rounds with the silhouette term, after stage 2.  Priors and step as in stage 2's
+# last round; e_in and e_cov are means over vertices and samples, so l_in = 10 lets the mean inside residual weigh like ten keypoints and
+# l_cov = 25 the mean coverage residual like twenty-five (the weights at which the float64 restatement recovers limbs without keypoints).
+DEFAULT_SILHOUETTE_STAGES = ((100, 0.005, 1., 1., 100., 10., 25.),)
+SAMPLE_FRAMES = 8        # frames per prefix sum while the contour samples are compacted
+SilhouetteField = namedtuple('SilhouetteField', 'd2 samples counts')          # [F,H,W] int32, [F,S,2] int32 (x, y), [F] int32; on the GPU
 
 
 # ---------------------------------------------------------------------------------------------- keypoints in, host side
@@ -213,12 +229,137 @@ def keypoint_energy(joints, trans, kp, joint_weights, camera, sigma):
     return _KeypointEnergy.apply(joints, trans, kp, joint_weights, camera, sigma)
 
 
-def _energy(smpl, root, body, trans, beta, kp, jw, cam, sigma, l_theta, l_beta, l_s, joints3d, l_3):
+# ---------------------------------------------------------------------------------------------- the silhouette term
+def _masks_on(masks, device):
+    m = masks if torch.is_tensor(masks) else torch.from_numpy(np.ascontiguousarray(np.asarray(masks)))
+    if m.dim() != 3 or m.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f"masks are [F,H,W] uint8 or bool, got {m.dtype} {tuple(m.shape)}")
+    if device is None:
+        device = m.device if m.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    return m.to(device)
+
+
+def distance_transform(masks, device=None):
+    """d2 [F,H,W] int32 on the GPU: of every pixel the exact squared distance, in pixels, to the nearest non-zero pixel of the same frame
+    of masks [F,H,W] (uint8 or bool, host or device); 0 on the mask.  A frame without any mask pixel holds ops.EDT_EMPTY = 1 << 30 in
+    every entry.  H, W <= 8192, so that the squared diagonal stays inside int32."""
+    return ops.edt(_masks_on(masks, device))
+
+
+def contour_samples(masks, samples):
+    """(samples [F,S,2] int32 = (x, y), counts [F] int32) on the masks' device (the GPU).  A contour pixel is a mask pixel with a
+    4-neighbour inside the image that is background (the image's border makes none: a body cropped by the frame has no edge there).
+    Of a frame's n contour pixels in row-major order all are taken when n <= S, else pixel floor(i n / S) for i < S (int64); counts
+    holds n, the rows past min(n, S) are zero.  Flags from sr_contour_flags, then a prefix sum and a binary search per frame: no host read."""
+    S = int(samples)
+    if S < 1 or S > ops.SIL_MAX_SAMPLES:
+        raise ValueError(f"contour_samples: 1 <= samples <= {ops.SIL_MAX_SAMPLES}, got {samples}")
+    flags = ops.contour_flags(masks)
+    F, H, W = flags.shape
+    dev = flags.device
+    out = torch.zeros((F, S, 2), dtype=torch.int32, device=dev)
+    counts = torch.empty((F,), dtype=torch.int32, device=dev)
+    i = torch.arange(S, dtype=torch.int64, device=dev).view(1, S)
+    for f0 in range(0, F, SAMPLE_FRAMES):
+        cum = torch.cumsum(flags[f0:f0 + SAMPLE_FRAMES].view(-1, H * W), 1, dtype=torch.int32)          # inclusive ranks, H W < 2^31
+        n = cum[:, -1].to(torch.int64).view(-1, 1)
+        rank = torch.where(n <= S, i, (i * n) // S)
+        live = i < n.clamp(max=S)
+        pos = torch.searchsorted(cum, (rank + 1).to(torch.int32))                                       # the first pixel whose rank is rank + 1
+        pos = torch.where(live, pos, torch.zeros_like(pos))
+        out[f0:f0 + SAMPLE_FRAMES, :, 0] = (pos % W).to(torch.int32)
+        out[f0:f0 + SAMPLE_FRAMES, :, 1] = (pos // W).to(torch.int32)
+        counts[f0:f0 + SAMPLE_FRAMES] = cum[:, -1]
+    return out, counts
+
+
+def silhouette_field(masks, samples=DEFAULT_SILHOUETTE['samples'], device=None):
+    """SilhouetteField(d2, samples, counts) of masks [F,H,W] (uint8 or bool, host or device), on the GPU: what silhouette_energy reads."""
+    m = _masks_on(masks, device)
+    return SilhouetteField(ops.edt(m), *contour_samples(m, samples))
+
+
+class _SilhouetteEnergy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, d2, samples, counts, camera, sigma, margin):
+        e_in, e_cov, outside, g_points, _ = ops.silhouette_energy(points.contiguous(), d2, samples, counts, camera, sigma, margin)
+        ctx.save_for_backward(g_points)
+        ctx.mark_non_differentiable(outside)
+        return e_in, e_cov, outside
+
+    @staticmethod
+    def backward(ctx, g_in, g_cov, _):
+        g_points, = ctx.saved_tensors
+        return torch.addcmul(g_points[0] * g_in.view(-1, 1, 1), g_points[1], g_cov.view(-1, 1, 1)), None, None, None, None, None, None
+
+
+def silhouette_energy(points, field, camera, sigma=DEFAULT_SILHOUETTE['sigma'], margin=DEFAULT_SILHOUETTE['margin']):
+    """(e_in [F], e_cov [F], outside [F] int32), differentiable in points [F,V,3] (world positions, the translation added); field:
+    silhouette_field(...); camera: camera_floats(...).  e_in[t] = mean_v rho_sigma(d(project(p_tv))) with d the bilinear interpolation of
+    the distance field, e_cov[t] = mean_s rho_sigma(max(0, min_v |c_ts - project(p_tv)| - margin)) with the match held fixed in the
+    gradient; outside counts the vertices behind the camera, off the image or non-finite, which add nothing to e_in."""
+    return _SilhouetteEnergy.apply(points, field.d2, field.samples, field.counts, camera, sigma, margin)
+
+
+def silhouette_residuals(points, field, camera, margin):
+    """(inside [F], cover [F]) float32: the two terms' mean residuals in pixels, without the robustifier -- the mean of d over the
+    vertices inside the image and the mean of max(0, distance to the matched vertex - margin) over the samples in use (0 for a frame
+    without either).  The matches are the kernel's; the means are torch operators: this is the report, not the loop."""
+    with torch.no_grad():
+        pts = points.detach().contiguous()
+        _, _, _, _, match = ops.silhouette_energy(pts, field.d2, field.samples, field.counts, camera, 1., margin)
+        R = torch.tensor(camera[:9], dtype=torch.float32, device=pts.device).view(3, 3)
+        T = torch.tensor(camera[9:12], dtype=torch.float32, device=pts.device)
+        pc = pts.matmul(R) + T
+        front = pc[..., 2] > 0
+        z = torch.where(front, pc[..., 2], torch.ones_like(pc[..., 2]))
+        xy = torch.stack([camera[14] - camera[12] * pc[..., 0] / z, camera[15] - camera[13] * pc[..., 1] / z], -1)
+        F, H, W = field.d2.shape
+        ok = front & torch.isfinite(xy).all(-1) & (xy[..., 0] >= 0) & (xy[..., 0] <= W - 1) & (xy[..., 1] >= 0) & (xy[..., 1] <= H - 1)
+        ok &= (field.d2[:, 0, 0] != ops.EDT_EMPTY).view(F, 1)
+        x = torch.where(ok, xy[..., 0], torch.zeros_like(z))
+        y = torch.where(ok, xy[..., 1], torch.zeros_like(z))
+        x0, y0 = x.floor().clamp(0, W - 2).long(), y.floor().clamp(0, H - 2).long()
+        fx, fy = x - x0, y - y0
+        flat = field.d2.view(F, H * W)
+        tap = lambda dy, dx: torch.gather(flat, 1, (y0 + dy) * W + x0 + dx).float().sqrt()          # noqa: E731
+        d = (tap(0, 0) * (1 - fx) + tap(0, 1) * fx) * (1 - fy) + (tap(1, 0) * (1 - fx) + tap(1, 1) * fx) * fy
+        inside = torch.where(ok, d, torch.zeros_like(d)).sum(1) / ok.sum(1).clamp(min=1)
+        S = field.samples.shape[1]
+        used = (torch.arange(S, device=pts.device).view(1, S) < field.counts.clamp(max=S).view(F, 1)) & (match >= 0)
+        hit = torch.gather(xy, 1, match.clamp(min=0).long().unsqueeze(-1).expand(F, S, 2))
+        r = ((hit - field.samples.float()).norm(dim=-1) - margin).clamp(min=0)
+        cover = torch.where(used, r, torch.zeros_like(r)).sum(1) / field.counts.clamp(min=1, max=S)
+    return inside, cover
+
+
+def mask_error(smpl, points, masks, camera):
+    """[F]: 1 - IoU of the rasterised body (points [F,V,3] with the model's faces) against masks [F,H,W] on the GPU, through
+    posed.rasterize_posed and posed.mask_iou_error; None when the image is not square (the rasteriser's limit) or the model has no faces."""
+    from . import posed
+    from .model.CameraMine import RectifiedPerspectiveCameras
+    F, H, W = masks.shape
+    faces = getattr(smpl, 'faces_tensor', None)
+    if H != W or faces is None or faces.numel() == 0:
+        return None
+    f32 = lambda a: torch.as_tensor(np.asarray(a, np.float32), device=points.device)          # noqa: E731
+    cams = RectifiedPerspectiveCameras(f32([camera['fx'], camera['fy']]), f32([camera['cx'], camera['cy']]), f32(camera['R']), f32(camera['T']), [(W, H)])
+    frags, _ = posed.rasterize_posed(points.detach().contiguous(), faces.to(points.device), cams, H, W)
+    return posed.mask_iou_error((frags.pix_to_face[..., 0] >= 0).float(), (masks != 0).float())
+
+
+def _energy(smpl, root, body, trans, beta, kp, jw, cam, sigma, l_theta, l_beta, l_s, joints3d, l_3, sil=None):
     F = root.shape[0]
     theta = torch.cat([root.view(F, 1, 3), body], 1)
-    joints = smpl(beta.expand(F, -1), theta)
+    if sil is None:
+        joints = smpl(beta.expand(F, -1), theta)
+    else:                                                 # (field, sigma, margin, l_in, l_cov): the vertices of the same forward
+        verts, joints, _ = smpl(beta.expand(F, -1), theta, get_skin=True)
     e_kp, _ = keypoint_energy(joints, trans, kp, jw, cam, sigma)
     E = e_kp.sum()
+    if sil is not None:
+        e_in, e_cov, _ = silhouette_energy(verts + trans.view(F, 1, 3), sil[0], cam, sil[1], sil[2])
+        E = E + sil[3] * e_in.sum() + sil[4] * e_cov.sum()
     if l_theta:
         E = E + l_theta * (body ** 2).sum()
     if l_beta:
@@ -248,7 +389,7 @@ def _descend(smpl, params, frozen, iters, lr, history, offset, energy_args):
 
 
 def fit_sequence(smpl, keypoints, camera, *, joints3d=None, init=None, gender='neutral', sigma=100., stages=DEFAULT_STAGES, joint_weights=None,
-                 starts=None, seed=0, lambda_3d=LAMBDA_3D):
+                 starts=None, seed=0, lambda_3d=LAMBDA_3D, masks=None, silhouette=None, silhouette_stages=DEFAULT_SILHOUETTE_STAGES):
     """Fit `smpl` (a DifferentiableSMPL with the 19 cocoplus joints, on the GPU) to keypoints [F,19,3] = (x, y, confidence) under
     `camera` (make_camera / read_camera).  -> dict: poses [F,24,3], shape [10], trans [F,3] float32 numpy; reproj [F] (mean pixel
     error over the joints with confidence > 0), behind [F] (joints behind the camera), history (the energy of every iteration, in
@@ -257,7 +398,15 @@ def fit_sequence(smpl, keypoints, camera, *, joints3d=None, init=None, gender='n
     joints3d [F,19,3] adds lambda_3d sum |J3d - joints3d|^2 (joint positions in the world, translation included) -- for converting or
     refining the output of another estimator.  init (a dict or npz path with poses, shape, trans) replaces stages 0 and 1.
     joint_weights [19] scale the 2-D term per joint (default ones).  starts [S,3]: the root orientations stage 1 tries (default_starts).
-    `seed` is accepted for interface stability only: the fit draws no random numbers."""
+    `seed` is accepted for interface stability only: the fit draws no random numbers.
+
+    masks [F,H,W] (uint8 or bool, host or device) adds the silhouette term: after stage 2 the rounds of silhouette_stages =
+    (iterations, lr, l_theta, l_beta, l_s, l_in, l_cov) minimise the energy above plus l_in sum_t e_in[t] + l_cov sum_t e_cov[t]
+    (silhouette_energy) over all parameters; `silhouette` overrides entries of DEFAULT_SILHOUETTE (sigma, margin, samples).  history
+    grows by those iterations and the result gains sil_inside [F], sil_cover [F] (the two terms' mean residuals in pixels at the end,
+    silhouette_residuals), sil_outside [F] (vertices that are behind the camera, off the image or non-finite), sil_empty (the number of
+    frames without a mask pixel: they take no part in the term) and mask_error ([F] 1 - IoU of the rasterised body, or None: mask_error).
+    Without masks nothing changes: the same operators run and the result has the same keys."""
     dev = smpl.v_template.device
     if smpl.joint_regressor.shape[1] != NUM_KEYPOINTS:
         raise ValueError("fit_sequence: the body model must regress the 19 cocoplus joints (joint_type='cocoplus')")
@@ -281,7 +430,22 @@ def fit_sequence(smpl, keypoints, camera, *, joints3d=None, init=None, gender='n
     nbeta = smpl.num_betas
     zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)          # noqa: E731
     starts_host = default_starts(camera) if starts is None else np.asarray(starts, np.float64).reshape(-1, 3)
-    history = zeros(sum(s[0] for s in stages[1:]) + (0 if init is not None else stages[0][0] * starts_host.shape[0]))
+    field = None
+    if masks is not None:
+        unknown = set(silhouette or {}) - set(DEFAULT_SILHOUETTE)
+        if unknown:
+            raise ValueError(f"fit_sequence: silhouette has {sorted(unknown)}; known: {sorted(DEFAULT_SILHOUETTE)}")
+        sil_cfg = dict(DEFAULT_SILHOUETTE, **(silhouette or {}))
+        sil_stages = tuple(tuple(s) for s in silhouette_stages)
+        if any(len(s) != 7 for s in sil_stages):
+            raise ValueError("fit_sequence: silhouette_stages is a tuple of (iterations, lr, l_theta, l_beta, l_s, l_in, l_cov)")
+        masks_dev = _masks_on(masks, dev)
+        if masks_dev.shape[0] != F:
+            raise ValueError(f"fit_sequence: masks {tuple(masks_dev.shape)} for {F} frames")
+        field = silhouette_field(masks_dev, sil_cfg['samples'])
+    else:
+        sil_stages = ()
+    history = zeros(sum(s[0] for s in stages[1:]) + (0 if init is not None else stages[0][0] * starts_host.shape[0]) + sum(s[0] for s in sil_stages))
     start_index = torch.zeros((), dtype=torch.int64, device=dev)
     done = 0
     if init is not None:
@@ -315,14 +479,30 @@ def fit_sequence(smpl, keypoints, camera, *, joints3d=None, init=None, gender='n
         args = (kp, jw, cam, sigma, l_theta, l_beta, l_s, target3d, lambda_3d)
         state = _descend(smpl, dict(state), {}, iters, lr, history, done, args)
         done += iters
+    for iters, lr, l_theta, l_beta, l_s, l_in, l_cov in sil_stages:
+        args = (kp, jw, cam, sigma, l_theta, l_beta, l_s, target3d, lambda_3d, (field, sil_cfg['sigma'], sil_cfg['margin'], l_in, l_cov))
+        state = _descend(smpl, dict(state), {}, iters, lr, history, done, args)
+        done += iters
     with torch.no_grad():
         theta = torch.cat([state['root'].view(F, 1, 3), state['body']], 1)
-        joints = smpl(state['beta'].expand(F, -1).contiguous(), theta)
+        if field is None:
+            joints = smpl(state['beta'].expand(F, -1).contiguous(), theta)
+        else:
+            verts, joints, _ = smpl(state['beta'].expand(F, -1).contiguous(), theta, get_skin=True)
         _, behind = keypoint_energy(joints, state['trans'], kp, jw, cam, sigma)
         reproj = reprojection_error(joints + state['trans'].view(F, 1, 3), kp, camera)
-    return {'poses': theta.cpu().numpy(), 'shape': state['beta'].view(-1).cpu().numpy(), 'trans': state['trans'].cpu().numpy(),
-            'reproj': reproj.cpu().numpy(), 'behind': behind.cpu().numpy(), 'history': history.cpu().numpy(), 'start': int(start_index),
-            'gender': str(gender)}
+    result = {'poses': theta.cpu().numpy(), 'shape': state['beta'].view(-1).cpu().numpy(), 'trans': state['trans'].cpu().numpy(),
+              'reproj': reproj.cpu().numpy(), 'behind': behind.cpu().numpy(), 'history': history.cpu().numpy(), 'start': int(start_index),
+              'gender': str(gender)}
+    if field is not None:
+        with torch.no_grad():
+            points = (verts + state['trans'].view(F, 1, 3)).contiguous()
+            _, _, outside = silhouette_energy(points, field, cam, sil_cfg['sigma'], sil_cfg['margin'])
+            inside, cover = silhouette_residuals(points, field, cam, sil_cfg['margin'])
+            err = mask_error(smpl, points, masks_dev, camera)
+        result.update({'sil_inside': inside.cpu().numpy(), 'sil_cover': cover.cpu().numpy(), 'sil_outside': outside.cpu().numpy(),
+                       'sil_empty': int((field.d2[:, 0, 0] == ops.EDT_EMPTY).sum()), 'mask_error': None if err is None else err.cpu().numpy()})
+    return result
 
 
 def reprojection_error(points, kp, camera):
