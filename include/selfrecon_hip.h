@@ -565,7 +565,29 @@ int sr_texture_fill(const float* tex_median, const uint8_t* mask_final, const ui
  *   sr_chart_uv: vt [3F,2], vt[3 f + corner] = (origin[chart] + padding + 0.5 + (p - bbox_min[chart]) scale) / R in double, rounded
  *     once; origin [C,2] int64.
  *   sr_uv_overlap_count: total [1] = the number of texel centres (sr_uv_rasterize's convention) that lie strictly inside two or more
- *     non-degenerate UV triangles (every barycentric > eps); count [R,R] int32 = triangles per texel. */
+ *     non-degenerate UV triangles (every barycentric > eps); count [R,R] int32 = triangles per texel.
+ * Quadric-optimal placement of the cluster representatives (the clustering, the faces and the map are unchanged):
+ *   sr_meshprep_cell_faces: slot [3F]; slot[3 f + k] = vertex_map[faces[f][k]] unless an earlier corner of face f has that cell or the
+ *     row has an index outside [0, V): then C.  A stable sort of slot by value lists, per cell, every face that touches it once, in
+ *     ascending face index.
+ *   sr_meshprep_cell_quadric: per cell c of `cells` [C] (its grid key; ijk = key mod nx, key / nx mod ny, key / (nx ny)), from the faces
+ *     face_slots[face_offsets[c] .. face_offsets[c + 1]) / 3 (positions of the sorted slots) and the members order[offsets[c] ..
+ *     offsets[c + 1]) as for sr_meshprep_cell_mean, all in double from the float32 inputs: every face with area adds w n n^T to A and
+ *     w d n to b (N = (p1 - p0) x (p2 - p0), L = |N|, n = N / L, w = L / 2, d = n . p0; L = 0 or not finite adds nothing); entry e of
+ *     the list goes to partial sum e mod 16, each partial sum runs in list order, and the 16 meet pairwise (1, 2, 4, 8 apart).  m = the
+ *     cell mean, lambda = reg trace(A) / 3, x = m + (A + lambda I)^-1 (b - A m) by Cholesky; lambda > 0 false, or x not finite: x = m
+ *     and SR_QUADRIC_NO_PLANES.  x is clamped per component to [lo + i cell, lo + (i + 1) cell] (SR_QUADRIC_CLAMPED when that moved
+ *     it) and rounded once: out [C,3]; flags [C] int32; shift [C] float32 = |x - m| / cell.  reg > 0 and finite, cell > 0.
+ *   sr_meshprep_face_flips: for g in [0, Fn), new face new_faces[g] at new_verts [Vn,3] against old face faces[source[g]] at verts:
+ *     counts [2] int64 = (faces whose unnormalised normals have a negative dot product, faces whose new normal is zero). */
+#define SR_QUADRIC_CLAMPED 1
+#define SR_QUADRIC_NO_PLANES 2
+int sr_meshprep_cell_faces(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t C, int64_t* slot, void* stream);
+int sr_meshprep_cell_quadric(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* face_slots, const int64_t* face_offsets,
+                             const int64_t* order, const int64_t* offsets, const int64_t* cells, int64_t C, const float* lo, float cell, int64_t nx,
+                             int64_t ny, double reg, float* out, int32_t* flags, float* shift, void* stream);
+int sr_meshprep_face_flips(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* new_verts, int64_t Vn,
+                           const int64_t* new_faces, const int64_t* source, int64_t Fn, int64_t* counts, void* stream);
 int sr_meshprep_bounds(const float* verts, int64_t V, int32_t* box, void* stream);
 int sr_meshprep_cell_keys(const float* verts, int64_t V, const float* lo, float cell, int64_t nx, int64_t ny, int64_t nz, int64_t* key, void* stream);
 int sr_meshprep_cell_mean(const float* verts, int64_t V, const int64_t* order, const int64_t* offsets, int64_t C, float* out, void* stream);

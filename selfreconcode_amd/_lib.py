@@ -256,6 +256,9 @@ SIGNATURES = {
     "sr_meshprep_cell_mean": [_vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "sr_meshprep_face_keys": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
     "sr_meshprep_face_first": [_vp, _vp, _vp, _i64, _vp, _vp],
+    "sr_meshprep_cell_faces": [_vp, _i64, _vp, _i64, _i64, _vp, _vp],
+    "sr_meshprep_cell_quadric": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.c_float, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp],
+    "sr_meshprep_face_flips": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
     "sr_chart_classify": [_vp, _i64, _vp, _i64, _vp, _vp],
     "sr_chart_edge_keys": [_vp, _i64, _i64, _vp, _vp, _vp],
     "sr_chart_hook": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],

@@ -7,14 +7,17 @@
 //    occupied cell, its members summed in ascending original index in double), sr_meshprep_face_keys (remapped corners, the sorted
 //    triple as a two-part key, -1 for a collapsed face) and sr_meshprep_face_first (first of every run of equal keys after two stable
 //    sorts = the lowest original index).
+//  * quadric placement (optional): sr_meshprep_cell_faces (cell-face incidence as sortable slots), sr_meshprep_cell_quadric (16 lanes
+//    per cell: the cell's summed plane quadrics, the regularised 3 x 3 solve about the cell mean, the clamp to the cell's box) and
+//    sr_meshprep_face_flips (surviving faces whose normal turned over or vanished).
 //  * unwrap: sr_chart_classify (dominant axis and sign of the float64 normal, every product and difference rounded on its own),
 //    sr_chart_edge_keys (half-edge keys that carry the class, so equal keys = same edge and same class), sr_chart_hook / sr_chart_jump
 //    (connected components by min-label hooking of roots and pointer doubling, both double-buffered: the number of passes is a function
 //    of the input alone), sr_chart_bbox (per-chart box of the projected corners) and sr_chart_uv.
 //  * sr_uv_overlap_count: texel centres strictly inside two or more UV triangles, with sr_uv_rasterize's texel convention.
 //
-// Stream / gather work bound by HBM and by atomics on a few addresses; no float atomics anywhere: sums are sequential per thread, the
-// atomics are integer adds and min / max, so two calls give identical bits.
+// Stream / gather work bound by HBM and by atomics on a few addresses; no float atomics anywhere: sums are sequential per thread (the
+// quadric sums: per lane, then a butterfly of fixed shape), the atomics are integer adds and min / max, so two calls give identical bits.
 #include "sr_common.h"
 #include "uv_device.h"
 
@@ -122,15 +125,158 @@ __global__ __launch_bounds__(256) void face_first(const int64_t* __restrict__ ke
   }
 }
 
-// ---------------------------------------------------------------------------------------------- unwrap
-// class = 2 axis + (negative ? 1 : 0) of the unnormalised normal (b - a) x (c - a) in double, no contraction: the restatement rounds
-// every product and every difference on its own and must agree on ties
-__device__ int32_t face_class(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc) {
+// n = (b - a) x (c - a) in double from float32 corners with every product and every difference rounded on its own (no contraction: a
+// fused a b - round(c d) would turn the exact zero of a degenerate face into a rounding error, and a numpy restatement into a stranger)
+__device__ __forceinline__ void face_normal(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc, double n[3]) {
 #pragma clang fp contract(off)                      // (plain operators under this pragma: __dmul_rn / __dsub_rn are inline functions that contract)
   const double ux = (double)pb[0] - (double)pa[0], uy = (double)pb[1] - (double)pa[1], uz = (double)pb[2] - (double)pa[2];
   const double vx = (double)pc[0] - (double)pa[0], vy = (double)pc[1] - (double)pa[1], vz = (double)pc[2] - (double)pa[2];
   const double yz = uy * vz, zy = uz * vy, zx = uz * vx, xz = ux * vz, xy = ux * vy, yx = uy * vx;
-  const double n[3] = {yz - zy, zx - xz, xy - yx};
+  n[0] = yz - zy; n[1] = zx - xz; n[2] = xy - yx;
+}
+
+// ---------------------------------------------------------------------------------------------- quadric placement
+// slot[3 f + k] = the cell of corner k, or C (an empty slot) when an earlier corner of the face has that cell already or the row is not
+// a face: sorted by cell (stable), every cell's list holds each face that touches it once, in ascending face index
+__global__ __launch_bounds__(256) void cell_face_slots(const int64_t* __restrict__ faces, int64_t F, const int64_t* __restrict__ vmap, int64_t V, int64_t C,
+                                                        int64_t* __restrict__ slot) {
+  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
+    int64_t x = C, y = C, z = C;
+    if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) {
+      x = vmap[a]; y = vmap[b]; z = vmap[c];
+      if (x < 0 || x > C) x = C;
+      if (y < 0 || y > C || y == x) y = C;
+      if (z < 0 || z > C || z == x || z == y) z = C;
+    }
+    slot[f * 3] = x; slot[f * 3 + 1] = y; slot[f * 3 + 2] = z;
+  }
+}
+
+#define SR_QUADRIC_LANES 16                            // lanes per cell: part of the stated order of the sums, not a tuning knob
+
+__device__ __forceinline__ double group_sum(double v) {
+  for (int m = SR_QUADRIC_LANES / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, SR_QUADRIC_LANES);   // (a + b = b + a: every lane ends with the same bits)
+  return v;
+}
+
+// 16 lanes per occupied cell.  Lane l sums the plane quadrics of entries l, l + 16, ... of the cell's face list in that order, the 16
+// partial sums meet in a butterfly of fixed shape, and every lane then holds A (6 numbers) and b (3).  The mean is summed by every
+// lane on its own in cell_mean's order (the loads are broadcasts), the 3 x 3 system is solved by Cholesky, lane 0 stores.  The order of
+// every sum depends on the lists alone, not on the grid.
+__global__ __launch_bounds__(256) void cell_quadric(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                                     const int64_t* __restrict__ face_slots, const int64_t* __restrict__ face_offsets,
+                                                     const int64_t* __restrict__ order, const int64_t* __restrict__ offsets,
+                                                     const int64_t* __restrict__ cells, int64_t C, const float* __restrict__ lo, float cell, int64_t nx,
+                                                     int64_t ny, double reg, float* __restrict__ out, int32_t* __restrict__ flags,
+                                                     float* __restrict__ shift) {
+  const int lane = threadIdx.x & (SR_QUADRIC_LANES - 1);
+  const int64_t group = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / SR_QUADRIC_LANES;
+  const int64_t groups = (int64_t)gridDim.x * blockDim.x / SR_QUADRIC_LANES;
+  const double l0[3] = {(double)lo[0], (double)lo[1], (double)lo[2]}, h = (double)cell;
+  for (int64_t c = group; c < C; c += groups) {
+    double xx = 0., xy = 0., xz = 0., yy = 0., yz = 0., zz = 0., bx = 0., by = 0., bz = 0.;
+    const int64_t fs = max(face_offsets[c], (int64_t)0), fe = min(face_offsets[c + 1], 3 * F);
+    for (int64_t e = fs + lane; e < fe; e += SR_QUADRIC_LANES) {
+      const int64_t s = face_slots[e];
+      if (s < 0 || s >= 3 * F) continue;
+      const int64_t f = s / 3, i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+      if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) continue;
+      const double px = (double)verts[i0 * 3], py = (double)verts[i0 * 3 + 1], pz = (double)verts[i0 * 3 + 2];
+      double N[3];
+      face_normal(verts + i0 * 3, verts + i1 * 3, verts + i2 * 3, N);
+      const double L = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+      if (!(L > 0.) || !isfinite(L)) continue;
+      const double n0 = N[0] / L, n1 = N[1] / L, n2 = N[2] / L, w = 0.5 * L, d = n0 * px + n1 * py + n2 * pz;
+      const double w0 = w * n0, w1 = w * n1, w2 = w * n2, wd = w * d;
+      xx += w0 * n0; xy += w0 * n1; xz += w0 * n2; yy += w1 * n1; yz += w1 * n2; zz += w2 * n2;
+      bx += wd * n0; by += wd * n1; bz += wd * n2;
+    }
+    xx = group_sum(xx); xy = group_sum(xy); xz = group_sum(xz); yy = group_sum(yy); yz = group_sum(yz); zz = group_sum(zz);
+    bx = group_sum(bx); by = group_sum(by); bz = group_sum(bz);
+
+    double m[3] = {0., 0., 0.};
+    int64_t n = 0;
+    const int64_t ms = max(offsets[c], (int64_t)0), me = min(offsets[c + 1], V);
+    for (int64_t k = ms; k < me; ++k) {
+      const int64_t v = order[k];
+      if (v < 0 || v >= V) continue;
+      m[0] += (double)verts[v * 3]; m[1] += (double)verts[v * 3 + 1]; m[2] += (double)verts[v * 3 + 2]; ++n;
+    }
+    const double cnt = n > 0 ? (double)n : 1.;
+    m[0] /= cnt; m[1] /= cnt; m[2] /= cnt;
+
+    int32_t flag = 0;
+    double x[3] = {m[0], m[1], m[2]};
+    const double lam = reg * (xx + yy + zz) / 3.;
+    if (lam > 0.) {
+      // (A + lam I) y = b - A m by Cholesky: the pivots are at least lam
+      const double r0 = bx - (xx * m[0] + xy * m[1] + xz * m[2]), r1 = by - (xy * m[0] + yy * m[1] + yz * m[2]),
+                   r2 = bz - (xz * m[0] + yz * m[1] + zz * m[2]);
+      const double g00 = sqrt(xx + lam), g10 = xy / g00, g20 = xz / g00;
+      const double g11 = sqrt(yy + lam - g10 * g10), g21 = (yz - g20 * g10) / g11;
+      const double g22 = sqrt(zz + lam - g20 * g20 - g21 * g21);
+      const double t0 = r0 / g00, t1 = (r1 - g10 * t0) / g11, t2 = (r2 - g20 * t0 - g21 * t1) / g22;
+      const double y2 = t2 / g22, y1 = (t1 - g21 * y2) / g11, y0 = (t0 - g10 * y1 - g20 * y2) / g00;
+      x[0] += y0; x[1] += y1; x[2] += y2;
+      if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) { x[0] = m[0]; x[1] = m[1]; x[2] = m[2]; flag |= SR_QUADRIC_NO_PLANES; }
+    } else {
+      flag |= SR_QUADRIC_NO_PLANES;
+    }
+    const int64_t key = cells[c];
+    const int64_t ijk[3] = {key % nx, (key / nx) % ny, key / (nx * ny)};
+    double s2 = 0.;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const double wlo = l0[k] + (double)ijk[k] * h, whi = l0[k] + (double)(ijk[k] + 1) * h;
+      if (x[k] < wlo) { x[k] = wlo; flag |= SR_QUADRIC_CLAMPED; }
+      if (x[k] > whi) { x[k] = whi; flag |= SR_QUADRIC_CLAMPED; }
+      s2 += (x[k] - m[k]) * (x[k] - m[k]);
+    }
+    if (lane == 0) {
+      out[c * 3] = (float)x[0]; out[c * 3 + 1] = (float)x[1]; out[c * 3 + 2] = (float)x[2];
+      flags[c] = flag;
+      shift[c] = (float)(sqrt(s2) / h);
+    }
+  }
+}
+
+// per surviving face: the normal at the new positions against the normal of the face it comes from (both unnormalised, in double).
+// counts[0] += the dot product is negative, counts[1] += the new normal is zero.
+__global__ __launch_bounds__(256) void face_flips(const float* __restrict__ verts, int64_t V, const int64_t* __restrict__ faces, int64_t F,
+                                                   const float* __restrict__ new_verts, int64_t Vn, const int64_t* __restrict__ new_faces,
+                                                   const int64_t* __restrict__ source, int64_t Fn, unsigned long long* __restrict__ counts) {
+  int32_t flipped = 0, flat = 0;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < Fn; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = source[g];
+    if (f < 0 || f >= F) continue;
+    double N[2][3];
+    bool ok = true;
+#pragma unroll
+    for (int side = 0; side < 2; ++side) {
+      const float* __restrict__ p = side ? new_verts : verts;
+      const int64_t* __restrict__ t = side ? new_faces + g * 3 : faces + f * 3;
+      const int64_t lim = side ? Vn : V, a = t[0], b = t[1], c = t[2];
+      if (a < 0 || b < 0 || c < 0 || a >= lim || b >= lim || c >= lim) { ok = false; break; }
+      face_normal(p + a * 3, p + b * 3, p + c * 3, N[side]);
+    }
+    if (!ok) continue;
+    if (N[1][0] == 0. && N[1][1] == 0. && N[1][2] == 0.) ++flat;
+    else if (N[0][0] * N[1][0] + N[0][1] * N[1][1] + N[0][2] * N[1][2] < 0.) ++flipped;
+  }
+  for (int m = SR_WAVE / 2; m > 0; m >>= 1) { flipped += __shfl_xor(flipped, m, SR_WAVE); flat += __shfl_xor(flat, m, SR_WAVE); }
+  if ((threadIdx.x & (SR_WAVE - 1)) == 0) {
+    if (flipped) atomicAdd(counts, (unsigned long long)flipped);
+    if (flat) atomicAdd(counts + 1, (unsigned long long)flat);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- unwrap
+// class = 2 axis + (negative ? 1 : 0) of the unnormalised normal (b - a) x (c - a) in double, no contraction: the restatement rounds
+// every product and every difference on its own and must agree on ties
+__device__ int32_t face_class(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc) {
+  double n[3];
+  face_normal(pa, pb, pc, n);
   int k = 0;
   if (fabs(n[1]) > fabs(n[k])) k = 1;
   if (fabs(n[2]) > fabs(n[k])) k = 2;                 // (strict: the lowest axis wins a tie, and a zero normal stays +x)
@@ -309,6 +455,35 @@ extern "C" int sr_meshprep_face_keys(const int64_t* faces, int64_t F, const int6
 extern "C" int sr_meshprep_face_first(const int64_t* key_hi, const int64_t* key_lo, const int64_t* perm, int64_t F, uint8_t* keep, void* stream) {
   if (!key_hi || !key_lo || !perm || !keep || F <= 0) return SR_EINVAL;
   hipLaunchKernelGGL(face_first, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, key_hi, key_lo, perm, F, keep);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_cell_faces(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t C, int64_t* slot, void* stream) {
+  if (!faces || !vertex_map || !slot || F <= 0 || V <= 0 || C <= 0) return SR_EINVAL;
+  hipLaunchKernelGGL(cell_face_slots, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, vertex_map, V, C, slot);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_cell_quadric(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* face_slots,
+                                        const int64_t* face_offsets, const int64_t* order, const int64_t* offsets, const int64_t* cells, int64_t C,
+                                        const float* lo, float cell, int64_t nx, int64_t ny, double reg, float* out, int32_t* flags, float* shift,
+                                        void* stream) {
+  if (!verts || !faces || !face_slots || !face_offsets || !order || !offsets || !cells || !lo || !out || !flags || !shift || V <= 0 || F <= 0 ||
+      C <= 0 || !(cell > 0.f) || nx <= 0 || ny <= 0 || !(reg > 0.) || !(reg < INFINITY))
+    return SR_EINVAL;
+  if (F > INT64_MAX / 3 || C > INT64_MAX / SR_QUADRIC_LANES || (__int128)nx * ny >= ((__int128)1 << 62)) return SR_EINVAL;
+  hipLaunchKernelGGL(cell_quadric, dim3(sr_stream_grid(C * SR_QUADRIC_LANES, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, face_slots,
+                     face_offsets, order, offsets, cells, C, lo, cell, nx, ny, reg, out, flags, shift);
+  return sr_launch_status();
+}
+
+extern "C" int sr_meshprep_face_flips(const float* verts, int64_t V, const int64_t* faces, int64_t F, const float* new_verts, int64_t Vn,
+                                      const int64_t* new_faces, const int64_t* source, int64_t Fn, int64_t* counts, void* stream) {
+  if (!verts || !faces || !new_verts || !new_faces || !source || !counts || V <= 0 || F <= 0 || Vn <= 0 || Fn <= 0) return SR_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return SR_ELAUNCH;
+  hipLaunchKernelGGL(face_flips, dim3(sr_stream_grid(Fn, 256)), dim3(256), 0, st, verts, V, faces, F, new_verts, Vn, new_faces, source, Fn,
+                     (unsigned long long*)counts);
   return sr_launch_status();
 }
 

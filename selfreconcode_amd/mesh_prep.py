@@ -1,15 +1,20 @@
 """Template preparation for the texture stage, on the GPU: what the reference's README leaves to the user ("you need to simplify and
 parameterize the template mesh tmp.ply yourself, then save the result mesh as .../template/uvmap.obj").
 
-    simplify_mesh / simplify_to   vertex clustering on a uniform grid (87k-196k marching-cubes vertices -> a face budget)
+    simplify_mesh / simplify_to   vertex clustering on a uniform grid (87k-196k marching-cubes vertices -> a face budget); the new
+                                  vertices at the cell means (default) or, placement="quadric", at the quadric optima of their cells
+    simplify_quality              surface distances and volume ratio between a simplified mesh and its source
     unwrap_charts                 box projection: charts = connected faces of one dominant normal axis and sign, shelf-packed
     prepare_template              extract -> simplify -> unwrap -> template/uvmap.obj
 
 The reference has no code for this step and pytorch3d / xatlas are not dependencies, so the semantics are this package's own (DESIGN.md
 3.15: stated, unpinned) and are held to a float64 numpy restatement by the tests.  Known limits, also in DESIGN: the stretch of box
 projection (UV area / surface area of a face is |n_axis| / |n|, between 1 / sqrt(3) and 1), seams at every change of the dominant axis,
-vertices placed at cell means rather than quadric optima, and no repair of a chart that overlaps itself in projection -- that is
-counted (`overlap_texels`), not fixed.
+and no repair of a chart that overlaps itself in projection -- that is counted (`overlap_texels`), not fixed.  The default placement
+puts a vertex at its cell's mean, which lies inside the hull of the members: the body shrinks and creases are rounded off.
+placement="quadric" moves it to the regularised minimiser of the cell's plane quadrics instead (Lindstrom's out-of-core
+simplification), clamped to the cell's box: two clamped neighbours can meet on their shared wall; boundary-edge quadrics for open meshes,
+edge collapse or any other change of connectivity, and attribute-aware quadrics are out of scope.
 """
 import os
 from collections import namedtuple
@@ -25,6 +30,7 @@ ChartAtlas = namedtuple("ChartAtlas", "vt ft chart labels bbox_min extent origin
 PreparedTemplate = namedtuple("PreparedTemplate", "mesh atlas obj_path source_faces")
 
 BISECT_STEPS = 16
+PLACEMENTS = ("mean", "quadric")
 PACK_STEPS = 24
 
 
@@ -34,13 +40,26 @@ def _grid(verts, cell):
 
 
 def _clustered(verts, faces, lo, n, cell):
-    """(vertex_map, number of cells, remapped faces, keep) of one grid."""
+    """(vertex_map, the occupied cells' keys, remapped faces, keep) of one grid."""
     cells, vmap = mp.cluster(mp.cell_keys(verts, lo, cell, n))
     remapped, keep = mp.surviving_faces(faces, vmap, cells.shape[0])
-    return vmap, cells.shape[0], remapped, keep
+    return vmap, cells, remapped, keep
 
 
-def simplify_mesh(verts, faces, cell):
+def _placement(placement, reg):
+    """The checked (placement, reg): ValueError for a placement that is not one of PLACEMENTS or a reg that is not finite and positive."""
+    if placement not in PLACEMENTS:
+        raise ValueError(f"placement must be one of {PLACEMENTS}, got {placement!r}")
+    try:
+        reg = float(reg)
+    except (TypeError, ValueError):
+        raise ValueError(f"reg must be a finite positive number, got {reg!r}") from None
+    if not (np.isfinite(reg) and reg > 0):
+        raise ValueError(f"reg must be a finite positive number, got {reg}")
+    return placement, reg
+
+
+def simplify_mesh(verts, faces, cell, placement="mean", reg=1e-3, report=None):
     """Vertex clustering of verts [V,3] float32 / faces [F,3] int64 (GPU tensors) on a uniform grid of side `cell`.
 
     Faces with a negative index are dropped first.  With lo the per-axis float32 minimum, a vertex lies in cell ijk = floor((v - lo) /
@@ -49,7 +68,21 @@ def simplify_mesh(verts, faces, cell):
     gives old -> new.  Faces are remapped; a face with a repeated corner is dropped, and of the faces with the same unordered vertex set
     the one with the lowest original index stays.  Survivors keep their corner order and their relative order; new vertices no face
     references are kept.  ValueError for cell <= 0, non-finite vertices or a grid of 2^62 cells or more.  Two calls give identical
-    bits.  -> SimplifiedMesh(verts [Vn,3], faces [Fn,3], vertex_map [V], cell)."""
+    bits.  -> SimplifiedMesh(verts [Vn,3], faces [Fn,3], vertex_map [V], cell).
+
+    placement="quadric" changes the positions only -- the clustering, vertex_map, the faces and their order are those of "mean".  Every
+    original face with area feeds its plane quadric (w n n^T, w d n; w its area) once to each distinct cell among its corners; a cell's
+    vertex goes to x = m + (A + lambda I)^-1 (b - A m), m its mean and lambda = reg trace(A) / 3, clamped per component to the cell's
+    box and rounded once (mesh_prep_ops.cell_quadric_optima).  A cell no face with area touches stays at its mean.
+    `reg` = 1e-3 is a documented default, not a tuned one: it keeps the directions the planes leave free (a flat patch, a straight
+    crease) at the mean, with a condition number of at most 3 / reg.  ValueError, before any GPU work, for another placement or a
+    reg that is not finite and positive.
+
+    `report`, a dict, receives placement, cells, clamped, no_planes (cells at the clamp / without a usable quadric; 0 for "mean"),
+    max_shift (the largest |x - m| in units of the cell), and flipped / zero_area: the surviving faces whose normal at the new positions
+    points against the normal of the original face they come from, or has vanished (mesh_prep_ops.face_flips, either placement).
+    Filling it costs one launch and three small device -> host copies."""
+    placement, reg = _placement(placement, reg)
     _lib.require_gpu(verts, faces)
     verts = _lib.f32c(verts)
     faces = mp.clean_faces(faces)
@@ -57,21 +90,45 @@ def simplify_mesh(verts, faces, cell):
     if not cell > 0:
         raise ValueError(f"cell must be positive, got {cell}")
     lo, n = _grid(verts, cell)
-    vmap, C, remapped, keep = _clustered(verts, faces, lo, n, cell)
-    return SimplifiedMesh(mp.cell_means(verts, vmap, C), remapped[keep].contiguous(), vmap, cell)
+    vmap, cells, remapped, keep = _clustered(verts, faces, lo, n, cell)
+    C = cells.shape[0]
+    flags = shift = None
+    if placement == "quadric":
+        new_verts, flags, shift = mp.cell_quadric_optima(verts, faces, vmap, cells, lo, cell, n, reg)
+    else:
+        new_verts = mp.cell_means(verts, vmap, C)
+    mesh = SimplifiedMesh(new_verts, remapped[keep].contiguous(), vmap, cell)
+    if report is not None:
+        _fill_report(report, placement, verts, faces, mesh, keep.nonzero().view(-1), flags, shift)
+    return mesh
 
 
-def simplify_to(verts, faces, target_faces, probes=None):
+def _fill_report(report, placement, verts, faces, mesh, source, flags, shift):
+    clamped = no_planes = 0
+    max_shift = 0.
+    if flags is not None:
+        clamped, no_planes = torch.stack([((flags & mp.QUADRIC_CLAMPED) != 0).sum(), ((flags & mp.QUADRIC_NO_PLANES) != 0).sum()]).tolist()
+        max_shift = float(shift.max())
+    flipped, zero_area = mp.face_flips(verts, faces, mesh.verts, mesh.faces, source)
+    report.update(placement=placement, cells=int(mesh.verts.shape[0]), clamped=clamped, no_planes=no_planes, flipped=flipped, zero_area=zero_area,
+                  max_shift=max_shift)
+
+
+def simplify_to(verts, faces, target_faces, probes=None, placement="mean", reg=1e-3, report=None):
     """simplify_mesh at the smallest probed cell that leaves at most `target_faces` faces.  A mesh that is within the budget already
     comes back cleaned (no negative rows) with the identity map and cell 0.  Otherwise the cell is bisected geometrically in [d / 1024,
     d / 2], d the longest side of the box, in 16 steps of keys -> count of surviving faces (no positions); ValueError if even d / 2
-    leaves more.  `probes`, a list, receives every (cell, face count) tried, in order."""
+    leaves more.  `probes`, a list, receives every (cell, face count) tried, in order.  `placement`, `reg` and `report` are
+    simplify_mesh's; the bisection never needs positions, so the cell, the probes and the faces are the same for both placements."""
+    placement, reg = _placement(placement, reg)
     _lib.require_gpu(verts, faces)
     verts = _lib.f32c(verts)
     faces = mp.clean_faces(faces)
     target = int(target_faces)
     if faces.shape[0] <= target:
         mp.mesh_bounds(verts)                                            # (the refusal of non-finite vertices holds here too)
+        if report is not None:                                           # (nothing moved: every vertex is its own cell)
+            report.update(placement=placement, cells=int(verts.shape[0]), clamped=0, no_planes=0, flipped=0, zero_area=0, max_shift=0.)
         return SimplifiedMesh(verts, faces, torch.arange(verts.shape[0], dtype=torch.int64, device=verts.device), 0.)
     lo, hi = mp.mesh_bounds(verts)
     lo_h, hi_h = lo.cpu().numpy(), hi.cpu().numpy()
@@ -96,7 +153,28 @@ def simplify_to(verts, faces, target_faces, probes=None):
             b = best = cell
         else:
             a = cell
-    return simplify_mesh(verts, faces, best)
+    return simplify_mesh(verts, faces, best, placement, reg, report)
+
+
+def signed_volume(verts, faces):
+    """The signed volume sum p0 . (p1 x p2) / 6 of a triangle mesh (positive for outward normals), in double: a 0-d GPU tensor."""
+    p = verts.double()[faces]
+    return (p[:, 0] * torch.linalg.cross(p[:, 1], p[:, 2])).sum() / 6.
+
+
+def simplify_quality(mesh, verts, faces, samples=200_000, seed=0):
+    """How far a SimplifiedMesh is from its source verts / faces, as a dict of Python floats: `simplified_to_source` and
+    `source_to_simplified` with mean / rms / max of the exact distances of `samples` area-weighted surface samples of one mesh to the
+    other (evaluate.surface_metrics, no alignment), `chamfer`, and `volume_source`, `volume_simplified`, `volume_ratio` = simplified /
+    source of the signed volumes (below 1: the simplified body has shrunk)."""
+    from .evaluate import surface_metrics
+    _lib.require_gpu(mesh.verts, mesh.faces, verts, faces)
+    verts = _lib.f32c(verts)
+    faces = mp.clean_faces(faces)
+    m = surface_metrics((mesh.verts, mesh.faces), (verts, faces), samples=samples, seed=seed)
+    vs, vm = torch.stack([signed_volume(verts, faces), signed_volume(mesh.verts, mesh.faces)]).tolist()
+    return {"simplified_to_source": m["pred_to_gt"], "source_to_simplified": m["gt_to_pred"], "chamfer": m["chamfer"], "volume_source": vs,
+            "volume_simplified": vm, "volume_ratio": vm / vs if vs != 0 else float("nan")}
 
 
 def _shelves(size, R):
@@ -186,18 +264,20 @@ def unwrap_charts(verts, faces, resolution=1680, padding=2):
                       mp.uv_overlap_count(vt, ft, R))
 
 
-def prepare_template(net, out_root, ratio=None, target_faces=20000, resolution=1680, padding=2, TmpVs=None, Tmpfs=None):
+def prepare_template(net, out_root, ratio=None, target_faces=20000, resolution=1680, padding=2, TmpVs=None, Tmpfs=None, placement="mean", reg=1e-3,
+                     report=None):
     """Extracts the template of `net` with discretizeSDF(ratio, None, 0.) as infer does (all ratios 1 unless given; or takes TmpVs /
     Tmpfs), simplifies it to `target_faces`, unwraps it and writes out_root/template/uvmap.obj, the file export_texture reads.
     -> PreparedTemplate(mesh SimplifiedMesh, atlas ChartAtlas, obj_path, source_faces: the faces of the extracted template).
 
     20000 faces is a default, not a measured optimum: at 1680^2 texels with about half of the atlas covered it leaves some 70 texels
-    per face."""
+    per face.  `placement`, `reg` and `report` go to simplify_to."""
     from .mesh_io import write_obj_uv
     from .posed import FULL_RATIO
+    placement, reg = _placement(placement, reg)
     if TmpVs is None or Tmpfs is None:
         TmpVs, Tmpfs = net.discretizeSDF(ratio or FULL_RATIO, None, 0.)
-    mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces)
+    mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces, placement=placement, reg=reg, report=report)
     atlas = unwrap_charts(mesh.verts, mesh.faces, resolution, padding)
     folder = os.path.join(out_root, "template")
     os.makedirs(folder, exist_ok=True)

@@ -7,6 +7,7 @@ from . import _lib
 from .ops import _faces
 
 MAX_ROUNDS = 4096          # passes of the component search before it is declared stuck (a 40 000-face strip needs about 20)
+QUADRIC_CLAMPED, QUADRIC_NO_PLANES = 1, 2          # bits of cell_quadric_optima's flags (SR_QUADRIC_* of the header)
 
 
 def _verts2(verts):
@@ -76,17 +77,64 @@ def cluster(key):
     return cells, vmap.contiguous()
 
 
+def _lists(key, C):
+    """(order, offsets [C + 1]): the positions of `key` grouped by value in [0, C), each group in ascending position (a stable sort);
+    positions whose key is C or more come after offsets[C]."""
+    order = torch.sort(key, stable=True)[1].contiguous()
+    offsets = torch.zeros((C + 1,), dtype=torch.int64, device=key.device)
+    offsets[1:] = torch.cumsum(torch.bincount(key, minlength=C)[:C], 0)
+    return order, offsets
+
+
 def cell_means(verts, vertex_map, C):
     """[C,3] float32: the mean of every cell's members, summed in ascending original index in double (sr_meshprep_cell_mean)."""
     _lib.require_gpu(verts, vertex_map)
     verts = _verts2(verts)
-    vmap = _lib.i64c(vertex_map)
-    order = torch.sort(vmap, stable=True)[1].contiguous()
-    offsets = torch.zeros((C + 1,), dtype=torch.int64, device=verts.device)
-    offsets[1:] = torch.cumsum(torch.bincount(vmap, minlength=C), 0)
+    order, offsets = _lists(_lib.i64c(vertex_map), C)
     out = torch.empty((C, 3), dtype=torch.float32, device=verts.device)
     _lib.launch("sr_meshprep_cell_mean", verts, verts, verts.shape[0], order, offsets, C, out)
     return out
+
+
+def cell_quadric_optima(verts, faces, vertex_map, cells, lo, cell, n, reg=1e-3):
+    """(positions [C,3] float32, flags [C] int32, shift [C] float32) of the cells `cells` [C] (ascending keys of the grid lo / cell / n
+    that vertex_map [V] indexes): every cell's representative at the minimiser of the summed plane quadrics of the original faces that
+    touch the cell plus reg trace(A) / 3 |x - mean|^2, clamped to the cell's box (sr_meshprep_cell_faces, a stable sort,
+    sr_meshprep_cell_quadric).  flags: QUADRIC_CLAMPED, QUADRIC_NO_PLANES (such a cell sits at its mean); shift = |x - mean| / cell.
+    Rows of `faces` with a negative index are skipped.  No device -> host copy."""
+    _lib.require_gpu(verts, faces, vertex_map, cells, lo)
+    verts = _verts2(verts); faces = _faces(faces); vmap = _lib.i64c(vertex_map); cells = _lib.i64c(cells)
+    C, dev = cells.shape[0], verts.device
+    if faces.shape[0] == 0:
+        faces = torch.full((1, 3), -1, dtype=torch.int64, device=dev)            # (no face: every cell keeps its mean)
+    F = faces.shape[0]
+    slot = torch.empty((3 * F,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_meshprep_cell_faces", verts, faces, F, vmap, vmap.shape[0], C, slot)
+    face_slots, face_offsets = _lists(slot, C)
+    order, offsets = _lists(vmap, C)
+    out = torch.empty((C, 3), dtype=torch.float32, device=dev)
+    flags = torch.empty((C,), dtype=torch.int32, device=dev); shift = torch.empty((C,), dtype=torch.float32, device=dev)
+    _lib.launch("sr_meshprep_cell_quadric", verts, verts, verts.shape[0], faces, F, face_slots, face_offsets, order, offsets, cells, C, _lib.f32c(lo),
+                float(np.float32(cell)), n[0], n[1], float(reg), out, flags, shift)
+    return out, flags, shift
+
+
+def face_flips(verts, faces, new_verts, new_faces, source):
+    """(flipped, zero_area) as Python ints: of the faces new_faces [Fn,3] at new_verts, how many have a normal whose dot product with
+    the normal of faces[source[g]] at verts is negative, and how many have no area at all (sr_meshprep_face_flips; the normals are
+    unnormalised cross products in double).  One device -> host copy."""
+    _lib.require_gpu(verts, faces, new_verts, new_faces, source)
+    verts = _verts2(verts); new_verts = _verts2(new_verts)
+    faces = _faces(faces); new_faces = _faces(new_faces); source = _lib.i64c(source)
+    Fn = new_faces.shape[0]
+    if source.shape != (Fn,):
+        raise ValueError(f"source [{Fn}] expected, got {tuple(source.shape)}")
+    if Fn == 0 or faces.shape[0] == 0:
+        return 0, 0
+    counts = torch.empty((2,), dtype=torch.int64, device=verts.device)
+    _lib.launch("sr_meshprep_face_flips", verts, verts, verts.shape[0], faces, faces.shape[0], new_verts, new_verts.shape[0], new_faces, source, Fn, counts)
+    flipped, flat = counts.tolist()
+    return flipped, flat
 
 
 def surviving_faces(faces, vertex_map, Vn):

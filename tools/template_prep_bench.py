@@ -1,5 +1,6 @@
 """Times the template preparation of the texture stage at the fine stage's template size -- cube_sphere(170): 173 402 vertices, 346 800
-faces -> simplify_to(20000) -> unwrap_charts(1680) -- on the GPU, stage by stage.  Wall time around synchronised calls after seconds of
+faces -> simplify_to(20000) -> unwrap_charts(1680) -- on the GPU, stage by stage, the simplification with both vertex placements (and
+their report counts and simplify_quality against the source).  Wall time around synchronised calls after seconds of
 warm-up (these functions read flags and boxes back, so they are host-paced: HIP events around them would say the same).
 
     python tools/template_prep_bench.py [--out profiles/template_prepare.md] [--seconds 2.0]
@@ -50,6 +51,16 @@ def main():
            "rounds": atlas.rounds, "overlap_texels": atlas.overlap_texels}
     res["simplify_mesh_ms"], res["simplify_mesh_runs"] = timed(lambda: mesh_prep.simplify_mesh(v, f, mesh.cell), args.seconds)
     res["simplify_to_ms"], res["simplify_to_runs"] = timed(lambda: mesh_prep.simplify_to(v, f, TARGET), args.seconds)
+    # the quadric placement: the same clustering, two more launches and one more sort; its counts and both placements' distance to the source
+    res["simplify_mesh_quadric_ms"], res["simplify_mesh_quadric_runs"] = timed(lambda: mesh_prep.simplify_mesh(v, f, mesh.cell, placement="quadric"), args.seconds)
+    res["simplify_to_quadric_ms"], res["simplify_to_quadric_runs"] = timed(lambda: mesh_prep.simplify_to(v, f, TARGET, placement="quadric"), args.seconds)
+    res["simplify_mesh_again_ms"], _ = timed(lambda: mesh_prep.simplify_mesh(v, f, mesh.cell), args.seconds)      # (the spread of the first line)
+    for placement in mesh_prep.PLACEMENTS:
+        report = {}
+        m = mesh_prep.simplify_to(v, f, TARGET, placement=placement, report=report)
+        res["report_" + placement] = report
+        res["quality_" + placement] = mesh_prep.simplify_quality(m, v, f)
+        res["sphere_error_" + placement] = float((m.verts.double().norm(dim=1) - 1.).abs().max())            # (the template is the unit sphere)
     res["unwrap_ms"], res["unwrap_runs"] = timed(lambda: mesh_prep.unwrap_charts(mesh.verts, mesh.faces, R), args.seconds)
     res["unwrap_full_size_ms"], _ = timed(lambda: mesh_prep.unwrap_charts(v, f, R), args.seconds)       # the unsimplified template: the kernels at size
     ext = atlas.extent.cpu().numpy()
@@ -61,9 +72,21 @@ def main():
             fh.write(f"| stage (cube_sphere({N}): {res['vertices']} vertices, {res['faces']} faces) | time |\n|---|---|\n")
             fh.write(f"| simplify_mesh at the chosen cell {res['cell']:.5f} -> {res['out_vertices']} vertices, {res['out_faces']} faces | {res['simplify_mesh_ms']:.2f} ms |\n")
             fh.write(f"| simplify_to({TARGET}): {res['probes']} probes + the mesh | {res['simplify_to_ms']:.2f} ms |\n")
+            fh.write(f"| simplify_mesh at that cell, placement=\"quadric\" | {res['simplify_mesh_quadric_ms']:.2f} ms |\n")
+            fh.write(f"| simplify_to({TARGET}), placement=\"quadric\" | {res['simplify_to_quadric_ms']:.2f} ms |\n")
+            fh.write(f"| simplify_mesh at that cell, placement=\"mean\", timed again | {res['simplify_mesh_again_ms']:.2f} ms |\n")
             fh.write(f"| unwrap_charts({R}) of the result: {res['charts']} charts, {res['rounds']} passes of the component search | {res['unwrap_ms']:.2f} ms |\n")
             fh.write(f"| of which pack_charts on the host | {res['pack_host_ms']:.2f} ms |\n")
             fh.write(f"| unwrap_charts({R}) of the unsimplified template | {res['unwrap_full_size_ms']:.2f} ms |\n\n")
+            fh.write("| placement | clamped | no_planes | flipped | zero_area | max_shift | source -> simplified mean / max | simplified -> source mean / max "
+                     "| volume ratio | largest \\| \\|x\\| - 1 \\| of a vertex |\n|---|---|---|---|---|---|---|---|---|---|\n")
+            for placement in mesh_prep.PLACEMENTS:
+                r, q = res["report_" + placement], res["quality_" + placement]
+                fh.write(f"| {placement} | {r['clamped']} | {r['no_planes']} | {r['flipped']} | {r['zero_area']} | {r['max_shift']:.4f} | "
+                         f"{q['source_to_simplified']['mean']:.3g} / {q['source_to_simplified']['max']:.3g} | "
+                         f"{q['simplified_to_source']['mean']:.3g} / {q['simplified_to_source']['max']:.3g} | {q['volume_ratio']:.6f} | "
+                         f"{res['sphere_error_' + placement]:.3g} |\n")
+            fh.write("\n")
             fh.write(json.dumps(res) + "\n")
 
 
