@@ -606,6 +606,49 @@ int sr_chart_uv(const float* verts, int64_t V, const int64_t* faces, int64_t F, 
 int sr_uv_overlap_count(const float* vt, const int64_t* ft, int64_t Vt, int64_t F, int32_t R, double eps, int32_t* count, int64_t* total,
                         void* stream);
 
+/* Edge-collapse decimation of the template (csrc/mesh_collapse.hip; DESIGN.md 3.15: this package's own semantics, unpinned).  One round
+ * on verts [V,3] float32, faces [F,3] (every index in [0, V), no repeated corner) and quadrics [V,10] double (xx xy xz yy yz zz of
+ * sum w n n^T, then sum w d n, then sum w d^2); sorting, unique and compaction happen between the calls (mesh_prep_ops.py).  Integer
+ * atomics only (or, add, 64-bit min).  V <= 2^31 and F <= 2^30 throughout, else SR_EINVAL.
+ *   sr_collapse_vertex_quadrics: quadrics[v] = the plane quadrics (n, w, d as for sr_meshprep_cell_quadric) of the faces slots[offsets[v]
+ *     .. offsets[v + 1]) / 3, summed in that order; slots [3F] = the corners 3 f + c sorted (stably) by the vertex they hold.
+ *   sr_collapse_edge_keys: key [3F] of half-edge 3 f + c (corner c to corner c + 1) = min V + max; -1 in a row that is not a face.
+ *   sr_collapse_edge_heads: unique_key [E] ascending, its run perm[offsets[e] .. offsets[e + 1]) in the sorted half-edges (perm [3F]:
+ *     position -> half-edge): edges [E,2] = (key / V, key mod V), count [E] = the run's length, opposite [E,2] = the vertex opposite
+ *     the run's first and second half-edge (-1: none), locked [V] int32 = 1 on both ends of every edge whose count is not 2 (zeroed
+ *     here first), directed [2E] = a V + b and, E later, b V + a: sorted, they list every vertex's neighbours in ascending order.
+ *   sr_collapse_candidates: per edge (a, b): Q = Q_a + Q_b, m the midpoint, x = m + (A + lambda I)^-1 (b - A m), lambda = reg trace(A)
+ *     / 3, by Cholesky (x = m when lambda > 0 fails or x is not finite); positions [E,3] = x rounded to float32; cost = max(x^T A x -
+ *     2 b^T x + c, 0) at the rounded x in double, rounded to float32.  key [E] = (bits of cost) << 32 | fmix32(e) (murmur3's 32-bit
+ *     finaliser) when the edge is a candidate, else INT64_MAX.  A candidate has count 2, unlocked ends, two distinct opposite vertices
+ *     that are the only common neighbours of a and b (neighbours [2E] = the sorted `directed`, neighbour_offsets [V + 1] into it),
+ *     val(a) + val(b) - 4 >= 3 and val(opposite) - 1 >= 3, and every face at a or b that does not hold the other keeps n_old . n_new
+ *     > flip_cos |n_old| |n_new| and |n_new| > 0 with that corner at x.  reg > 0 and finite, -1 <= flip_cos < 1.
+ *   sr_collapse_min1: m1 [V] = the least key < INT64_MAX over the edges at v, INT64_MAX without one.
+ *   sr_collapse_min2: m2 [V] = min(m1[v], m1[u] over the neighbours u of v); m2 must not be m1.
+ *   sr_collapse_select: selected [E] uint8 = key < INT64_MAX and key == m2[a] == m2[b]; record [2] int64 = (selected, candidates).
+ *   sr_collapse_apply_vertices: for every selected edge, in place: verts[a] = positions[e], quadrics[a] += quadrics[b], target[b] = a
+ *     (target [V] int64; the selected edges must share no endpoint, as those of sr_collapse_select do).
+ *   sr_collapse_apply_faces: out_faces [F,3] = target[faces]; keep [F] uint8 = the three are distinct.
+ *   sr_collapse_map_jump: next[v] = parent[parent[v]]; changed [1] int32 = 1 when some next[v] != parent[v]; next must not be parent. */
+int sr_collapse_vertex_quadrics(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* slots, const int64_t* offsets,
+                                double* quadrics, void* stream);
+int sr_collapse_edge_keys(const int64_t* faces, int64_t F, int64_t V, int64_t* key, void* stream);
+int sr_collapse_edge_heads(const int64_t* unique_key, const int64_t* offsets, int64_t E, const int64_t* perm, const int64_t* faces, int64_t F, int64_t V,
+                           int64_t* edges, int32_t* count, int64_t* opposite, int32_t* locked, int64_t* directed, void* stream);
+int sr_collapse_candidates(const float* verts, int64_t V, const int64_t* faces, int64_t F, const double* quadrics, const int64_t* slots,
+                           const int64_t* offsets, const int64_t* neighbours, const int64_t* neighbour_offsets, const int64_t* edges,
+                           const int32_t* count, const int64_t* opposite, const int32_t* locked, int64_t E, double reg, double flip_cos,
+                           float* positions, int64_t* key, void* stream);
+int sr_collapse_min1(const int64_t* edges, const int64_t* key, int64_t E, int64_t V, int64_t* m1, void* stream);
+int sr_collapse_min2(const int64_t* edges, int64_t E, int64_t V, const int64_t* m1, int64_t* m2, void* stream);
+int sr_collapse_select(const int64_t* edges, const int64_t* key, int64_t E, int64_t V, const int64_t* m2, uint8_t* selected, int64_t* record,
+                       void* stream);
+int sr_collapse_apply_vertices(const int64_t* edges, const float* positions, const uint8_t* selected, int64_t E, float* verts, int64_t V,
+                               double* quadrics, int64_t* target, void* stream);
+int sr_collapse_apply_faces(const int64_t* faces, int64_t F, const int64_t* target, int64_t V, int64_t* out_faces, uint8_t* keep, void* stream);
+int sr_collapse_map_jump(const int64_t* parent, int64_t V, int64_t* next, int32_t* changed, void* stream);
+
 /* Drawing the textured template (csrc/texrender.hip): a mip-mapped UV shader on the fragments of sr_rasterize_meshes.  The semantics
  * are this package's own: stated here, restated in float64 by the tests, unpinned.
  *   Mip buffer: float4 texels, levels concatenated; level 0 has side R, level l + 1 side (R_l + 1) / 2, the last level side 1 (L

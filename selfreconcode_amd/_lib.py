@@ -259,6 +259,16 @@ SIGNATURES = {
     "sr_meshprep_cell_faces": [_vp, _i64, _vp, _i64, _i64, _vp, _vp],
     "sr_meshprep_cell_quadric": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.c_float, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp],
     "sr_meshprep_face_flips": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
+    "sr_collapse_vertex_quadrics": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
+    "sr_collapse_edge_keys": [_vp, _i64, _i64, _vp, _vp],
+    "sr_collapse_edge_heads": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+    "sr_collapse_candidates": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp],
+    "sr_collapse_min1": [_vp, _vp, _i64, _i64, _vp, _vp],
+    "sr_collapse_min2": [_vp, _i64, _i64, _vp, _vp, _vp],
+    "sr_collapse_select": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    "sr_collapse_apply_vertices": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sr_collapse_apply_faces": [_vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "sr_collapse_map_jump": [_vp, _i64, _vp, _vp, _vp],
     "sr_chart_classify": [_vp, _i64, _vp, _i64, _vp, _vp],
     "sr_chart_edge_keys": [_vp, _i64, _i64, _vp, _vp, _vp],
     "sr_chart_hook": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],

@@ -20,6 +20,7 @@
 // quadric sums: per lane, then a butterfly of fixed shape), the atomics are integer adds and min / max, so two calls give identical bits.
 #include "sr_common.h"
 #include "uv_device.h"
+#include "quadric_device.h"
 
 namespace {
 
@@ -125,16 +126,6 @@ __global__ __launch_bounds__(256) void face_first(const int64_t* __restrict__ ke
   }
 }
 
-// n = (b - a) x (c - a) in double from float32 corners with every product and every difference rounded on its own (no contraction: a
-// fused a b - round(c d) would turn the exact zero of a degenerate face into a rounding error, and a numpy restatement into a stranger)
-__device__ __forceinline__ void face_normal(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc, double n[3]) {
-#pragma clang fp contract(off)                      // (plain operators under this pragma: __dmul_rn / __dsub_rn are inline functions that contract)
-  const double ux = (double)pb[0] - (double)pa[0], uy = (double)pb[1] - (double)pa[1], uz = (double)pb[2] - (double)pa[2];
-  const double vx = (double)pc[0] - (double)pa[0], vy = (double)pc[1] - (double)pa[1], vz = (double)pc[2] - (double)pa[2];
-  const double yz = uy * vz, zy = uz * vy, zx = uz * vx, xz = ux * vz, xy = ux * vy, yx = uy * vx;
-  n[0] = yz - zy; n[1] = zx - xz; n[2] = xy - yx;
-}
-
 // ---------------------------------------------------------------------------------------------- quadric placement
 // slot[3 f + k] = the cell of corner k, or C (an empty slot) when an earlier corner of the face has that cell already or the row is not
 // a face: sorted by cell (stable), every cell's list holds each face that touches it once, in ascending face index
@@ -207,22 +198,8 @@ __global__ __launch_bounds__(256) void cell_quadric(const float* __restrict__ ve
     m[0] /= cnt; m[1] /= cnt; m[2] /= cnt;
 
     int32_t flag = 0;
-    double x[3] = {m[0], m[1], m[2]};
-    const double lam = reg * (xx + yy + zz) / 3.;
-    if (lam > 0.) {
-      // (A + lam I) y = b - A m by Cholesky: the pivots are at least lam
-      const double r0 = bx - (xx * m[0] + xy * m[1] + xz * m[2]), r1 = by - (xy * m[0] + yy * m[1] + yz * m[2]),
-                   r2 = bz - (xz * m[0] + yz * m[1] + zz * m[2]);
-      const double g00 = sqrt(xx + lam), g10 = xy / g00, g20 = xz / g00;
-      const double g11 = sqrt(yy + lam - g10 * g10), g21 = (yz - g20 * g10) / g11;
-      const double g22 = sqrt(zz + lam - g20 * g20 - g21 * g21);
-      const double t0 = r0 / g00, t1 = (r1 - g10 * t0) / g11, t2 = (r2 - g20 * t0 - g21 * t1) / g22;
-      const double y2 = t2 / g22, y1 = (t1 - g21 * y2) / g11, y0 = (t0 - g10 * y1 - g20 * y2) / g00;
-      x[0] += y0; x[1] += y1; x[2] += y2;
-      if (!(isfinite(x[0]) && isfinite(x[1]) && isfinite(x[2]))) { x[0] = m[0]; x[1] = m[1]; x[2] = m[2]; flag |= SR_QUADRIC_NO_PLANES; }
-    } else {
-      flag |= SR_QUADRIC_NO_PLANES;
-    }
+    double x[3];
+    if (!quadric_optimum(xx, xy, xz, yy, yz, zz, bx, by, bz, m, reg, x)) flag |= SR_QUADRIC_NO_PLANES;
     const int64_t key = cells[c];
     const int64_t ijk[3] = {key % nx, (key / nx) % ny, key / (nx * ny)};
     double s2 = 0.;

@@ -3,6 +3,7 @@ parameterize the template mesh tmp.ply yourself, then save the result mesh as ..
 
     simplify_mesh / simplify_to   vertex clustering on a uniform grid (87k-196k marching-cubes vertices -> a face budget); the new
                                   vertices at the cell means (default) or, placement="quadric", at the quadric optima of their cells
+    simplify_collapse             edge-collapse decimation to a face budget in rounds of independent collapses: keeps a manifold a manifold
     simplify_quality              surface distances and volume ratio between a simplified mesh and its source
     unwrap_charts                 box projection: charts = connected faces of one dominant normal axis and sign, shelf-packed
     prepare_template              extract -> simplify -> unwrap -> template/uvmap.obj
@@ -13,8 +14,10 @@ projection (UV area / surface area of a face is |n_axis| / |n|, between 1 / sqrt
 and no repair of a chart that overlaps itself in projection -- that is counted (`overlap_texels`), not fixed.  The default placement
 puts a vertex at its cell's mean, which lies inside the hull of the members: the body shrinks and creases are rounded off.
 placement="quadric" moves it to the regularised minimiser of the cell's plane quadrics instead (Lindstrom's out-of-core
-simplification), clamped to the cell's box: two clamped neighbours can meet on their shared wall; boundary-edge quadrics for open meshes,
-edge collapse or any other change of connectivity, and attribute-aware quadrics are out of scope.
+simplification), clamped to the cell's box: two clamped neighbours can meet on their shared wall.  Clustering decides by position alone:
+it can weld two sheets of the surface that pass through one cell and leave non-manifold edges.  simplify_collapse does not -- every
+collapse passes the link condition -- at the price of some tens of rounds instead of one pass; boundary and non-manifold edges are kept
+as they are (their vertices are locked).  Boundary-edge quadrics for open meshes and attribute-aware quadrics are out of scope.
 """
 import os
 from collections import namedtuple
@@ -31,6 +34,7 @@ PreparedTemplate = namedtuple("PreparedTemplate", "mesh atlas obj_path source_fa
 
 BISECT_STEPS = 16
 PLACEMENTS = ("mean", "quadric")
+METHODS = ("cluster", "collapse")
 PACK_STEPS = 24
 
 
@@ -156,6 +160,82 @@ def simplify_to(verts, faces, target_faces, probes=None, placement="mean", reg=1
     return simplify_mesh(verts, faces, best, placement, reg, report)
 
 
+def simplify_collapse(verts, faces, target_faces, reg=1e-3, flip_cos=0.2, max_rounds=1024, report=None):
+    """Edge-collapse decimation of verts [V,3] float32 / faces [F,3] int64 (GPU tensors) to `target_faces` faces, in rounds of
+    independent collapses (mesh_prep_ops.collapse_round / collapse_apply).  Unlike the clustering it changes the
+    connectivity one valid collapse at a time: a closed oriented manifold stays one, and boundary or non-manifold edges keep their
+    vertices untouched (they are locked).
+
+    Rows with a negative index or a repeated corner are dropped first; a mesh within the budget then comes back as simplify_to returns
+    it (identity map, cell 0).  Every vertex gets the summed plane quadrics of its faces once (float64).  A round lists the edges,
+    gives each one that may collapse (two faces, unlocked ends, link condition, valences, no face turned by more than acos(flip_cos))
+    the position x = m + (A + lambda I)^-1 (b - A m) of Q_a + Q_b about its midpoint, lambda = reg trace(A) / 3, rounded to float32, and
+    the key (float32 bits of the cost at x) << 32 | hash(edge index); the edges whose key is the least among all edges at their ends and
+    at their ends' neighbours collapse -- they touch disjoint faces -- the cheapest first when fewer are needed: verts[a] = x, Q_a +=
+    Q_b, b -> a.  A full run ends at F - 2 ceil((F - target) / 2) faces.  It stops early ("stalled") when a round selects nothing or
+    after `max_rounds`.  Unreferenced vertices are dropped at the end, the survivors keep their ascending original order, and
+    vertex_map [V] sends every original vertex to its survivor (-1 for a vertex no face ever used).  The host reads one small record
+    per round.  ValueError for non-finite vertices, an index outside [0, V), reg not finite and positive or flip_cos outside [-1, 1).
+    Two calls give identical bits.  -> SimplifiedMesh(verts [Vn,3], faces [Fn,3], vertex_map [V], cell = 0.).
+
+    `report`, a dict, receives method ("collapse"), rounds, collapses, stalled, locked_vertices (of the first round), candidates_first
+    / candidates_last (of the first and the last round), vertices, faces, and flipped / zero_area: the surviving faces whose normal
+    points against the normal of the triangle their three survivors made at their original positions, or has vanished
+    (mesh_prep_ops.face_flips with every face as its own source).  `flipped` measures how far survivors have travelled, not folds: a
+    vertex that has moved past a neighbour's old place counts, on a flat grid too; every collapse has passed the flip test."""
+    _, reg = _placement("mean", reg)
+    flip_cos = float(flip_cos)
+    if not -1. <= flip_cos < 1.:
+        raise ValueError(f"flip_cos must lie in [-1, 1), got {flip_cos}")
+    _lib.require_gpu(verts, faces)
+    verts = _lib.f32c(verts)
+    mp.mesh_bounds(verts)                                                # (refuses non-finite vertices, as simplify_mesh does)
+    V, dev = verts.shape[0], verts.device
+    faces = mp._indexed(mp.proper_faces(faces), V, "simplify_collapse")
+    target, F = int(target_faces), faces.shape[0]
+    parent = torch.arange(V, dtype=torch.int64, device=dev)
+    stats = dict(method="collapse", rounds=0, collapses=0, stalled=False, locked_vertices=0, candidates_first=0, candidates_last=0)
+    if F <= target:
+        if report is not None:
+            report.update(stats, vertices=V, faces=F, flipped=0, zero_area=0)
+        return SimplifiedMesh(verts, faces, parent, 0.)
+    moved = verts.clone()
+    quadrics = mp.vertex_quadrics(verts, faces)
+    while F > target:
+        if stats["rounds"] >= int(max_rounds):
+            stats["stalled"] = True
+            break
+        edges, keys, positions, selected, record, locked = mp._round(moved, faces, quadrics, reg, flip_cos)
+        n_selected, n_candidates = record.tolist()                       # the round's one device -> host copy
+        if stats["rounds"] == 0:
+            stats.update(locked_vertices=int(locked.sum()), candidates_first=n_candidates)
+        stats["rounds"] += 1
+        stats["candidates_last"] = n_candidates
+        if n_selected == 0:
+            stats["stalled"] = True
+            break
+        need = (F - target + 1) // 2
+        if n_selected > need:                                            # the `need` cheapest of the selected (the keys are unique)
+            ranked = torch.where(selected.bool(), keys, torch.full_like(keys, mp.INT64_MAX))
+            selected = ranked <= torch.kthvalue(ranked, need)[0]
+            n_selected = need
+        faces = mp.collapse_apply(moved, faces, quadrics, parent, edges, positions, selected)
+        stats["collapses"] += n_selected
+        if faces.shape[0] != F - 2 * n_selected:
+            raise RuntimeError(f"simplify_collapse: {n_selected} collapses removed {F - faces.shape[0]} faces")
+        F = faces.shape[0]
+    root = mp.collapse_roots(parent)
+    used = torch.zeros((V,), dtype=torch.bool, device=dev)
+    used[faces.view(-1)] = True
+    new = torch.cumsum(used, 0) - 1
+    vertex_map = torch.where(used[root], new[root], torch.full_like(root, -1))
+    mesh = SimplifiedMesh(moved[used].contiguous(), new[faces].contiguous(), vertex_map, 0.)
+    if report is not None:
+        flipped, zero_area = mp.face_flips(verts, faces, moved, faces, torch.arange(F, dtype=torch.int64, device=dev))
+        report.update(stats, vertices=int(mesh.verts.shape[0]), faces=F, flipped=flipped, zero_area=zero_area)
+    return mesh
+
+
 def signed_volume(verts, faces):
     """The signed volume sum p0 . (p1 x p2) / 6 of a triangle mesh (positive for outward normals), in double: a 0-d GPU tensor."""
     p = verts.double()[faces]
@@ -265,19 +345,27 @@ def unwrap_charts(verts, faces, resolution=1680, padding=2):
 
 
 def prepare_template(net, out_root, ratio=None, target_faces=20000, resolution=1680, padding=2, TmpVs=None, Tmpfs=None, placement="mean", reg=1e-3,
-                     report=None):
+                     report=None, method="cluster"):
     """Extracts the template of `net` with discretizeSDF(ratio, None, 0.) as infer does (all ratios 1 unless given; or takes TmpVs /
     Tmpfs), simplifies it to `target_faces`, unwraps it and writes out_root/template/uvmap.obj, the file export_texture reads.
     -> PreparedTemplate(mesh SimplifiedMesh, atlas ChartAtlas, obj_path, source_faces: the faces of the extracted template).
 
     20000 faces is a default, not a measured optimum: at 1680^2 texels with about half of the atlas covered it leaves some 70 texels
-    per face.  `placement`, `reg` and `report` go to simplify_to."""
+    per face.  `method` is "cluster" (simplify_to, which takes `placement`, `reg` and `report`) or "collapse" (simplify_collapse, which
+    takes `reg` and `report`; ValueError with placement="quadric", which places cluster representatives)."""
     from .mesh_io import write_obj_uv
     from .posed import FULL_RATIO
     placement, reg = _placement(placement, reg)
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
+    if method == "collapse" and placement != "mean":
+        raise ValueError(f"placement={placement!r} belongs to method='cluster'; method='collapse' places every vertex by its own quadric")
     if TmpVs is None or Tmpfs is None:
         TmpVs, Tmpfs = net.discretizeSDF(ratio or FULL_RATIO, None, 0.)
-    mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces, placement=placement, reg=reg, report=report)
+    if method == "collapse":
+        mesh = simplify_collapse(TmpVs.detach(), Tmpfs, target_faces, reg=reg, report=report)
+    else:
+        mesh = simplify_to(TmpVs.detach(), Tmpfs, target_faces, placement=placement, reg=reg, report=report)
     atlas = unwrap_charts(mesh.verts, mesh.faces, resolution, padding)
     folder = os.path.join(out_root, "template")
     os.makedirs(folder, exist_ok=True)

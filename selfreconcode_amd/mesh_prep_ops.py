@@ -1,4 +1,4 @@
-"""Operators of the template preparation (csrc/mesh_prep.hip): GPU tensors only, no autograd.  `mesh_prep.py` is the public interface.
+"""Operators of the template preparation (csrc/mesh_prep.hip, csrc/mesh_collapse.hip): GPU tensors only, no autograd.  `mesh_prep.py` is the public interface.
 Sorting, unique and compaction are torch's; everything per element is a HIP kernel.  Two calls give identical bits."""
 import numpy as np
 import torch
@@ -230,3 +230,128 @@ def uv_overlap_count(vt, ft, resolution, eps=1e-6):
     total = torch.empty((1,), dtype=torch.int64, device=vt.device)
     _lib.launch("sr_uv_overlap_count", vt, vt, ft, vt.shape[0], ft.shape[0], R, float(eps), count, total)
     return int(total)
+
+
+# ------------------------------------------------------------------------------------------------ edge collapse (csrc/mesh_collapse.hip)
+INT64_MAX = (1 << 63) - 1          # the key of an edge that is no candidate
+QUADRIC_DOUBLES = 10               # xx xy xz yy yz zz of sum w n n^T, sum w d n, sum w d^2
+
+
+def proper_faces(faces):
+    """The rows of faces [F,3] without a negative index or a repeated corner, in order."""
+    faces = clean_faces(faces)
+    a, b, c = faces.unbind(1)
+    return faces[(a != b) & (b != c) & (a != c)].contiguous()
+
+
+def _collapse_mesh(verts, faces, what):
+    """(verts, faces) checked for a round: float32 [V,3], int64 [F,3] with F > 0, every index in [0, V) and no repeated corner."""
+    _lib.require_gpu(verts, faces)
+    verts = _verts2(verts)
+    faces = _indexed(faces, verts.shape[0], what)
+    if faces.shape[0] == 0:
+        raise ValueError(f"{what}: no faces")
+    a, b, c = faces.unbind(1)
+    if bool(((a == b) | (b == c) | (a == c)).any()):
+        raise ValueError(f"{what}: a face with a repeated corner")
+    return verts, faces
+
+
+def _quadrics(quadrics, V):
+    if quadrics.dtype != torch.float64 or tuple(quadrics.shape) != (V, QUADRIC_DOUBLES) or not quadrics.is_contiguous():
+        raise ValueError(f"quadrics: a contiguous float64 [{V},{QUADRIC_DOUBLES}] expected, got {quadrics.dtype} {tuple(quadrics.shape)}")
+    return quadrics
+
+
+def vertex_quadrics(verts, faces):
+    """Q [V,10] float64: per vertex the plane quadrics (w n n^T as xx xy xz yy yz zz, w d n, w d^2; n the unit normal, w the area, d = n . p0
+    as cell_quadric_optima takes them) of its faces, summed in ascending face index (a stable sort, sr_collapse_vertex_quadrics)."""
+    verts, faces = _collapse_mesh(verts, faces, "vertex_quadrics")
+    V, F = verts.shape[0], faces.shape[0]
+    slots, offsets = _lists(faces.view(-1), V)
+    Q = torch.empty((V, QUADRIC_DOUBLES), dtype=torch.float64, device=verts.device)
+    _lib.launch("sr_collapse_vertex_quadrics", verts, verts, V, faces, F, slots, offsets, Q)
+    return Q
+
+
+def _round(verts, faces, quadrics, reg, flip_cos):
+    """Steps 1-4 of a round on checked arguments -> (edges, keys, positions, selected uint8, record [2] int64 on the device: selected,
+    candidates; locked [V] int32).  No device -> host copy but the edge count (torch.unique_consecutive's)."""
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    hkey = torch.empty((3 * F,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_collapse_edge_keys", verts, faces, F, V, hkey)
+    skey, perm = torch.sort(hkey, stable=True)
+    ukey, counts = torch.unique_consecutive(skey, return_counts=True)
+    E = ukey.shape[0]
+    offsets = torch.zeros((E + 1,), dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    edges = torch.empty((E, 2), dtype=torch.int64, device=dev); opp = torch.empty_like(edges)
+    count = torch.empty((E,), dtype=torch.int32, device=dev); locked = torch.empty((V,), dtype=torch.int32, device=dev)
+    directed = torch.empty((2 * E,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_collapse_edge_heads", verts, ukey, offsets, E, perm, faces, F, V, edges, count, opp, locked, directed)
+    nbr = torch.sort(directed)[0]
+    noff = torch.searchsorted(nbr, torch.arange(V + 1, dtype=torch.int64, device=dev) * V).contiguous()
+    slots, soff = _lists(faces.view(-1), V)
+    pos = torch.empty((E, 3), dtype=torch.float32, device=dev)
+    keys = torch.empty((E,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_collapse_candidates", verts, verts, V, faces, F, quadrics, slots, soff, nbr, noff, edges, count, opp, locked, E, float(reg),
+                float(flip_cos), pos, keys)
+    m1 = torch.empty((V,), dtype=torch.int64, device=dev); m2 = torch.empty_like(m1)
+    _lib.launch("sr_collapse_min1", verts, edges, keys, E, V, m1)
+    _lib.launch("sr_collapse_min2", verts, edges, E, V, m1, m2)
+    selected = torch.empty((E,), dtype=torch.uint8, device=dev)
+    record = torch.empty((2,), dtype=torch.int64, device=dev)
+    _lib.launch("sr_collapse_select", verts, edges, keys, E, V, m2, selected, record)
+    return edges, keys, pos, selected, record, locked
+
+
+def collapse_round(verts, faces, quadrics, reg=1e-3, flip_cos=0.2):
+    """Steps 1-4 of one round of the edge-collapse decimation on verts [V,3] float32 / faces [F,3] int64 / quadrics [V,10] float64 (GPU
+    tensors), nothing applied -> (edges [E,2] int64: a < b in ascending a V + b, keys [E] int64: (float32 bits of the
+    cost) << 32 | fmix32(e), or INT64_MAX for an edge that is no candidate, positions [E,3] float32: where a collapse of the edge would
+    put its vertex, selected [E] bool: key == m2[a] == m2[b] -- no two selected edges have adjacent or common endpoints).  ValueError for
+    an index outside [0, V), a repeated corner or no faces."""
+    verts, faces = _collapse_mesh(verts, faces, "collapse_round")
+    _lib.require_gpu(quadrics)
+    edges, keys, pos, selected, _, _ = _round(verts, faces, _quadrics(quadrics, verts.shape[0]), reg, flip_cos)
+    return edges, keys, pos, selected.bool()
+
+
+def collapse_apply(verts, faces, quadrics, target, edges, positions, selected):
+    """Applies the collapses of the edges `selected` [E] (bool or uint8; no two may share or have adjacent endpoints, as collapse_round
+    selects them) IN PLACE to verts [V,3] float32, quadrics [V,10] float64 and target [V] int64: verts[a] = positions[e], quadrics[a] +=
+    quadrics[b], target[b] = a.  -> the surviving faces: target[faces] (one level) without the rows with a repeated corner, in order."""
+    _lib.require_gpu(verts, faces, quadrics, target, edges, positions, selected)
+    V, E = verts.shape[0], edges.shape[0]
+    if verts.dtype != torch.float32 or not verts.is_contiguous() or verts.dim() != 2 or verts.shape[1] != 3:
+        raise ValueError("collapse_apply: a contiguous float32 verts [V,3] expected (it is updated in place)")
+    if target.dtype != torch.int64 or tuple(target.shape) != (V,) or not target.is_contiguous():
+        raise ValueError(f"collapse_apply: a contiguous int64 target [{V}] expected")
+    if tuple(edges.shape) != (E, 2) or tuple(positions.shape) != (E, 3) or tuple(selected.shape) != (E,):
+        raise ValueError("collapse_apply: edges [E,2], positions [E,3] and selected [E] expected")
+    quadrics = _quadrics(quadrics, V)
+    faces = _indexed(faces, V, "collapse_apply")
+    F, dev = faces.shape[0], verts.device
+    selected = selected.to(torch.uint8).contiguous()
+    if E:
+        _lib.launch("sr_collapse_apply_vertices", verts, _lib.i64c(edges), _lib.f32c(positions), selected, E, verts, V, quadrics, target)
+    if F == 0:
+        return faces
+    out = torch.empty((F, 3), dtype=torch.int64, device=dev); keep = torch.empty((F,), dtype=torch.uint8, device=dev)
+    _lib.launch("sr_collapse_apply_faces", verts, faces, F, target, V, out, keep)
+    return out[keep.bool()].contiguous()
+
+
+def collapse_roots(target):
+    """root [V] int64 of the forest target [V] (target[v] = v for a root) by pointer doubling (sr_collapse_map_jump; one flag read per
+    pass, at most 64 passes: a chain of V links needs log2 V)."""
+    _lib.require_gpu(target)
+    P = _lib.i64c(target).clone(); N = torch.empty_like(P)
+    V = P.shape[0]
+    changed = torch.zeros((1,), dtype=torch.int32, device=P.device)
+    for _ in range(64):
+        _lib.launch("sr_collapse_map_jump", P, P, V, N, changed)
+        P, N = N, P
+        if not int(changed):
+            return P
+    raise RuntimeError("collapse_roots: target is not a forest")

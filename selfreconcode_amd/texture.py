@@ -2,7 +2,7 @@
 texture_mesh_extract.py -- for a UV-mapped template, on the GPU.
 
     python -m selfreconcode_amd.texture --gpu-ids 0 --rec-root <capture folder>/result [--num 120] [--faces 20000] [--resolution 1680] [--padding 2]
-        [--placement {mean,quadric}] [--simplify-report]
+        [--placement {mean,quadric}] [--simplify {cluster,collapse}] [--simplify-report]
 
 The reference's scripts hand the unwrap and the per-view partial textures to opendr and VideoAvatar's Isomapper and the final fill to
 cv2; none of them is part of the reference repository.  What the script computes with them is restated here (restated,
@@ -26,7 +26,8 @@ The reference leaves simplifying and unwrapping the marching-cubes template to t
 The command honours such a file; without one it makes it (mesh_prep.prepare_template: vertex clustering to `--faces` faces and a
 box-projection chart atlas), so a trained folder gives template/texture.png with no hand-made file.  Everything it
 writes goes under rec_root/template/.  `--placement quadric` puts the simplified vertices at the quadric optima of their cells instead
-of the cell means; `--simplify-report` also writes template/simplify.json (the counts of the simplification and its distance to the
+of the cell means; `--simplify collapse` decimates by edge collapse instead of clustering (mesh_prep.simplify_collapse: a manifold
+template stays one); `--simplify-report` also writes template/simplify.json (the counts of the simplification and its distance to the
 extracted template).
 """
 import argparse
@@ -128,6 +129,8 @@ def build_parser():
     parser.add_argument('--padding', default=2, type=int, metavar='P', help='texels kept free around every chart')
     parser.add_argument('--placement', default='mean', choices=['mean', 'quadric'],
                         help='where a simplified vertex goes: the mean of its cell, or the quadric optimum of the faces that touch the cell')
+    parser.add_argument('--simplify', default='cluster', choices=['cluster', 'collapse'],
+                        help='how the template is brought to --faces faces: vertex clustering, or edge collapse (keeps a manifold a manifold)')
     parser.add_argument('--simplify-report', action='store_true',
                         help='write template/simplify.json: the counts of the simplification and its distance to the extracted template')
     return parser
@@ -142,20 +145,28 @@ def dataset_views(dataset, fids):
 
 def _prepare_with_report(net, args, folder, out):
     """prepare_template on the template extracted here (the same call it would make), so that the simplified mesh can be measured
-    against it: writes template/simplify.json (simplify_mesh's report and mesh_prep.simplify_quality) and prints one line."""
+    against it: writes template/simplify.json (the report of simplify_mesh or simplify_collapse, and mesh_prep.simplify_quality) and prints
+    one line."""
     import json
     from .mesh_prep import prepare_template, simplify_quality
     from .posed import FULL_RATIO
     TmpVs, Tmpfs = net.discretizeSDF(FULL_RATIO, None, 0.)
     report = {}
     prep = prepare_template(net, args.rec_root, target_faces=args.faces, resolution=args.resolution, padding=args.padding, TmpVs=TmpVs, Tmpfs=Tmpfs,
-                            placement=args.placement, report=report)
-    report['cell'] = prep.mesh.cell
+                            placement=args.placement, report=report, method=args.simplify)
+    if args.simplify == 'cluster':
+        report['cell'] = prep.mesh.cell
     report['quality'] = quality = simplify_quality(prep.mesh, TmpVs.detach(), Tmpfs)
     path = os.path.join(folder, 'simplify.json')
     with open(path, 'w') as fh:
         json.dump(report, fh, indent=1, sort_keys=True)
         fh.write('\n')
+    if args.simplify == 'collapse':
+        out('simplify: method collapse, %d rounds, %d collapses%s, %d locked vertices, %d flipped / %d zero-area faces, source -> simplified mean '
+            '%.3g, volume ratio %.4f; wrote %s' % (report['rounds'], report['collapses'], ' (stalled)' if report['stalled'] else '',
+                                                  report['locked_vertices'], report['flipped'], report['zero_area'],
+                                                  quality['source_to_simplified']['mean'], quality['volume_ratio'], path))
+        return prep
     out('simplify: placement %s, %d cells (%d clamped, %d without planes), %d flipped / %d zero-area faces, source -> simplified mean %.3g, '
         'volume ratio %.4f; wrote %s' % (report['placement'], report['cells'], report['clamped'], report['no_planes'], report['flipped'],
                                          report['zero_area'], quality['source_to_simplified']['mean'], quality['volume_ratio'], path))
@@ -172,6 +183,8 @@ def main(argv=None, out=print, resolutions=None):
     args = parser.parse_args(argv)
     if args.rec_root is None:
         parser.error('--rec-root is required')
+    if args.simplify == 'collapse' and args.placement != 'mean':
+        parser.error('--placement %s places the representatives of --simplify cluster; --simplify collapse has no placement' % args.placement)
     device = torch.device('cuda', args.gpu_ids[0])
     net, dataset, _ = load_network(args.rec_root, device, 1, out, resolutions)
     folder = os.path.join(args.rec_root, 'template')
@@ -183,7 +196,7 @@ def main(argv=None, out=print, resolutions=None):
             prep = _prepare_with_report(net, args, folder, out)
         else:
             prep = prepare_template(net, args.rec_root, target_faces=args.faces, resolution=args.resolution, padding=args.padding,
-                                    placement=args.placement)
+                                    placement=args.placement, method=args.simplify)
         mesh, atlas = prep.mesh, prep.atlas
         out('template: %d vertices / %d faces -> %d vertices / %d faces' % (mesh.vertex_map.shape[0], prep.source_faces, mesh.verts.shape[0],
                                                                            mesh.faces.shape[0]))

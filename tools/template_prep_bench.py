@@ -1,6 +1,7 @@
 """Times the template preparation of the texture stage at the fine stage's template size -- cube_sphere(170): 173 402 vertices, 346 800
 faces -> simplify_to(20000) -> unwrap_charts(1680) -- on the GPU, stage by stage, the simplification with both vertex placements (and
-their report counts and simplify_quality against the source).  Wall time around synchronised calls after seconds of
+their report counts and simplify_quality against the source), and with the edge-collapse decimation simplify_collapse(20000) and the
+unwrap of its result.  Wall time around synchronised calls after seconds of
 warm-up (these functions read flags and boxes back, so they are host-paced: HIP events around them would say the same).
 
     python tools/template_prep_bench.py [--out profiles/template_prepare.md] [--seconds 2.0]
@@ -61,6 +62,17 @@ def main():
         res["report_" + placement] = report
         res["quality_" + placement] = mesh_prep.simplify_quality(m, v, f)
         res["sphere_error_" + placement] = float((m.verts.double().norm(dim=1) - 1.).abs().max())            # (the template is the unit sphere)
+    # the edge-collapse decimation to the same budget: its rounds, its distance to the source, and what box projection makes of its result
+    report = {}
+    cm = mesh_prep.simplify_collapse(v, f, TARGET, report=report)
+    res["report_collapse"] = report
+    res["quality_collapse"] = mesh_prep.simplify_quality(cm, v, f)
+    res["sphere_error_collapse"] = float((cm.verts.double().norm(dim=1) - 1.).abs().max())
+    res["simplify_collapse_ms"], res["simplify_collapse_runs"] = timed(lambda: mesh_prep.simplify_collapse(v, f, TARGET), args.seconds)
+    catlas = mesh_prep.unwrap_charts(cm.verts, cm.faces, R)
+    res.update(collapse_charts=catlas.labels.shape[0], collapse_overlap_texels=catlas.overlap_texels, collapse_scale=catlas.scale, collapse_unwrap_rounds=catlas.rounds)
+    res["collapse_unwrap_ms"], _ = timed(lambda: mesh_prep.unwrap_charts(cm.verts, cm.faces, R), args.seconds)
+    res["simplify_to_again_ms"], _ = timed(lambda: mesh_prep.simplify_to(v, f, TARGET), args.seconds)           # (the clustering once more, after the collapse lines)
     res["unwrap_ms"], res["unwrap_runs"] = timed(lambda: mesh_prep.unwrap_charts(mesh.verts, mesh.faces, R), args.seconds)
     res["unwrap_full_size_ms"], _ = timed(lambda: mesh_prep.unwrap_charts(v, f, R), args.seconds)       # the unsimplified template: the kernels at size
     ext = atlas.extent.cpu().numpy()
@@ -75,7 +87,13 @@ def main():
             fh.write(f"| simplify_mesh at that cell, placement=\"quadric\" | {res['simplify_mesh_quadric_ms']:.2f} ms |\n")
             fh.write(f"| simplify_to({TARGET}), placement=\"quadric\" | {res['simplify_to_quadric_ms']:.2f} ms |\n")
             fh.write(f"| simplify_mesh at that cell, placement=\"mean\", timed again | {res['simplify_mesh_again_ms']:.2f} ms |\n")
-            fh.write(f"| unwrap_charts({R}) of the result: {res['charts']} charts, {res['rounds']} passes of the component search | {res['unwrap_ms']:.2f} ms |\n")
+            rc = res["report_collapse"]
+            fh.write(f"| simplify_collapse({TARGET}) -> {rc['vertices']} vertices, {rc['faces']} faces in {rc['rounds']} rounds ({rc['collapses']} collapses"
+                     f"{', stalled' if rc['stalled'] else ''}) | {res['simplify_collapse_ms']:.2f} ms |\n")
+            fh.write(f"| simplify_to({TARGET}), timed again after it | {res['simplify_to_again_ms']:.2f} ms |\n")
+            fh.write(f"| unwrap_charts({R}) of the collapse's result: {res['collapse_charts']} charts, overlap_texels {res['collapse_overlap_texels']}, "
+                     f"{res['collapse_unwrap_rounds']} passes | {res['collapse_unwrap_ms']:.2f} ms |\n")
+            fh.write(f"| unwrap_charts({R}) of the clustering's result: {res['charts']} charts, overlap_texels {res['overlap_texels']}, {res['rounds']} passes of the component search | {res['unwrap_ms']:.2f} ms |\n")
             fh.write(f"| of which pack_charts on the host | {res['pack_host_ms']:.2f} ms |\n")
             fh.write(f"| unwrap_charts({R}) of the unsimplified template | {res['unwrap_full_size_ms']:.2f} ms |\n\n")
             fh.write("| placement | clamped | no_planes | flipped | zero_area | max_shift | source -> simplified mean / max | simplified -> source mean / max "
@@ -86,6 +104,9 @@ def main():
                          f"{q['source_to_simplified']['mean']:.3g} / {q['source_to_simplified']['max']:.3g} | "
                          f"{q['simplified_to_source']['mean']:.3g} / {q['simplified_to_source']['max']:.3g} | {q['volume_ratio']:.6f} | "
                          f"{res['sphere_error_' + placement]:.3g} |\n")
+            q = res["quality_collapse"]
+            fh.write(f"| (collapse) | - | - | {rc['flipped']} | {rc['zero_area']} | - | {q['source_to_simplified']['mean']:.3g} / {q['source_to_simplified']['max']:.3g} | "
+                     f"{q['simplified_to_source']['mean']:.3g} / {q['simplified_to_source']['max']:.3g} | {q['volume_ratio']:.6f} | {res['sphere_error_collapse']:.3g} |\n")
             fh.write("\n")
             fh.write(json.dumps(res) + "\n")
 
