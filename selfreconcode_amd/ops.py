@@ -20,12 +20,15 @@ class SingularValues3x3(Function):
         S = torch.empty((n, 3), dtype=torch.float32, device=A.device)
         _lib.launch("sr_svd3x3", A, A, n, U, S, V)
         ctx.save_for_backward(U, V)
+        ctx.shape = J.shape
         return S
 
     @staticmethod
     def backward(ctx, gS):
         U, V = ctx.saved_tensors
-        return ((U * gS.unsqueeze(1)).unsqueeze(-1) * V.transpose(1, 2).unsqueeze(-3)).sum(-2)      # 3x3 products: see utils.small_matmul
+        gJ = torch.empty_like(U)
+        _lib.launch("sr_svd3x3_bwd", U, U, V, _lib.f32c(gS).view(-1, 3), U.shape[0], gJ)       # U diag(gS) V^T, one launch
+        return gJ.view(ctx.shape)
 
 
 def singular_values_3x3(J):
