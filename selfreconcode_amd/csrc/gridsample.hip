@@ -379,9 +379,8 @@ int gs_fwd(const T* input, sr_tensor5 in_d, const T* grid, sr_tensor5 g_d, T* ou
   if (!input || !grid || !out) return SR_EINVAL;
   if constexpr (sizeof(T) == 4) {
     if (channel_last_ok(input, in_d)) {
-#define SR_GS_FWD_CL(CV)                                                                                                          \
-  hipLaunchKernelGGL(gs_fwd_cl_kernel<CV>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, total, (const float*)input, \
-                     in_d, (const float*)grid, g_d, (float*)out, o_d)
+#define SR_GS_FWD_CL(CV) \
+  sr_launch_stream(gs_fwd_cl_kernel<CV>, total, 256, stream, total, (const float*)input, in_d, (const float*)grid, g_d, (float*)out, o_d)
       switch (channel_slab(in_d.size[1])) {
         case 6: SR_GS_FWD_CL(6); break;
         case 4: SR_GS_FWD_CL(4); break;
@@ -392,7 +391,7 @@ int gs_fwd(const T* input, sr_tensor5 in_d, const T* grid, sr_tensor5 g_d, T* ou
       return sr_launch_status();
     }
   }
-  hipLaunchKernelGGL(gs_fwd_kernel<T>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, total, input, in_d, grid, g_d, out, o_d);
+  sr_launch_stream(gs_fwd_kernel<T>, total, 256, stream, total, input, in_d, grid, g_d, out, o_d);
   return sr_launch_status();
 }
 template <typename T>
@@ -405,8 +404,8 @@ int gs_bwd(const T* input, sr_tensor5 in_d, const T* grid, sr_tensor5 g_d, const
   if constexpr (sizeof(T) == 4) {
     if (!gin && channel_last_ok(input, in_d)) {
 #define SR_GS_BWD_CL(CV)                                                                                                          \
-  hipLaunchKernelGGL(gs_bwd_cl_kernel<CV>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, total, (const float*)input, \
-                     in_d, (const float*)grid, g_d, (const float*)gout, go_d, (float*)ggrid)
+  sr_launch_stream(gs_bwd_cl_kernel<CV>, total, 256, stream, total, (const float*)input, in_d, (const float*)grid, g_d, (const float*)gout, go_d, \
+                   (float*)ggrid)
       switch (channel_slab(in_d.size[1])) {
         case 6: SR_GS_BWD_CL(6); break;
         case 4: SR_GS_BWD_CL(4); break;
@@ -417,7 +416,7 @@ int gs_bwd(const T* input, sr_tensor5 in_d, const T* grid, sr_tensor5 g_d, const
       return sr_launch_status();
     }
   }
-  hipLaunchKernelGGL(gs_bwd_kernel<T>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, total, input, in_d, grid, g_d, gout, go_d, gin, gi_d, ggrid);
+  sr_launch_stream(gs_bwd_kernel<T>, total, 256, stream, total, input, in_d, grid, g_d, gout, go_d, gin, gi_d, ggrid);
   return sr_launch_status();
 }
 template <typename T>
@@ -427,7 +426,7 @@ int gs_dbwd(const T* gOi, sr_tensor5 goi_d, const T* gOg, sr_tensor5 gog_d, cons
   const int64_t total = g_d.size[0] * g_d.size[1] * g_d.size[2] * g_d.size[3];
   if (total == 0) return SR_OK;
   if (!gOg || !input || !grid || !gout || !ggrid || !ggout) return SR_EINVAL;
-  hipLaunchKernelGGL(gs_dbwd_kernel<T>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, total, gOi, goi_d, gOg, gog_d, input, in_d, grid, g_d, gout, go_d, gin, gi_d, ggrid, ggout);
+  sr_launch_stream(gs_dbwd_kernel<T>, total, 256, stream, total, gOi, goi_d, gOg, gog_d, input, in_d, grid, g_d, gout, go_d, gin, gi_d, ggrid, ggout);
   return sr_launch_status();
 }
 }  // namespace

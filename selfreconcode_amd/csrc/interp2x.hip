@@ -100,7 +100,7 @@ int fwd(const T* in, int64_t BC, int d, int h, int w, float bal, T* out, uint8_t
   if (BC == 0) return SR_OK;
   if (!in || !out || !bnd) return SR_EINVAL;
   const int64_t total = BC * (2 * d - 1) * (2 * h - 1) * (2 * w - 1);
-  hipLaunchKernelGGL(interp2x_fwd_kernel<T>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)st, in, BC, d, h, w, bal, out, bnd);
+  sr_launch_stream(interp2x_fwd_kernel<T>, total, 256, st, in, BC, d, h, w, bal, out, bnd);
   return sr_launch_status();
 }
 template <typename T>
@@ -108,7 +108,7 @@ int bwd(const T* go, int64_t BC, int d, int h, int w, T* gi, void* st) {
   if (BC < 0 || d <= 0 || h <= 0 || w <= 0) return SR_EINVAL;
   if (BC == 0) return SR_OK;
   if (!go || !gi) return SR_EINVAL;
-  hipLaunchKernelGGL(interp2x_bwd_kernel<T>, dim3(sr_stream_grid(BC * d * h * w, 256)), dim3(256), 0, (hipStream_t)st, go, BC, d, h, w, gi);
+  sr_launch_stream(interp2x_bwd_kernel<T>, BC * d * h * w, 256, st, go, BC, d, h, w, gi);
   return sr_launch_status();
 }
 }  // namespace
@@ -154,8 +154,7 @@ int sr_seg3d_candidates(const uint8_t* is_boundary, const uint8_t* done, int32_t
                         void* stream) {
   if (D <= 0 || H <= 0 || W <= 0 || !is_boundary || !done || !out_index || !count_dev) return SR_EINVAL;
   if (hipMemsetAsync(count_dev, 0, 8, (hipStream_t)stream) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(seg3d_candidates_kernel, dim3(sr_stream_grid((int64_t)D * H * W, 256)), dim3(256), 0, (hipStream_t)stream, is_boundary, done, D, H, W,
-                     out_index, (unsigned long long*)count_dev);
+  sr_launch_stream(seg3d_candidates_kernel, (int64_t)D * H * W, 256, stream, is_boundary, done, D, H, W, out_index, (unsigned long long*)count_dev);
   return sr_launch_status();
 }
 int sr_interp2x3d_fwd_f32(const float* in, int64_t BC, int32_t d, int32_t h, int32_t w, float balance, float* out, uint8_t* is_boundary, void* s) { return fwd<float>(in, BC, d, h, w, balance, out, is_boundary, s); }

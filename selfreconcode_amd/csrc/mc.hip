@@ -382,7 +382,7 @@ int sr_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float iso, 
   const uint32_t* toff64 = voff64 + (L.G + 1);
   hipStream_t st = (hipStream_t)stream;
   Dim d{nx, ny, nz};
-  hipLaunchKernelGGL(mc_tag_kernel, dim3(sr_stream_grid(L.G, 256)), dim3(256), 0, st, d, planes, voff64, toff64, (uint32_t*)verts, faces);
+  sr_launch_stream(mc_tag_kernel, L.G, 256, st, d, planes, voff64, toff64, (uint32_t*)verts, faces);
   // V and F live on the device (off[G]); the per-output kernels bound their grid-stride loops by them
   const int out_grid = sr_stream_grid(L.G * 8 < (int64_t)1 << 22 ? L.G * 8 : (int64_t)1 << 22, 256);
   hipLaunchKernelGGL(mc_vertex_kernel, dim3(out_grid), dim3(256), 0, st, sdf, d, iso, voff64, xstep, ystep, zstep, xmin, ymin, zmin, verts);

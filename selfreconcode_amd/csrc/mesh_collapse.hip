@@ -15,8 +15,10 @@
 //
 // Gather- and latency-bound work on at most a few million elements: a thread walks two short CSR lists.  No float atomics anywhere:
 // every sum is sequential in one thread, the atomics are integer or / add / min, so two calls give identical bits.  Every list range is
-// clamped to its array and every index read from memory is checked before it is used.
+// clamped to its array and every index read from memory is checked before it is used.  The face and half-edge helpers, the face remap,
+// the pointer jump and the record flush are mesh_device.h's (shared with mesh_prep.hip); the plane quadric is quadric_device.h's.
 #include "sr_common.h"
+#include "mesh_device.h"
 #include "quadric_device.h"
 
 namespace {
@@ -41,16 +43,11 @@ __global__ __launch_bounds__(256) void vertex_quadrics(const float* __restrict__
       const int64_t h = slots[k];
       if (h < 0 || h >= 3 * F) continue;
       const int64_t f = h / 3, i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-      if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) continue;
-      double N[3];
-      face_normal(verts + i0 * 3, verts + i1 * 3, verts + i2 * 3, N);
-      const double L = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
-      if (!(L > 0.) || !isfinite(L)) continue;
-      const double n0 = N[0] / L, n1 = N[1] / L, n2 = N[2] / L, w = 0.5 * L;
-      const double d = n0 * (double)verts[i0 * 3] + n1 * (double)verts[i0 * 3 + 1] + n2 * (double)verts[i0 * 3 + 2];
-      const double w0 = w * n0, w1 = w * n1, w2 = w * n2, wd = w * d;
-      q[0] += w0 * n0; q[1] += w0 * n1; q[2] += w0 * n2; q[3] += w1 * n1; q[4] += w1 * n2; q[5] += w2 * n2;
-      q[6] += wd * n0; q[7] += wd * n1; q[8] += wd * n2; q[9] += wd * d;
+      if (!sr_face_ok(i0, i1, i2, V)) continue;
+      PlaneQuadric p;
+      if (!plane_quadric(verts + i0 * 3, verts + i1 * 3, verts + i2 * 3, p)) continue;
+      q[0] += p.w0 * p.n0; q[1] += p.w0 * p.n1; q[2] += p.w0 * p.n2; q[3] += p.w1 * p.n1; q[4] += p.w1 * p.n2; q[5] += p.w2 * p.n2;
+      q[6] += p.wd * p.n0; q[7] += p.wd * p.n1; q[8] += p.wd * p.n2; q[9] += p.wd * p.d;
     }
 #pragma unroll
     for (int k = 0; k < SR_COLLAPSE_Q; ++k) Q[v * SR_COLLAPSE_Q + k] = q[k];
@@ -60,17 +57,16 @@ __global__ __launch_bounds__(256) void vertex_quadrics(const float* __restrict__
 // half-edge h = 3 f + corner, from that corner to the next: min V + max; -1 for a row that is not a face
 __global__ __launch_bounds__(256) void edge_keys(const int64_t* __restrict__ faces, int64_t F, int64_t V, int64_t* __restrict__ key) {
   for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < 3 * F; h += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t f = h / 3, c = h - 3 * f;
-    const int64_t a = faces[h], b = faces[f * 3 + (c + 1) % 3], o = faces[f * 3 + (c + 2) % 3];
-    const bool ok = a >= 0 && b >= 0 && o >= 0 && a < V && b < V && o < V && a != b && a != o && b != o;
-    key[h] = ok ? min(a, b) * V + max(a, b) : -1;
+    const SrHalfEdge e = sr_half_edge(faces, h);
+    const bool ok = sr_face_ok(e.from, e.to, e.opp, V) && e.from != e.to && e.from != e.opp && e.to != e.opp;
+    key[h] = ok ? min(e.from, e.to) * V + max(e.from, e.to) : -1;
   }
 }
 
 // the vertex opposite half-edge h, or -1
 __device__ __forceinline__ int64_t opposite(const int64_t* __restrict__ faces, int64_t F, int64_t V, int64_t h) {
   if (h < 0 || h >= 3 * F) return -1;
-  const int64_t f = h / 3, c = h - 3 * f, o = faces[f * 3 + (c + 2) % 3];
+  const int64_t o = sr_half_edge(faces, h).opp;
   return o >= 0 && o < V ? o : -1;
 }
 
@@ -106,7 +102,7 @@ __device__ bool keeps_normals(const float* __restrict__ verts, int64_t V, const 
     if (h < 0 || h >= 3 * F) continue;
     const int64_t f = h / 3, c = h - 3 * f;
     const int64_t i[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-    if (i[0] < 0 || i[1] < 0 || i[2] < 0 || i[0] >= V || i[1] >= V || i[2] >= V) continue;
+    if (!sr_face_ok(i[0], i[1], i[2], V)) continue;
     if (i[0] == other || i[1] == other || i[2] == other) continue;
     double N0[3], N1[3];
     face_normal(verts + i[0] * 3, verts + i[1] * 3, verts + i[2] * 3, N0);
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256) void candidates(const float* __restrict__ vert
                                                    int64_t E, double reg, double flip_cos, float* __restrict__ pos, int64_t* __restrict__ key) {
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
     const int64_t a = edges[e * 2], b = edges[e * 2 + 1];
-    if (a < 0 || b < 0 || a >= V || b >= V || a == b) {
+    if (!sr_edge_ok(a, b, V)) {
       pos[e * 3] = 0.f; pos[e * 3 + 1] = 0.f; pos[e * 3 + 2] = 0.f; key[e] = INT64_MAX;
       continue;
     }
@@ -200,11 +196,8 @@ __global__ __launch_bounds__(256) void select(const int64_t* __restrict__ edges,
     selected[e] = sel ? 1 : 0;
     ns += sel ? 1 : 0; nc += cand ? 1 : 0;
   }
-  for (int m = SR_WAVE / 2; m > 0; m >>= 1) { ns += __shfl_xor(ns, m, SR_WAVE); nc += __shfl_xor(nc, m, SR_WAVE); }
-  if ((threadIdx.x & (SR_WAVE - 1)) == 0) {
-    if (ns) atomicAdd(record, (unsigned long long)ns);
-    if (nc) atomicAdd(record + 1, (unsigned long long)nc);
-  }
+  sr_record_add(record, ns);
+  sr_record_add(record + 1, nc);
 }
 
 // the selected edges share no endpoint, so every write below has one writer and Q[b] no writer at all
@@ -213,7 +206,7 @@ __global__ __launch_bounds__(256) void apply_vertices(const int64_t* __restrict_
   for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E; e += (int64_t)gridDim.x * blockDim.x) {
     if (!selected[e]) continue;
     const int64_t a = edges[e * 2], b = edges[e * 2 + 1];
-    if (a < 0 || b < 0 || a >= V || b >= V || a == b) continue;
+    if (!sr_edge_ok(a, b, V)) continue;
     verts[a * 3] = pos[e * 3]; verts[a * 3 + 1] = pos[e * 3 + 1]; verts[a * 3 + 2] = pos[e * 3 + 2];
 #pragma unroll
     for (int k = 0; k < SR_COLLAPSE_Q; ++k) Q[a * SR_COLLAPSE_Q + k] += Q[b * SR_COLLAPSE_Q + k];
@@ -224,21 +217,15 @@ __global__ __launch_bounds__(256) void apply_vertices(const int64_t* __restrict_
 __global__ __launch_bounds__(256) void apply_faces(const int64_t* __restrict__ faces, int64_t F, const int64_t* __restrict__ target, int64_t V,
                                                     int64_t* __restrict__ out_faces, uint8_t* __restrict__ keep) {
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    int64_t x = -1, y = -1, z = -1;
-    if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) { x = target[a]; y = target[b]; z = target[c]; }
+    int64_t x, y, z;
+    sr_face_remap(faces, f, target, V, x, y, z);
     out_faces[f * 3] = x; out_faces[f * 3 + 1] = y; out_faces[f * 3 + 2] = z;
-    keep[f] = x >= 0 && y >= 0 && z >= 0 && x < V && y < V && z < V && x != y && y != z && x != z ? 1 : 0;
+    keep[f] = sr_face_ok(x, y, z, V) && x != y && y != z && x != z ? 1 : 0;
   }
 }
 
 __global__ __launch_bounds__(256) void map_jump(const int64_t* __restrict__ P, int64_t V, int64_t* __restrict__ N, int32_t* __restrict__ changed) {
-  for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < V; v += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t p = P[v];
-    const int64_t g = p >= 0 && p < V ? P[p] : p;
-    N[v] = g;
-    if (g != p) *changed = 1;
-  }
+  sr_forest_jump(P, V, N, changed);
 }
 }  // namespace
 
@@ -248,13 +235,13 @@ __global__ __launch_bounds__(256) void map_jump(const int64_t* __restrict__ P, i
 extern "C" int sr_collapse_vertex_quadrics(const float* verts, int64_t V, const int64_t* faces, int64_t F, const int64_t* slots, const int64_t* offsets,
                                            double* quadrics, void* stream) {
   if (!verts || !faces || !slots || !offsets || !quadrics || V <= 0 || F <= 0 || V > SR_COLLAPSE_MAX_V || F > SR_COLLAPSE_MAX_F) return SR_EINVAL;
-  hipLaunchKernelGGL(vertex_quadrics, dim3(sr_stream_grid(V, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, slots, offsets, quadrics);
+  sr_launch_stream(vertex_quadrics, V, 256, stream, verts, V, faces, F, slots, offsets, quadrics);
   return sr_launch_status();
 }
 
 extern "C" int sr_collapse_edge_keys(const int64_t* faces, int64_t F, int64_t V, int64_t* key, void* stream) {
   if (!faces || !key || F <= 0 || V <= 0 || V > SR_COLLAPSE_MAX_V || F > SR_COLLAPSE_MAX_F) return SR_EINVAL;
-  hipLaunchKernelGGL(edge_keys, dim3(sr_stream_grid(3 * F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, V, key);
+  sr_launch_stream(edge_keys, 3 * F, 256, stream, faces, F, V, key);
   return sr_launch_status();
 }
 
@@ -265,8 +252,7 @@ extern "C" int sr_collapse_edge_heads(const int64_t* unique_key, const int64_t* 
     return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(locked, 0, (size_t)V * 4, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(edge_heads, dim3(sr_stream_grid(E, 256)), dim3(256), 0, st, unique_key, offsets, E, perm, faces, F, V, edges, count, opposite, locked,
-                     directed);
+  sr_launch_stream(edge_heads, E, 256, st, unique_key, offsets, E, perm, faces, F, V, edges, count, opposite, locked, directed);
   return sr_launch_status();
 }
 
@@ -278,16 +264,16 @@ extern "C" int sr_collapse_candidates(const float* verts, int64_t V, const int64
       !key || V <= 0 || F <= 0 || E <= 0 || V > SR_COLLAPSE_MAX_V || F > SR_COLLAPSE_MAX_F || E > 3 * F || !(reg > 0.) || !(reg < INFINITY) ||
       !(flip_cos >= -1.) || !(flip_cos < 1.))
     return SR_EINVAL;
-  hipLaunchKernelGGL(candidates, dim3(sr_stream_grid(E, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, quadrics, slots, offsets, neighbours,
-                     neighbour_offsets, edges, count, opposite, locked, E, reg, flip_cos, positions, key);
+  sr_launch_stream(candidates, E, 256, stream, verts, V, faces, F, quadrics, slots, offsets, neighbours, neighbour_offsets, edges, count, opposite, locked, E,
+                   reg, flip_cos, positions, key);
   return sr_launch_status();
 }
 
 extern "C" int sr_collapse_min1(const int64_t* edges, const int64_t* key, int64_t E, int64_t V, int64_t* m1, void* stream) {
   if (!edges || !key || !m1 || E <= 0 || V <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(fill64, dim3(sr_stream_grid(V, 256)), dim3(256), 0, st, m1, V, (int64_t)INT64_MAX);
-  hipLaunchKernelGGL(min1, dim3(sr_stream_grid(E, 256)), dim3(256), 0, st, edges, key, E, V, m1);
+  sr_launch_stream(fill64, V, 256, st, m1, V, (int64_t)INT64_MAX);
+  sr_launch_stream(min1, E, 256, st, edges, key, E, V, m1);
   return sr_launch_status();
 }
 
@@ -295,7 +281,7 @@ extern "C" int sr_collapse_min2(const int64_t* edges, int64_t E, int64_t V, cons
   if (!edges || !m1 || !m2 || m1 == m2 || E <= 0 || V <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemcpyAsync(m2, m1, (size_t)V * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(min2, dim3(sr_stream_grid(E, 256)), dim3(256), 0, st, edges, E, V, m1, m2);
+  sr_launch_stream(min2, E, 256, st, edges, E, V, m1, m2);
   return sr_launch_status();
 }
 
@@ -304,21 +290,20 @@ extern "C" int sr_collapse_select(const int64_t* edges, const int64_t* key, int6
   if (!edges || !key || !m2 || !selected || !record || E <= 0 || V <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(record, 0, 16, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(select, dim3(sr_stream_grid(E, 256)), dim3(256), 0, st, edges, key, E, V, m2, selected, (unsigned long long*)record);
+  sr_launch_stream(select, E, 256, st, edges, key, E, V, m2, selected, (unsigned long long*)record);
   return sr_launch_status();
 }
 
 extern "C" int sr_collapse_apply_vertices(const int64_t* edges, const float* positions, const uint8_t* selected, int64_t E, float* verts, int64_t V,
                                           double* quadrics, int64_t* target, void* stream) {
   if (!edges || !positions || !selected || !verts || !quadrics || !target || E <= 0 || V <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(apply_vertices, dim3(sr_stream_grid(E, 256)), dim3(256), 0, (hipStream_t)stream, edges, positions, selected, E, verts, V, quadrics,
-                     target);
+  sr_launch_stream(apply_vertices, E, 256, stream, edges, positions, selected, E, verts, V, quadrics, target);
   return sr_launch_status();
 }
 
 extern "C" int sr_collapse_apply_faces(const int64_t* faces, int64_t F, const int64_t* target, int64_t V, int64_t* out_faces, uint8_t* keep, void* stream) {
   if (!faces || !target || !out_faces || !keep || F <= 0 || V <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(apply_faces, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, target, V, out_faces, keep);
+  sr_launch_stream(apply_faces, F, 256, stream, faces, F, target, V, out_faces, keep);
   return sr_launch_status();
 }
 
@@ -326,6 +311,6 @@ extern "C" int sr_collapse_map_jump(const int64_t* parent, int64_t V, int64_t* n
   if (!parent || !next || !changed || parent == next || V <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(map_jump, dim3(sr_stream_grid(V, 256)), dim3(256), 0, st, parent, V, next, changed);
+  sr_launch_stream(map_jump, V, 256, st, parent, V, next, changed);
   return sr_launch_status();
 }

@@ -18,8 +18,11 @@
 //
 // Stream / gather work bound by HBM and by atomics on a few addresses; no float atomics anywhere: sums are sequential per thread (the
 // quadric sums: per lane, then a butterfly of fixed shape), the atomics are integer adds and min / max, so two calls give identical bits.
+// Shared with mesh_collapse.hip and stated once elsewhere: which rows are faces, half-edge corners, the face remap, the pointer jump and
+// the counter flush (mesh_device.h), the wave butterflies (sr_wave.h), the face normal and the plane quadric (quadric_device.h).
 #include "sr_common.h"
 #include "uv_device.h"
+#include "mesh_device.h"
 #include "quadric_device.h"
 
 namespace {
@@ -30,15 +33,6 @@ __device__ __forceinline__ int32_t ordered(float x) {
   return b ^ ((b >> 31) & 0x7fffffff);
 }
 __device__ __forceinline__ float unordered(int32_t o) { return __int_as_float(o ^ ((o >> 31) & 0x7fffffff)); }
-
-__device__ __forceinline__ int32_t wave_min(int32_t v) {
-  for (int m = SR_WAVE / 2; m > 0; m >>= 1) v = min(v, __shfl_xor(v, m, SR_WAVE));
-  return v;
-}
-__device__ __forceinline__ int32_t wave_max(int32_t v) {
-  for (int m = SR_WAVE / 2; m > 0; m >>= 1) v = max(v, __shfl_xor(v, m, SR_WAVE));
-  return v;
-}
 
 // ---------------------------------------------------------------------------------------------- simplify
 __global__ void bounds_init(int32_t* __restrict__ box) {
@@ -60,8 +54,8 @@ __global__ __launch_bounds__(256) void bounds_reduce(const float* __restrict__ v
     }
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { lo[k] = wave_min(lo[k]); hi[k] = wave_max(hi[k]); }
-  bad = wave_max(bad);
+  for (int k = 0; k < 3; ++k) { lo[k] = sr_wave_min(lo[k]); hi[k] = sr_wave_max(hi[k]); }
+  bad = sr_wave_max(bad);
   if ((threadIdx.x & (SR_WAVE - 1)) == 0) {
 #pragma unroll
     for (int k = 0; k < 3; ++k) { atomicMin(box + k, lo[k]); atomicMax(box + 3 + k, hi[k]); }
@@ -105,9 +99,8 @@ __global__ __launch_bounds__(256) void cell_mean(const float* __restrict__ verts
 __global__ __launch_bounds__(256) void face_keys(const int64_t* __restrict__ faces, int64_t F, const int64_t* __restrict__ vmap, int64_t V, int64_t Vn,
                                                   int64_t* __restrict__ out_faces, int64_t* __restrict__ key_hi, int64_t* __restrict__ key_lo) {
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    int64_t x = -1, y = -1, z = -1;
-    if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) { x = vmap[a]; y = vmap[b]; z = vmap[c]; }
+    int64_t x, y, z;
+    sr_face_remap(faces, f, vmap, V, x, y, z);
     out_faces[f * 3] = x; out_faces[f * 3 + 1] = y; out_faces[f * 3 + 2] = z;
     const bool dead = x < 0 || y < 0 || z < 0 || x >= Vn || y >= Vn || z >= Vn || x == y || y == z || x == z;
     const int64_t lo = min(x, min(y, z)), hi = max(x, max(y, z)), mid = x + y + z - lo - hi;
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(256) void cell_face_slots(const int64_t* __restrict
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
     int64_t x = C, y = C, z = C;
-    if (a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V) {
+    if (sr_face_ok(a, b, c, V)) {
       x = vmap[a]; y = vmap[b]; z = vmap[c];
       if (x < 0 || x > C) x = C;
       if (y < 0 || y > C || y == x) y = C;
@@ -146,10 +139,7 @@ __global__ __launch_bounds__(256) void cell_face_slots(const int64_t* __restrict
 
 #define SR_QUADRIC_LANES 16                            // lanes per cell: part of the stated order of the sums, not a tuning knob
 
-__device__ __forceinline__ double group_sum(double v) {
-  for (int m = SR_QUADRIC_LANES / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, SR_QUADRIC_LANES);   // (a + b = b + a: every lane ends with the same bits)
-  return v;
-}
+__device__ __forceinline__ double group_sum(double v) { return sr_wave_sum<double, SR_QUADRIC_LANES>(v); }
 
 // 16 lanes per occupied cell.  Lane l sums the plane quadrics of entries l, l + 16, ... of the cell's face list in that order, the 16
 // partial sums meet in a butterfly of fixed shape, and every lane then holds A (6 numbers) and b (3).  The mean is summed by every
@@ -172,16 +162,11 @@ __global__ __launch_bounds__(256) void cell_quadric(const float* __restrict__ ve
       const int64_t s = face_slots[e];
       if (s < 0 || s >= 3 * F) continue;
       const int64_t f = s / 3, i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
-      if (i0 < 0 || i1 < 0 || i2 < 0 || i0 >= V || i1 >= V || i2 >= V) continue;
-      const double px = (double)verts[i0 * 3], py = (double)verts[i0 * 3 + 1], pz = (double)verts[i0 * 3 + 2];
-      double N[3];
-      face_normal(verts + i0 * 3, verts + i1 * 3, verts + i2 * 3, N);
-      const double L = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
-      if (!(L > 0.) || !isfinite(L)) continue;
-      const double n0 = N[0] / L, n1 = N[1] / L, n2 = N[2] / L, w = 0.5 * L, d = n0 * px + n1 * py + n2 * pz;
-      const double w0 = w * n0, w1 = w * n1, w2 = w * n2, wd = w * d;
-      xx += w0 * n0; xy += w0 * n1; xz += w0 * n2; yy += w1 * n1; yz += w1 * n2; zz += w2 * n2;
-      bx += wd * n0; by += wd * n1; bz += wd * n2;
+      if (!sr_face_ok(i0, i1, i2, V)) continue;
+      PlaneQuadric p;
+      if (!plane_quadric(verts + i0 * 3, verts + i1 * 3, verts + i2 * 3, p)) continue;
+      xx += p.w0 * p.n0; xy += p.w0 * p.n1; xz += p.w0 * p.n2; yy += p.w1 * p.n1; yz += p.w1 * p.n2; zz += p.w2 * p.n2;
+      bx += p.wd * p.n0; by += p.wd * p.n1; bz += p.wd * p.n2;
     }
     xx = group_sum(xx); xy = group_sum(xy); xz = group_sum(xz); yy = group_sum(yy); yz = group_sum(yz); zz = group_sum(zz);
     bx = group_sum(bx); by = group_sum(by); bz = group_sum(bz);
@@ -234,18 +219,15 @@ __global__ __launch_bounds__(256) void face_flips(const float* __restrict__ vert
       const float* __restrict__ p = side ? new_verts : verts;
       const int64_t* __restrict__ t = side ? new_faces + g * 3 : faces + f * 3;
       const int64_t lim = side ? Vn : V, a = t[0], b = t[1], c = t[2];
-      if (a < 0 || b < 0 || c < 0 || a >= lim || b >= lim || c >= lim) { ok = false; break; }
+      if (!sr_face_ok(a, b, c, lim)) { ok = false; break; }
       face_normal(p + a * 3, p + b * 3, p + c * 3, N[side]);
     }
     if (!ok) continue;
     if (N[1][0] == 0. && N[1][1] == 0. && N[1][2] == 0.) ++flat;
     else if (N[0][0] * N[1][0] + N[0][1] * N[1][1] + N[0][2] * N[1][2] < 0.) ++flipped;
   }
-  for (int m = SR_WAVE / 2; m > 0; m >>= 1) { flipped += __shfl_xor(flipped, m, SR_WAVE); flat += __shfl_xor(flat, m, SR_WAVE); }
-  if ((threadIdx.x & (SR_WAVE - 1)) == 0) {
-    if (flipped) atomicAdd(counts, (unsigned long long)flipped);
-    if (flat) atomicAdd(counts + 1, (unsigned long long)flat);
-  }
+  sr_record_add(counts, flipped);
+  sr_record_add(counts + 1, flat);
 }
 
 // ---------------------------------------------------------------------------------------------- unwrap
@@ -264,7 +246,7 @@ __global__ __launch_bounds__(256) void chart_classify(const float* __restrict__ 
                                                        int32_t* __restrict__ cls) {
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    const bool ok = a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
+    const bool ok = sr_face_ok(a, b, c, V);
     cls[f] = ok ? face_class(verts + a * 3, verts + b * 3, verts + c * 3) : 0;
   }
 }
@@ -273,10 +255,8 @@ __global__ __launch_bounds__(256) void chart_classify(const float* __restrict__ 
 __global__ __launch_bounds__(256) void chart_edge_keys(const int64_t* __restrict__ faces, int64_t F, int64_t V, const int32_t* __restrict__ cls,
                                                         int64_t* __restrict__ key) {
   for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < 3 * F; h += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t f = h / 3, c = h - 3 * f;
-    const int64_t a = faces[h], b = faces[f * 3 + (c + 1) % 3];
-    const bool ok = a >= 0 && b >= 0 && a < V && b < V && a != b;
-    key[h] = ok ? (min(a, b) * V + max(a, b)) * 6 + cls[f] : -1;
+    const SrHalfEdge e = sr_half_edge(faces, h);
+    key[h] = sr_edge_ok(e.from, e.to, V) ? (min(e.from, e.to) * V + max(e.from, e.to)) * 6 + cls[h / 3] : -1;
   }
 }
 
@@ -296,12 +276,7 @@ __global__ __launch_bounds__(256) void chart_hook(const int64_t* __restrict__ sk
 }
 
 __global__ __launch_bounds__(256) void chart_jump(const int32_t* __restrict__ P, int64_t F, int32_t* __restrict__ Q, int32_t* __restrict__ changed) {
-  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
-    const int32_t p = P[f];
-    const int32_t g = p >= 0 && p < F ? P[p] : p;
-    Q[f] = g;
-    if (g != p) *changed = 1;
-  }
+  sr_forest_jump(P, F, Q, changed);
 }
 
 // (u, v) of a point under class `c`: the two axes after the dominant one, swapped for a negative sign
@@ -393,8 +368,7 @@ __global__ __launch_bounds__(256) void overlap_mark(const float* __restrict__ vt
 __global__ __launch_bounds__(256) void overlap_total(const int32_t* __restrict__ count, int64_t texels, unsigned long long* __restrict__ total) {
   int32_t n = 0;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < texels; i += (int64_t)gridDim.x * blockDim.x) n += count[i] >= 2 ? 1 : 0;
-  for (int m = SR_WAVE / 2; m > 0; m >>= 1) n += __shfl_xor(n, m, SR_WAVE);
-  if ((threadIdx.x & (SR_WAVE - 1)) == 0 && n) atomicAdd(total, (unsigned long long)n);
+  sr_record_add(total, n);
 }
 }  // namespace
 
@@ -402,7 +376,7 @@ extern "C" int sr_meshprep_bounds(const float* verts, int64_t V, int32_t* box, v
   if (!verts || !box || V <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(bounds_init, dim3(1), dim3(64), 0, st, box);
-  hipLaunchKernelGGL(bounds_reduce, dim3(sr_stream_grid(V, 256)), dim3(256), 0, st, verts, V, box);
+  sr_launch_stream(bounds_reduce, V, 256, st, verts, V, box);
   hipLaunchKernelGGL(bounds_finish, dim3(1), dim3(64), 0, st, box);
   return sr_launch_status();
 }
@@ -412,32 +386,32 @@ extern "C" int sr_meshprep_cell_keys(const float* verts, int64_t V, const float*
   if (!verts || !lo || !key || V <= 0 || !(cell > 0.f) || nx <= 0 || ny <= 0 || nz <= 0) return SR_EINVAL;
   const __int128 lim = (__int128)1 << 62;                                                 // the keys need nx ny nz < 2^62
   if ((__int128)nx * ny >= lim || (__int128)nx * ny * nz >= lim) return SR_EINVAL;
-  hipLaunchKernelGGL(cell_keys, dim3(sr_stream_grid(V, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, lo, cell, nx, ny, nz, key);
+  sr_launch_stream(cell_keys, V, 256, stream, verts, V, lo, cell, nx, ny, nz, key);
   return sr_launch_status();
 }
 
 extern "C" int sr_meshprep_cell_mean(const float* verts, int64_t V, const int64_t* order, const int64_t* offsets, int64_t C, float* out, void* stream) {
   if (!verts || !order || !offsets || !out || V <= 0 || C <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(cell_mean, dim3(sr_stream_grid(C, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, order, offsets, C, out);
+  sr_launch_stream(cell_mean, C, 256, stream, verts, V, order, offsets, C, out);
   return sr_launch_status();
 }
 
 extern "C" int sr_meshprep_face_keys(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t Vn, int64_t* out_faces,
                                      int64_t* key_hi, int64_t* key_lo, void* stream) {
   if (!faces || !vertex_map || !out_faces || !key_hi || !key_lo || F <= 0 || V <= 0 || Vn <= 0 || Vn > ((int64_t)1 << 31)) return SR_EINVAL;
-  hipLaunchKernelGGL(face_keys, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, vertex_map, V, Vn, out_faces, key_hi, key_lo);
+  sr_launch_stream(face_keys, F, 256, stream, faces, F, vertex_map, V, Vn, out_faces, key_hi, key_lo);
   return sr_launch_status();
 }
 
 extern "C" int sr_meshprep_face_first(const int64_t* key_hi, const int64_t* key_lo, const int64_t* perm, int64_t F, uint8_t* keep, void* stream) {
   if (!key_hi || !key_lo || !perm || !keep || F <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(face_first, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, key_hi, key_lo, perm, F, keep);
+  sr_launch_stream(face_first, F, 256, stream, key_hi, key_lo, perm, F, keep);
   return sr_launch_status();
 }
 
 extern "C" int sr_meshprep_cell_faces(const int64_t* faces, int64_t F, const int64_t* vertex_map, int64_t V, int64_t C, int64_t* slot, void* stream) {
   if (!faces || !vertex_map || !slot || F <= 0 || V <= 0 || C <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(cell_face_slots, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, vertex_map, V, C, slot);
+  sr_launch_stream(cell_face_slots, F, 256, stream, faces, F, vertex_map, V, C, slot);
   return sr_launch_status();
 }
 
@@ -449,8 +423,8 @@ extern "C" int sr_meshprep_cell_quadric(const float* verts, int64_t V, const int
       C <= 0 || !(cell > 0.f) || nx <= 0 || ny <= 0 || !(reg > 0.) || !(reg < INFINITY))
     return SR_EINVAL;
   if (F > INT64_MAX / 3 || C > INT64_MAX / SR_QUADRIC_LANES || (__int128)nx * ny >= ((__int128)1 << 62)) return SR_EINVAL;
-  hipLaunchKernelGGL(cell_quadric, dim3(sr_stream_grid(C * SR_QUADRIC_LANES, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, face_slots,
-                     face_offsets, order, offsets, cells, C, lo, cell, nx, ny, reg, out, flags, shift);
+  sr_launch_stream(cell_quadric, C * SR_QUADRIC_LANES, 256, stream, verts, V, faces, F, face_slots, face_offsets, order, offsets, cells, C, lo, cell, nx, ny,
+                   reg, out, flags, shift);
   return sr_launch_status();
 }
 
@@ -459,20 +433,19 @@ extern "C" int sr_meshprep_face_flips(const float* verts, int64_t V, const int64
   if (!verts || !faces || !new_verts || !new_faces || !source || !counts || V <= 0 || F <= 0 || Vn <= 0 || Fn <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(counts, 0, 16, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(face_flips, dim3(sr_stream_grid(Fn, 256)), dim3(256), 0, st, verts, V, faces, F, new_verts, Vn, new_faces, source, Fn,
-                     (unsigned long long*)counts);
+  sr_launch_stream(face_flips, Fn, 256, st, verts, V, faces, F, new_verts, Vn, new_faces, source, Fn, (unsigned long long*)counts);
   return sr_launch_status();
 }
 
 extern "C" int sr_chart_classify(const float* verts, int64_t V, const int64_t* faces, int64_t F, int32_t* cls, void* stream) {
   if (!verts || !faces || !cls || V <= 0 || F <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(chart_classify, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, cls);
+  sr_launch_stream(chart_classify, F, 256, stream, verts, V, faces, F, cls);
   return sr_launch_status();
 }
 
 extern "C" int sr_chart_edge_keys(const int64_t* faces, int64_t F, int64_t V, const int32_t* cls, int64_t* key, void* stream) {
   if (!faces || !cls || !key || F <= 0 || V <= 0 || V > ((int64_t)1 << 30)) return SR_EINVAL;       // (V V 6 < 2^63)
-  hipLaunchKernelGGL(chart_edge_keys, dim3(sr_stream_grid(3 * F, 256)), dim3(256), 0, (hipStream_t)stream, faces, F, V, cls, key);
+  sr_launch_stream(chart_edge_keys, 3 * F, 256, stream, faces, F, V, cls, key);
   return sr_launch_status();
 }
 
@@ -482,7 +455,7 @@ extern "C" int sr_chart_hook(const int64_t* sorted_key, const int64_t* perm, int
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SR_ELAUNCH;
   if (hipMemcpyAsync(next, parent, (size_t)F * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(chart_hook, dim3(sr_stream_grid(n, 256)), dim3(256), 0, st, sorted_key, perm, n, parent, next, F, changed);
+  sr_launch_stream(chart_hook, n, 256, st, sorted_key, perm, n, parent, next, F, changed);
   return sr_launch_status();
 }
 
@@ -490,7 +463,7 @@ extern "C" int sr_chart_jump(const int32_t* parent, int64_t F, int32_t* next, in
   if (!parent || !next || !changed || F <= 0 || F >= INT32_MAX) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(chart_jump, dim3(sr_stream_grid(F, 256)), dim3(256), 0, st, parent, F, next, changed);
+  sr_launch_stream(chart_jump, F, 256, st, parent, F, next, changed);
   return sr_launch_status();
 }
 
@@ -498,9 +471,9 @@ extern "C" int sr_chart_bbox(const float* verts, int64_t V, const int64_t* faces
                              int32_t* box, float* bbox_min, float* extent, void* stream) {
   if (!verts || !faces || !cls || !chart || !box || !bbox_min || !extent || V <= 0 || F <= 0 || C <= 0) return SR_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(box_init, dim3(sr_stream_grid(4 * C, 256)), dim3(256), 0, st, box, C);
-  hipLaunchKernelGGL(chart_box, dim3(sr_stream_grid(F, 256)), dim3(256), 0, st, verts, V, faces, F, cls, chart, C, box);
-  hipLaunchKernelGGL(box_finish, dim3(sr_stream_grid(2 * C, 256)), dim3(256), 0, st, (const int32_t*)box, C, bbox_min, extent);
+  sr_launch_stream(box_init, 4 * C, 256, st, box, C);
+  sr_launch_stream(chart_box, F, 256, st, verts, V, faces, F, cls, chart, C, box);
+  sr_launch_stream(box_finish, 2 * C, 256, st, (const int32_t*)box, C, bbox_min, extent);
   return sr_launch_status();
 }
 
@@ -508,8 +481,7 @@ extern "C" int sr_chart_uv(const float* verts, int64_t V, const int64_t* faces, 
                            const float* bbox_min, const int64_t* origin, double scale, int32_t padding, int32_t R, float* vt, void* stream) {
   if (!verts || !faces || !cls || !chart || !bbox_min || !origin || !vt || V <= 0 || F <= 0 || C <= 0 || !(scale >= 0.) || padding < 0 || R <= 0)
     return SR_EINVAL;
-  hipLaunchKernelGGL(chart_uv, dim3(sr_stream_grid(3 * F, 256)), dim3(256), 0, (hipStream_t)stream, verts, V, faces, F, cls, chart, C, bbox_min, origin,
-                     scale, padding, R, vt);
+  sr_launch_stream(chart_uv, 3 * F, 256, stream, verts, V, faces, F, cls, chart, C, bbox_min, origin, scale, padding, R, vt);
   return sr_launch_status();
 }
 
@@ -519,7 +491,7 @@ extern "C" int sr_uv_overlap_count(const float* vt, const int64_t* ft, int64_t V
   hipStream_t st = (hipStream_t)stream;
   const int64_t texels = (int64_t)R * R;
   if (hipMemsetAsync(count, 0, (size_t)texels * 4, st) != hipSuccess || hipMemsetAsync(total, 0, 8, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(overlap_mark, dim3(sr_stream_grid(F * SR_WAVE, 256)), dim3(256), 0, st, vt, ft, Vt, F, R, eps, count);
-  hipLaunchKernelGGL(overlap_total, dim3(sr_stream_grid(texels, 256)), dim3(256), 0, st, (const int32_t*)count, texels, (unsigned long long*)total);
+  sr_launch_stream(overlap_mark, F * SR_WAVE, 256, st, vt, ft, Vt, F, R, eps, count);
+  sr_launch_stream(overlap_total, texels, 256, st, (const int32_t*)count, texels, (unsigned long long*)total);
   return sr_launch_status();
 }

@@ -19,6 +19,7 @@
 // inside a thread is therefore done in double (float32 in memory, double in registers), which costs nothing measurable here and leaves
 // the float32 rounding of the stored q / e / staged rows and of the final gradient as the only error against a float64 evaluation.
 #include "sr_common.h"
+#include "sr_wave.h"
 
 namespace {
 constexpr int kBlk = 256;
@@ -35,8 +36,7 @@ __device__ __forceinline__ void st3(float* __restrict__ p, int64_t i, const D3& 
 
 // fixed order: lanes of a wave (xor butterfly) -> the waves of the workgroup in ascending order; the total returns in thread 0
 __device__ __forceinline__ double block_sum(double v, double* smem /* [kBlk / 64] */) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
+  v = sr_wave_sum(v);
   if ((threadIdx.x & 63) == 0) smem[threadIdx.x >> 6] = v;
   __syncthreads();
   double t = 0.;

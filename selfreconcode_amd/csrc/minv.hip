@@ -95,14 +95,14 @@ template <typename T>
 int minv_fwd(const T* ms, T* invs, uint8_t* checks, int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!ms || !invs || !checks))) return SR_EINVAL;
   if (n == 0) return SR_OK;
-  hipLaunchKernelGGL(minv_fwd_kernel<T>, dim3(sr_stream_grid(n, kMat)), dim3(kMat), 0, (hipStream_t)stream, ms, invs, checks, n);
+  sr_launch_stream(minv_fwd_kernel<T>, n, kMat, stream, ms, invs, checks, n);
   return sr_launch_status();
 }
 template <typename T>
 int minv_bwd(const T* grads, const T* invs, T* outs, int64_t n, void* stream) {
   if (n < 0 || (n > 0 && (!grads || !invs || !outs))) return SR_EINVAL;
   if (n == 0) return SR_OK;
-  hipLaunchKernelGGL(minv_bwd_kernel<T>, dim3(sr_stream_grid(n, kMat)), dim3(kMat), 0, (hipStream_t)stream, grads, invs, outs, n);
+  sr_launch_stream(minv_bwd_kernel<T>, n, kMat, stream, grads, invs, outs, n);
   return sr_launch_status();
 }
 }  // namespace

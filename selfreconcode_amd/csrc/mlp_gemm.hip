@@ -955,8 +955,8 @@ int sr_mlp_gemm_tn(const sr_gemm_tn_args* a, void* stream) {
                          rows_per_split);
   }
   const int64_t total = (int64_t)a->N * a->lddw / 4 + (a->db ? a->N : 0);
-  hipLaunchKernelGGL(slab_reduce_kernel, dim3(sr_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, a->partial, a->dW,
-                     a->N, a->K, a->lddw, a->R > 0 ? a->splits : 0, a->accumulate, a->db_partial, a->db);
+  sr_launch_stream(slab_reduce_kernel, total, 256, stream, a->partial, a->dW, a->N, a->K, a->lddw, a->R > 0 ? a->splits : 0, a->accumulate, a->db_partial,
+                   a->db);
   return sr_launch_status();
 }
 
@@ -1047,8 +1047,7 @@ extern "C" int sr_pe_embed(const float* x, int64_t P, int32_t L, const float* ba
   if (P < 0 || L < 0 || L > 16 || E < 0 || (group != 1 && group != 4) || ldo < 3 + 6 * L + E) return SR_EINVAL;
   if (P == 0) return SR_OK;
   if (!x || !out || (L > 0 && !band_weights) || (E > 0 && !extra)) return SR_EINVAL;
-  hipLaunchKernelGGL(pe_embed_kernel, dim3(sr_stream_grid(P * ldo, 256)), dim3(256), 0, (hipStream_t)stream, x, P, L, band_weights,
-                     extra, ldextra, E, extra_index, group, out, ldo);
+  sr_launch_stream(pe_embed_kernel, P * ldo, 256, stream, x, P, L, band_weights, extra, ldextra, E, extra_index, group, out, ldo);
   return sr_launch_status();
 }
 
@@ -1084,7 +1083,6 @@ extern "C" int sr_pe_embed_bwd(const float* x, int64_t P, int32_t L, const float
   if (P < 0 || L < 0 || L > 16 || (group != 1 && group != 4) || ldg < 3 + 6 * L) return SR_EINVAL;
   if (P == 0) return SR_OK;
   if (!x || !gA0 || !xbar || (L > 0 && !band_weights)) return SR_EINVAL;
-  hipLaunchKernelGGL(pe_embed_bwd_kernel, dim3(sr_stream_grid(P * 3, 256)), dim3(256), 0, (hipStream_t)stream, x, P, L, band_weights,
-                     group, gA0, ldg, xbar);
+  sr_launch_stream(pe_embed_bwd_kernel, P * 3, 256, stream, x, P, L, band_weights, group, gA0, ldg, xbar);
   return sr_launch_status();
 }

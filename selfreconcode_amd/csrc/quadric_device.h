@@ -1,5 +1,5 @@
 // Device functions shared by the quadric placement of the vertex clustering (mesh_prep.hip) and the edge-collapse decimation
-// (mesh_collapse.hip): the face normal both build their plane quadrics from, and the regularised 3 x 3 solve.
+// (mesh_collapse.hip): the face normal, the plane quadric of a face that both sum, and the regularised 3 x 3 solve.
 #pragma once
 #include "sr_common.h"
 
@@ -11,6 +11,23 @@ static __device__ __forceinline__ void face_normal(const float* __restrict__ pa,
   const double vx = (double)pc[0] - (double)pa[0], vy = (double)pc[1] - (double)pa[1], vz = (double)pc[2] - (double)pa[2];
   const double yz = uy * vz, zy = uz * vy, zx = uz * vx, xz = ux * vz, xy = ux * vy, yx = uy * vx;
   n[0] = yz - zy; n[1] = zx - xz; n[2] = xy - yx;
+}
+
+// The area-weighted plane quadric of the face (pa, pb, pc), as the factors of its terms: n the unit normal, w = area, d = n . pa, and
+// w0 w1 w2 wd = w (n0 n1 n2 d).  The quadric is A = w n n^T (xx = w0 n0, xy = w0 n1, xz = w0 n2, yy = w1 n1, yz = w1 n2, zz = w2 n2),
+// b = w d n (wd n0, wd n1, wd n2) and c = w d^2 (wd d).  The caller forms each product inside its own `+=`, so that the compiler
+// contracts product and sum as it did when every kernel spelled this out.  false for a face without area or with a non-finite one.
+struct PlaneQuadric { double n0, n1, n2, d, w0, w1, w2, wd; };
+static __device__ __forceinline__ bool plane_quadric(const float* __restrict__ pa, const float* __restrict__ pb, const float* __restrict__ pc, PlaneQuadric& p) {
+  double N[3];
+  face_normal(pa, pb, pc, N);
+  const double L = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+  if (!(L > 0.) || !isfinite(L)) return false;
+  const double w = 0.5 * L;
+  p.n0 = N[0] / L; p.n1 = N[1] / L; p.n2 = N[2] / L;
+  p.d = p.n0 * (double)pa[0] + p.n1 * (double)pa[1] + p.n2 * (double)pa[2];
+  p.w0 = w * p.n0; p.w1 = w * p.n1; p.w2 = w * p.n2; p.wd = w * p.d;
+  return true;
 }
 
 // x = m + (A + lam I)^-1 (b - A m), lam = reg trace(A) / 3, for the symmetric A = (xx xy xz; xy yy yz; xz yz zz), by Cholesky: the

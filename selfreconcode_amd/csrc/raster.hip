@@ -22,9 +22,10 @@
 //
 // Both work in pytorch3d's NDC frame: +x left, +y up, pixel (row, col) centred at (1 - (2 col + 1)/W, 1 - (2 row + 1)/H).
 #include "sr_common.h"
+#include "sr_wave.h"
 
 namespace {
-constexpr float kEps = 1e-8f;        // kEpsilon of pytorch3d's geometry_utils.cuh
+constexpr float kEps = 1e-8f;       // kEpsilon of pytorch3d's geometry_utils.cuh
 constexpr float kAlphaMax = 1.0f - 1e-6f;   // a point exactly on a pixel centre would make log(1 - a) infinite
 
 __device__ __forceinline__ float pix_to_ndc(int i, int S) { return 1.0f - (2.0f * (float)i + 1.0f) / (float)S; }
@@ -135,25 +136,8 @@ __global__ __launch_bounds__(256) void ps_gather(const float* __restrict__ xy, c
   }
 }
 
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
 // Pass 4: one wave per queued pixel: K-th smallest key (binary search on the 64 key bits), then the composite of the
 // keys up to it (integer sums: deterministic whatever order the bucket was filled in).
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void ps_select(const float* __restrict__ xy, int H, int W, float radius, int K, float scale, const uint32_t* __restrict__ count,
                                                   const unsigned long long* __restrict__ over, const int64_t* __restrict__ over_pix,
                                                   const int64_t* __restrict__ over_off, const unsigned long long* __restrict__ bucket,
@@ -175,7 +159,7 @@ __global__ __launch_bounds__(256) void ps_select(const float* __restrict__ xy, i
         const unsigned long long k = keys[j];
         zeros += ((k & hi_mask) == (prefix & hi_mask) && !((k >> bit) & 1ull)) ? 1u : 0u;
       }
-      zeros = wave_sum_u32(zeros);
+      zeros = sr_wave_sum(zeros);
       if (want > zeros) { want -= zeros; prefix |= 1ull << bit; }
     }
     const int c = (int)(o % W), r = (int)((o / W) % H);
@@ -188,7 +172,7 @@ __global__ __launch_bounds__(256) void ps_select(const float* __restrict__ xy, i
       const float dx = xf - xy[i * 2], dy = yf - xy[i * 2 + 1];
       qsum += ps_quantise(dx * dx + dy * dy, r2, scale);
     }
-    qsum = wave_sum_i64(qsum);
+    qsum = sr_wave_sum(qsum);
     const float acc = (float)qsum / scale;
     if (lane == 0) { thresh[o] = prefix; logT[o] = acc; mask[o] = 1.0f - __expf(acc); }
   }
@@ -269,10 +253,10 @@ int sr_points_silhouette_fwd(const float* xy_ndc, const float* z, int64_t nimg, 
   int64_t* over_off = (int64_t*)(ws + L.over_off); uint32_t* fill = (uint32_t*)(ws + L.fill);
   unsigned long long* bucket = (unsigned long long*)(ws + L.bucket);
   if (npts > 0)
-    hipLaunchKernelGGL(ps_accumulate, dim3(sr_stream_grid(npts, 256)), dim3(256), 0, st, xy_ndc, z, npts, pts_per_img, H, W, radius, scale, acc);
-  hipLaunchKernelGGL(ps_resolve, dim3(sr_stream_grid(L.npix, 256)), dim3(256), 0, st, L.npix, K, 1.0f / scale, acc, count, logT, mask, thresh, slot_of, over, over_pix, over_off);
+    sr_launch_stream(ps_accumulate, npts, 256, st, xy_ndc, z, npts, pts_per_img, H, W, radius, scale, acc);
+  sr_launch_stream(ps_resolve, L.npix, 256, st, L.npix, K, 1.0f / scale, acc, count, logT, mask, thresh, slot_of, over, over_pix, over_off);
   if (npts > 0) {
-    hipLaunchKernelGGL(ps_gather, dim3(sr_stream_grid(npts, 256)), dim3(256), 0, st, xy_ndc, z, npts, pts_per_img, H, W, radius, slot_of, over, over_off, fill, bucket);
+    sr_launch_stream(ps_gather, npts, 256, st, xy_ndc, z, npts, pts_per_img, H, W, radius, slot_of, over, over_off, fill, bucket);
     hipLaunchKernelGGL(ps_select, dim3(512), dim3(256), 0, st, xy_ndc, H, W, radius, K, scale, count, over, over_pix, over_off, bucket, mask, logT, thresh);
   }
   return sr_launch_status();
@@ -286,8 +270,8 @@ int sr_points_silhouette_bwd(const float* xy_ndc, const float* z, int64_t nimg, 
   if (!xy_ndc || !z || !workspace || !gmask || !gxy) return SR_EINVAL;
   const PsLayout L = ps_layout(nimg, pts_per_img, H, W, radius);
   const char* ws = (const char*)workspace;
-  hipLaunchKernelGGL(ps_backward, dim3(sr_stream_grid(npts, 256)), dim3(256), 0, (hipStream_t)stream, xy_ndc, z, npts, pts_per_img, H, W, radius,
-                     (const float*)(ws + L.logT), (const unsigned long long*)(ws + L.thresh), gmask, gxy);
+  sr_launch_stream(ps_backward, npts, 256, stream, xy_ndc, z, npts, pts_per_img, H, W, radius, (const float*)(ws + L.logT),
+                   (const unsigned long long*)(ws + L.thresh), gmask, gxy);
   return sr_launch_status();
 }
 }
@@ -462,12 +446,10 @@ extern "C" int sr_rasterize_meshes(const float* xy_ndc, const float* z, const in
     unsigned long long* big_count = (unsigned long long*)bary;
     const int64_t big_cap = nimg * H * W;
     if (hipMemsetAsync(big_count, 0, 8, st) != hipSuccess) return SR_ELAUNCH;
-    hipLaunchKernelGGL(rm_pass1, dim3(sr_stream_grid(nimg * F, 256)), dim3(256), 0, st, xy_ndc, z, faces, nimg, V, F, H, W,
-                       (unsigned long long*)zbuf_u64, pix_to_face, big_count, big_cap);
+    sr_launch_stream(rm_pass1, nimg * F, 256, st, xy_ndc, z, faces, nimg, V, F, H, W, (unsigned long long*)zbuf_u64, pix_to_face, big_count, big_cap);
     hipLaunchKernelGGL(rm_pass1b, dim3(512), dim3(256), 0, st, xy_ndc, z, faces, V, F, H, W, (unsigned long long*)zbuf_u64, pix_to_face,
                        big_count, big_cap);
   }
-  hipLaunchKernelGGL(rm_pass2, dim3(sr_stream_grid(nimg * H * W, 256)), dim3(256), 0, st, xy_ndc, z, faces, nimg, V, F, H, W,
-                     (const unsigned long long*)zbuf_u64, pix_to_face, bary, zout);
+  sr_launch_stream(rm_pass2, nimg * H * W, 256, st, xy_ndc, z, faces, nimg, V, F, H, W, (const unsigned long long*)zbuf_u64, pix_to_face, bary, zout);
   return sr_launch_status();
 }

@@ -279,7 +279,7 @@ int sr_refine_embed(const sr_refine_args* a, int32_t phase, void* stream) {
   const int rc = check_args(a);
   if (rc != SR_OK || a->P == 0) return rc;
   if (phase < 0 || phase > a->times + 1 || !a->a0 || !a->a0d || !a->w_sdf || !a->w_def || (a->E > 0 && !a->conds)) return SR_EINVAL;
-  hipLaunchKernelGGL(refine_embed_kernel, dim3(sr_stream_grid((int64_t)a->P * (a->ld_a0 + a->ld_a0d), 256)), dim3(256), 0, (hipStream_t)stream, *a, phase);
+  sr_launch_stream(refine_embed_kernel, (int64_t)a->P * (a->ld_a0 + a->ld_a0d), 256, stream, *a, phase);
   return sr_launch_status();
 }
 
@@ -302,7 +302,7 @@ int sr_refine_finish(const sr_refine_args* a, int32_t phase, void* stream) {
   if (phase < 1 || phase > a->times || !a->conv || !a->t || !a->s || !a->a0bar || !a->a0dbar || !a->sdf_out || !a->w_sdf || !a->w_def) return SR_EINVAL;
   if (a->ld_a0bar < 3 + 6 * a->L_sdf || a->ld_a0dbar < 3 + 6 * a->L_def || (a->skipbar && a->n_skip > a->ld_skipbar)) return SR_EINVAL;
   if ((a->a0 != nullptr) != (a->a0d != nullptr) || (a->E > 0 && a->a0 && !a->conds)) return SR_EINVAL;
-  hipLaunchKernelGGL(refine_finish_kernel, dim3(sr_stream_grid((int64_t)a->P * (256 / kEnq), 256)), dim3(256), 0, (hipStream_t)stream, *a, phase);
+  sr_launch_stream(refine_finish_kernel, (int64_t)a->P * (256 / kEnq), 256, stream, *a, phase);
   return sr_launch_status();
 }
 }

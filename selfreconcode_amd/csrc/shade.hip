@@ -11,18 +11,15 @@
 //
 // All of it is a bandwidth-bound gather: no LDS tiling, no MFMA.
 #include "sr_common.h"
+#include "mesh_device.h"
 
 namespace {
-
-__device__ __forceinline__ bool face_ok(int64_t a, int64_t b, int64_t c, int64_t V) {
-  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;     // -1: marching-cubes border faces (skipped, as the rasteriser does)
-}
 
 // offsets[v + 1] += number of corners of used faces at v (integer atomics: the counts do not depend on the order)
 __global__ __launch_bounds__(256) void adj_count(const int64_t* __restrict__ faces, int64_t V, int64_t F, unsigned long long* __restrict__ offsets) {
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    if (!face_ok(a, b, c, V)) continue;
+    if (!sr_face_ok(a, b, c, V)) continue;
     atomicAdd(offsets + a + 1, 1ull); atomicAdd(offsets + b + 1, 1ull); atomicAdd(offsets + c + 1, 1ull);
   }
 }
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(256) void adj_fill(const int64_t* __restrict__ face
                                                  int32_t* __restrict__ cursor, int64_t* __restrict__ keys) {
   for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
     const int64_t v[3] = {faces[f * 3], faces[f * 3 + 1], faces[f * 3 + 2]};
-    if (!face_ok(v[0], v[1], v[2], V)) continue;
+    if (!sr_face_ok(v[0], v[1], v[2], V)) continue;
 #pragma unroll
     for (int c = 0; c < 3; ++c) keys[offsets[v[c]] + atomicAdd(cursor + v[c], 1)] = 3 * f + c;
   }
@@ -125,7 +122,7 @@ __global__ __launch_bounds__(256) void phong_shade(const float* __restrict__ ver
     if (p >= 0 && p < N * F) {
       const int64_t fi = p / F, f = p - fi * F;              // packed index: the face's mesh is image fi
       const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-      if (face_ok(a, b, c, V)) {
+      if (sr_face_ok(a, b, c, V)) {
         const float b0 = bary[i * 3], b1 = bary[i * 3 + 1], b2 = bary[i * 3 + 2];
         const float* P = verts + fi * V * 3;
         const float* Q = normals + fi * V * 3;
@@ -165,13 +162,13 @@ extern "C" int sr_vertex_adjacency(const int64_t* faces, int64_t V, int64_t F, i
   hipLaunchKernelGGL(adj_count, dim3(g), dim3(256), 0, st, faces, V, F, (unsigned long long*)offsets);
   hipLaunchKernelGGL(adj_scan, dim3(1), dim3(1024), 0, st, offsets, V + 1);
   hipLaunchKernelGGL(adj_fill, dim3(g), dim3(256), 0, st, faces, V, F, (const int64_t*)offsets, cursor, (int64_t*)nbr);
-  hipLaunchKernelGGL(adj_finish, dim3(sr_stream_grid(V, 256)), dim3(256), 0, st, faces, V, (const int64_t*)offsets, (int64_t*)nbr, (int2*)nbr);
+  sr_launch_stream(adj_finish, V, 256, st, faces, V, (const int64_t*)offsets, (int64_t*)nbr, (int2*)nbr);
   return sr_launch_status();
 }
 
 extern "C" int sr_vertex_normals(const float* verts, int64_t N, int64_t V, const int64_t* offsets, const int32_t* nbr, float* normals, void* stream) {
   if (!verts || !offsets || !nbr || !normals || N <= 0 || V <= 0 || V > INT32_MAX || ((uintptr_t)nbr & 7)) return SR_EINVAL;
-  hipLaunchKernelGGL(vn_gather, dim3(sr_stream_grid(N * V, 256)), dim3(256), 0, (hipStream_t)stream, verts, N, V, offsets, (const int2*)nbr, normals);
+  sr_launch_stream(vn_gather, N * V, 256, stream, verts, N, V, offsets, (const int2*)nbr, normals);
   return sr_launch_status();
 }
 
@@ -187,7 +184,6 @@ extern "C" int sr_shade_phong(const float* verts, const float* normals, const in
   }
   ph.shininess = host_phong[9];
   const int64_t HW = (int64_t)H * W;
-  hipLaunchKernelGGL(phong_shade, dim3(sr_stream_grid(N * HW, 256)), dim3(256), 0, (hipStream_t)stream, verts, normals, faces, N, V, F, HW,
-                     pix_to_face, bary, cam_pos, light_loc, ph, (float4*)rgba);
+  sr_launch_stream(phong_shade, N * HW, 256, stream, verts, normals, faces, N, V, F, HW, pix_to_face, bary, cam_pos, light_loc, ph, (float4*)rgba);
   return sr_launch_status();
 }

@@ -18,6 +18,7 @@
 //     what the two launches before wrote: per lane ascending, the xor butterfly inside a wave, the waves in ascending order.
 // No atomics; every loop is bounded by an integer fixed before it starts; two calls give identical bits.
 #include "sr_common.h"
+#include "sr_wave.h"
 
 #define EDT_MAX_DIM 8192
 #define EDT_GINF 32768                    // g of a column without a mask pixel; its square is SR_EDT_EMPTY
@@ -239,12 +240,7 @@ __global__ __launch_bounds__(SIL_GRAD_BLOCK) void sil_grad_kernel(const float* _
       nout += valid[(int64_t)t * V + v] != 2;
     }
     for (int s = tid; s < n; s += SIL_GRAD_BLOCK) acc_cov += sres[((int64_t)t * S + s) * 3];
-#pragma unroll
-    for (int off = SR_WAVE / 2; off >= 1; off >>= 1) {
-      acc_in += __shfl_xor(acc_in, off, SR_WAVE);
-      acc_cov += __shfl_xor(acc_cov, off, SR_WAVE);
-      nout += __shfl_xor(nout, off, SR_WAVE);
-    }
+    acc_in = sr_wave_sum(acc_in); acc_cov = sr_wave_sum(acc_cov); nout = sr_wave_sum(nout);
     if ((tid & (SR_WAVE - 1)) == 0) { wsum[0][tid / SR_WAVE] = acc_in; wsum[1][tid / SR_WAVE] = acc_cov; wcnt[tid / SR_WAVE] = nout; }
     __syncthreads();
     if (tid == 0) {

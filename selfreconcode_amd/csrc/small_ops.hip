@@ -5,6 +5,7 @@
 //    would dominate the iteration).  Singular values descending, like torch.svd.
 //  (the point-silhouette renderer and the mesh rasteriser live in raster.hip)
 #include "sr_common.h"
+#include "sr_wave.h"
 
 namespace {
 __device__ __forceinline__ void jacobi_rotate(float (&S)[3][3], float (&V)[3][3], int p, int q) {
@@ -70,7 +71,7 @@ int sr_svd3x3(const float* A, int64_t n, float* U, float* S, float* V, void* str
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!A || !U || !S || !V) return SR_EINVAL;
-  hipLaunchKernelGGL(svd3_kernel, dim3(sr_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, A, n, U, S, V);
+  sr_launch_stream(svd3_kernel, n, 256, stream, A, n, U, S, V);
   return sr_launch_status();
 }
 }
@@ -84,12 +85,6 @@ int sr_svd3x3(const float* A, int64_t n, float* U, float* S, float* V, void* str
 //        (aten::_weight_norm_interface_backward), or gw = dW[:, :K] for a plain layer; optionally added to existing gradients.
 // One wave per weight row.
 namespace {
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void pack_weights_kernel(sr_pack_table t) {
   const sr_pack_layer L = t.layer[blockIdx.y];
   const int lane = threadIdx.x & 63;
@@ -101,7 +96,7 @@ __global__ __launch_bounds__(256) void pack_weights_kernel(sr_pack_table t) {
       if (L.g) {
         float ss = 0.f;
         for (int k = lane; k < L.K; k += 64) ss += v[k] * v[k];
-        const float nrm = sqrtf(wave_sum64(ss));
+        const float nrm = sqrtf(sr_wave_sum(ss));
         if (lane == 0) L.norms[n] = nrm;
         scale = L.g[n] / nrm;
       }
@@ -129,7 +124,7 @@ __global__ __launch_bounds__(256) void unpack_grads_kernel(sr_unpack_table t) {
       const float* v = L.v + (int64_t)n * L.K;
       float dot = 0.f;
       for (int k = lane; k < L.K; k += 64) dot += d[k] * v[k];
-      dot = wave_sum64(dot);
+      dot = sr_wave_sum(dot);
       const float nrm = L.norms[n], inv = 1.f / nrm;
       const float a = L.g[n] * inv, b = dot * inv * inv;
       for (int k = lane; k < L.K; k += 64) {
@@ -238,8 +233,7 @@ int sr_rows_pad(const float* a, int64_t lda, int32_t na, const float* b, int64_t
   if (rows < 0 || (group != 1 && group != 2) || width < 1 || ldd < width || na < 0 || nb < 0 || na > width || nb > width) return SR_EINVAL;
   if (rows == 0) return SR_OK;
   if (!dst || (a && lda < na) || (b && ldb < nb)) return SR_EINVAL;
-  hipLaunchKernelGGL(rows_pad_kernel, dim3(sr_stream_grid(rows * group * (int64_t)width, 256)), dim3(256), 0, (hipStream_t)stream, a, lda, na, b, ldb, nb,
-                     rows, group, dst, ldd, width);
+  sr_launch_stream(rows_pad_kernel, rows * group * (int64_t)width, 256, stream, a, lda, na, b, ldb, nb, rows, group, dst, ldd, width);
   return sr_launch_status();
 }
 int64_t sr_rows_frame_sum_workspace_floats(int64_t P, int32_t E, int32_t n) {
@@ -254,7 +248,7 @@ int sr_rows_frame_sum(const float* X, int64_t ldx, int64_t P, int32_t E, const i
   const int64_t rows_per_slice = sr_cdiv(P, slices);
   hipLaunchKernelGGL(rows_frame_sum_kernel, dim3((unsigned)sr_cdiv(E, kFsCols), slices), dim3(kFsCols * kFsGroups), sizeof(float) * kFsGroups * n * kFsCols,
                      (hipStream_t)stream, X, ldx, P, E, index, n, rows_per_slice, partial);
-  hipLaunchKernelGGL(rows_frame_sum_finish, dim3(sr_stream_grid((int64_t)n * E, 256)), dim3(256), 0, (hipStream_t)stream, partial, slices, (int64_t)n * E, out);
+  sr_launch_stream(rows_frame_sum_finish, (int64_t)n * E, 256, stream, partial, slices, (int64_t)n * E, out);
   return sr_launch_status();
 }
 int sr_stream_stamp(uint64_t* out, void* stream) {

@@ -18,6 +18,7 @@
 //     k are taken by lane 0 in ascending order.
 // No float atomics; every sum has an order fixed by the shapes: two calls give identical bits.
 #include "sr_common.h"
+#include "sr_wave.h"
 #include "rot_dual.h"
 
 #define SMPL_NJ 24
@@ -103,8 +104,7 @@ __global__ __launch_bounds__(SMPL_EW_BLOCK) void smpl_shape_bwd_partial_kernel(c
       const int e = q * SMPL_EW_BLOCK + t;
       acc = fmaf(e < n ? s[e] : 0.f, gv[q], acc);
     }
-#pragma unroll
-    for (int off = SR_WAVE / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, SR_WAVE);
+    acc = sr_wave_sum(acc);
     if ((t & (SR_WAVE - 1)) == 0) ws[i * (SMPL_EW_BLOCK / SR_WAVE) + t / SR_WAVE] = acc;
   }
   __syncthreads();

@@ -19,3 +19,9 @@ static inline int sr_stream_grid(int64_t work_items, int block) {
   if (g < 1) g = 1;
   return (int)g;
 }
+
+// One launch of a memory-bound kernel: sr_stream_grid(work_items, block) workgroups of `block` threads on `stream`, no dynamic LDS.
+template <typename... Params, typename... Args>
+static inline void sr_launch_stream(void (*kernel)(Params...), int64_t work_items, int block, void* stream, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3(sr_stream_grid(work_items, block)), dim3(block), 0, (hipStream_t)stream, args...);
+}

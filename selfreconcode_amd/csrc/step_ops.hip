@@ -13,17 +13,12 @@
 // Reference semantics (file:line cited at each entry point in include/selfrecon_hip.h):
 //   model/CameraMine.py:44-70,129-170,171-262   utils/utils.py:48-52,132-169   model/network.py:543-639,647-697,702-814
 #include "sr_common.h"
+#include "sr_wave.h"
 
 namespace {
 constexpr int kBlk = 256;
 constexpr int kRedMaxFrames = SR_STEP_MAX_FRAMES;     // per-frame (numerator, denominator) pairs kept in registers
 constexpr int kNV = 2 * kRedMaxFrames;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s, 64);
-  return v;
-}
 
 // Sum NV per-thread values over the workgroup (<= 1024 threads); every thread returns with the totals in v.
 template <int NV>
@@ -31,7 +26,7 @@ __device__ __forceinline__ void block_sum(float (&v)[NV], float* smem /* [NV * 1
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
-    v[i] = wave_sum(v[i]);
+    v[i] = sr_wave_sum(v[i]);
     if (lane == 0) smem[i * 16 + wave] = v[i];
   }
   __syncthreads();
@@ -586,7 +581,7 @@ int sr_cam_project_ndc_fwd(const float* ps, int64_t n, const sr_camera* cam, flo
   if (n < 0 || !cam || !cam->R || !cam->f || !cam->c) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!ps || !xy || !z) return SR_EINVAL;
-  hipLaunchKernelGGL(project_ndc_fwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, ps, n, *cam, xy, z);
+  sr_launch_stream(project_ndc_fwd_kernel, n, kBlk, stream, ps, n, *cam, xy, z);
   return sr_launch_status();
 }
 int sr_cam_project_ndc_bwd(const float* ps, int64_t n, const sr_camera* cam, const float* gxy, const float* gz, float* gps, float* partial,
@@ -606,7 +601,7 @@ int sr_cam_view_rays_fwd(const float* pixels, int64_t n, const sr_camera* cam, f
   if (n < 0 || !cam || !cam->R || !cam->f || !cam->c) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!pixels || !rays) return SR_EINVAL;
-  hipLaunchKernelGGL(view_rays_fwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, pixels, n, *cam, rays);
+  sr_launch_stream(view_rays_fwd_kernel, n, kBlk, stream, pixels, n, *cam, rays);
   return sr_launch_status();
 }
 int sr_cam_view_rays_bwd(const float* pixels, int64_t n, const sr_camera* cam, const float* grays, float* partial, float* gparams, void* stream) {
@@ -623,21 +618,21 @@ int sr_cardinal_rays_fwd(const float* J, const float* v, int64_t n, float* out, 
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!J || !v || !out || !ok) return SR_EINVAL;
-  hipLaunchKernelGGL(cardinal_rays_fwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, J, v, n, out, ok);
+  sr_launch_stream(cardinal_rays_fwd_kernel, n, kBlk, stream, J, v, n, out, ok);
   return sr_launch_status();
 }
 int sr_cardinal_rays_bwd(const float* J, const float* v, int64_t n, const float* gout, float* gJ, float* gv, void* stream) {
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!J || !v || !gout || (!gJ && !gv)) return SR_EINVAL;
-  hipLaunchKernelGGL(cardinal_rays_bwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, J, v, n, gout, gJ, gv);
+  sr_launch_stream(cardinal_rays_bwd_kernel, n, kBlk, stream, J, v, n, gout, gJ, gv);
   return sr_launch_status();
 }
 int sr_deformed_normals(const float* J, const float* onx, int64_t n, float* out, void* stream) {
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!J || !onx || !out) return SR_EINVAL;
-  hipLaunchKernelGGL(deformed_normals_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, J, onx, n, out);
+  sr_launch_stream(deformed_normals_kernel, n, kBlk, stream, J, onx, n, out);
   return sr_launch_status();
 }
 
@@ -652,7 +647,7 @@ int sr_color_loss_fwd(const sr_ray_pixels* px, const float* colors, const float*
 int sr_color_loss_bwd(const sr_ray_pixels* px, const float* colors, const float* gt, const float* saved, const float* gloss, float* gcolors,
                       void* stream) {
   if (bad_px(px) || px->P < 1 || !colors || !gt || !saved || !gloss || !gcolors) return SR_EINVAL;
-  hipLaunchKernelGGL(color_loss_bwd_kernel, dim3(sr_stream_grid(px->P, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, *px, colors, gt, saved, gloss, gcolors);
+  sr_launch_stream(color_loss_bwd_kernel, px->P, kBlk, stream, *px, colors, gt, saved, gloss, gcolors);
   return sr_launch_status();
 }
 int sr_normal_loss_fwd(const sr_ray_pixels* px, const float* nx_raw, const float* J, const float* gt_normals, const float* R, const float* rays,
@@ -667,8 +662,7 @@ int sr_normal_loss_fwd(const sr_ray_pixels* px, const float* nx_raw, const float
 int sr_normal_loss_bwd(const sr_ray_pixels* px, const float* nx_raw, const float* J, const float* gt_normals, const float* R, const float* rays,
                        int weighted, const float* saved, const float* gloss, float* gnx_raw, float* gJ, void* stream) {
   if (bad_px(px) || px->P < 1 || !nx_raw || !J || !gt_normals || !R || (weighted && !rays) || !saved || !gloss || !gnx_raw) return SR_EINVAL;
-  hipLaunchKernelGGL(normal_loss_bwd_kernel, dim3(sr_stream_grid(px->P, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, *px, nx_raw, J, gt_normals, R, rays,
-                     weighted, saved, gloss, gnx_raw, gJ);
+  sr_launch_stream(normal_loss_bwd_kernel, px->P, kBlk, stream, *px, nx_raw, J, gt_normals, R, rays, weighted, saved, gloss, gnx_raw, gJ);
   return sr_launch_status();
 }
 int sr_eikonal_loss_fwd(const float* g, int64_t n, float* partial, float* out, void* stream) {
@@ -681,7 +675,7 @@ int sr_eikonal_loss_fwd(const float* g, int64_t n, float* partial, float* out, v
 }
 int sr_eikonal_loss_bwd(const float* g, int64_t n, const float* gloss, float* gg, void* stream) {
   if (n < 1 || !g || !gloss || !gg) return SR_EINVAL;
-  hipLaunchKernelGGL(eikonal_bwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, g, n, gloss, gg);
+  sr_launch_stream(eikonal_bwd_kernel, n, kBlk, stream, g, n, gloss, gg);
   return sr_launch_status();
 }
 int sr_def_regu_loss_fwd(const float* S, int64_t n, float c, float* partial, float* out, void* stream) {
@@ -694,14 +688,14 @@ int sr_def_regu_loss_fwd(const float* S, int64_t n, float c, float* partial, flo
 }
 int sr_def_regu_loss_bwd(const float* U, const float* S, const float* V, int64_t n, float c, const float* gloss, float* gJ, void* stream) {
   if (n < 1 || !U || !S || !V || !gloss || !gJ || !(c > 0.f)) return SR_EINVAL;
-  hipLaunchKernelGGL(def_regu_bwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, U, S, V, n, c, gloss, gJ);
+  sr_launch_stream(def_regu_bwd_kernel, n, kBlk, stream, U, S, V, n, c, gloss, gJ);
   return sr_launch_status();
 }
 int sr_svd3x3_bwd(const float* U, const float* V, const float* gS, int64_t n, float* gJ, void* stream) {
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!U || !V || !gS || !gJ) return SR_EINVAL;
-  hipLaunchKernelGGL(svd_bwd_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, U, V, gS, n, gJ);
+  sr_launch_stream(svd_bwd_kernel, n, kBlk, stream, U, V, gS, n, gJ);
   return sr_launch_status();
 }
 int sr_mask_iou_loss_fwd(const float* masks, const float* gt, int N, int64_t hw, float* partial, float* out, void* stream) {
@@ -714,8 +708,7 @@ int sr_mask_iou_loss_fwd(const float* masks, const float* gt, int N, int64_t hw,
 }
 int sr_mask_iou_loss_bwd(const float* masks, const float* gt, int N, int64_t hw, const float* saved, const float* gloss, float* gmasks, void* stream) {
   if (N < 1 || N > SR_STEP_MAX_FRAMES || hw < 1 || !masks || !gt || !saved || !gloss || !gmasks) return SR_EINVAL;
-  hipLaunchKernelGGL(mask_iou_bwd_kernel, dim3(sr_stream_grid((int64_t)N * hw, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, masks, gt, N, hw, saved, gloss,
-                     gmasks);
+  sr_launch_stream(mask_iou_bwd_kernel, (int64_t)N * hw, kBlk, stream, masks, gt, N, hw, saved, gloss, gmasks);
   return sr_launch_status();
 }
 int sr_implicit_solve(const float* grad_f, const float* J, const float* v, const float* grad_l, int64_t n, float* cot_f, float* rhs_tail, float* temp,
@@ -723,8 +716,7 @@ int sr_implicit_solve(const float* grad_f, const float* J, const float* v, const
   if (n < 0) return SR_EINVAL;
   if (n == 0) return SR_OK;
   if (!grad_f || !J || !v || !grad_l || !cot_f || !rhs_tail || !temp || !ok) return SR_EINVAL;
-  hipLaunchKernelGGL(implicit_solve_kernel, dim3(sr_stream_grid(n, kBlk)), dim3(kBlk), 0, (hipStream_t)stream, grad_f, J, v, grad_l, n, cot_f, rhs_tail,
-                     temp, ok);
+  sr_launch_stream(implicit_solve_kernel, n, kBlk, stream, grad_f, J, v, grad_l, n, cot_f, rhs_tail, temp, ok);
   return sr_launch_status();
 }
 }

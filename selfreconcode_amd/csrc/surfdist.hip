@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void mesh_sample(const float4* __restrict__ tr
 extern "C" int sr_surfdist_face_cells(const float* tri, int64_t F, const float* lo, float cell, int32_t nx, int32_t ny, int32_t nz, int64_t* count,
                                       void* stream) {
   if (!tri || !lo || !count || F <= 0 || F >= INT32_MAX || misaligned(tri) || bad_grid(cell, nx, ny, nz)) return SR_EINVAL;
-  hipLaunchKernelGGL(face_cells, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)tri, F, lo, cell, nx, ny, nz, count);
+  sr_launch_stream(face_cells, F, 256, stream, (const float4*)tri, F, lo, cell, nx, ny, nz, count);
   return sr_launch_status();
 }
 
@@ -153,8 +153,7 @@ extern "C" int sr_surfdist_emit_pairs(const float* tri, int64_t F, const float* 
                                       const int64_t* offset, int64_t pairs, int64_t* key, int32_t* pair_face, void* stream) {
   if (!tri || !lo || !offset || !key || !pair_face || F <= 0 || F >= INT32_MAX || pairs < F || misaligned(tri) || bad_grid(cell, nx, ny, nz))
     return SR_EINVAL;
-  hipLaunchKernelGGL(emit_pairs, dim3(sr_stream_grid(F, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)tri, F, lo, cell, nx, ny, nz, offset,
-                     pairs, key, pair_face);
+  sr_launch_stream(emit_pairs, F, 256, stream, (const float4*)tri, F, lo, cell, nx, ny, nz, offset, pairs, key, pair_face);
   return sr_launch_status();
 }
 
@@ -164,16 +163,14 @@ extern "C" int sr_surfdist_query(const float* points, int64_t P, const float* tr
   if (!points || !tri || !lo || !cell_start || !cell_faces || !dist || !face || !closest || P <= 0 || F <= 0 || F >= INT32_MAX || pairs < 0 ||
       misaligned(tri) || bad_grid(cell, nx, ny, nz))
     return SR_EINVAL;
-  hipLaunchKernelGGL(grid_query, dim3(sr_stream_grid(P, 256)), dim3(256), 0, (hipStream_t)stream, points, P, (const float4*)tri, F, lo, cell, nx, ny,
-                     nz, cell_start, cell_faces, pairs, dist, face, closest);
+  sr_launch_stream(grid_query, P, 256, stream, points, P, (const float4*)tri, F, lo, cell, nx, ny, nz, cell_start, cell_faces, pairs, dist, face, closest);
   return sr_launch_status();
 }
 
 extern "C" int sr_surfdist_brute(const float* points, int64_t P, const float* tri, int64_t F, float* dist, int64_t* face, float* closest,
                                  void* stream) {
   if (!points || !tri || !dist || !face || !closest || P <= 0 || F <= 0 || F >= INT32_MAX || misaligned(tri)) return SR_EINVAL;
-  hipLaunchKernelGGL(brute_query, dim3(sr_stream_grid(P, 256)), dim3(256), 0, (hipStream_t)stream, points, P, (const float4*)tri, F, dist, face,
-                     closest);
+  sr_launch_stream(brute_query, P, 256, stream, points, P, (const float4*)tri, F, dist, face, closest);
   return sr_launch_status();
 }
 
@@ -182,7 +179,6 @@ extern "C" int sr_mesh_sample(const float* tri, const double* cum_area, int64_t 
   if (!tri || !cum_area || !points || !face || !normals || F <= 0 || F >= INT32_MAX || n <= 0 || n > ((int64_t)1 << 40) || misaligned(tri))
     return SR_EINVAL;
   const uint64_t seed_term = (uint64_t)seed * 0x9E3779B97F4A7C15ull;
-  hipLaunchKernelGGL(mesh_sample, dim3(sr_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, (const float4*)tri, cum_area, F, n, seed_term, points,
-                     face, normals);
+  sr_launch_stream(mesh_sample, n, 256, stream, (const float4*)tri, cum_area, F, n, seed_term, points, face, normals);
   return sr_launch_status();
 }

@@ -9,6 +9,7 @@
 //
 // The shader is a bandwidth-bound gather like phong_shade: a thread per pixel, 16-byte taps, no LDS tiling, no MFMA, no atomics.
 #include "sr_common.h"
+#include "mesh_device.h"
 
 namespace {
 
@@ -66,10 +67,6 @@ __global__ __launch_bounds__(256) void mips_next(const float4* __restrict__ src,
   }
 }
 
-__device__ __forceinline__ bool tri_ok(int64_t a, int64_t b, int64_t c, int64_t n) {
-  return a >= 0 && b >= 0 && c >= 0 && a < n && b < n && c < n;
-}
-
 // thread per (image, face)
 __global__ __launch_bounds__(256) void face_lod(const float* __restrict__ xy, const int64_t* __restrict__ faces, const float* __restrict__ vt,
                                                  const int64_t* __restrict__ ft, int64_t N, int64_t V, int64_t F, int64_t Vt, float R, float bias,
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void face_lod(const float* __restrict__ xy, co
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
     const int64_t ta = ft[f * 3], tb = ft[f * 3 + 1], tc = ft[f * 3 + 2];
     float out = top;
-    if (tri_ok(a, b, c, V) && tri_ok(ta, tb, tc, Vt)) {
+    if (sr_face_ok(a, b, c, V) && sr_face_ok(ta, tb, tc, Vt)) {
       const float2* P = (const float2*)xy + n * V;
       const float2* T = (const float2*)vt;
       const float2 p0 = P[a], p1 = P[b], p2 = P[c], t0 = T[ta], t1 = T[tb], t2 = T[tc];
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(256) void shade_textured(const int64_t* __restrict_
     if (p >= 0 && p < N * F) {
       const int64_t f = p % F;
       const int64_t ta = ft[f * 3], tb = ft[f * 3 + 1], tc = ft[f * 3 + 2];
-      if (tri_ok(ta, tb, tc, Vt)) {
+      if (sr_face_ok(ta, tb, tc, Vt)) {
         const float b0 = bary[i * 3], b1 = bary[i * 3 + 1], b2 = bary[i * 3 + 2];
         const float2* T = (const float2*)vt;
         const float2 t0 = T[ta], t1 = T[tb], t2 = T[tc];
@@ -161,12 +158,12 @@ extern "C" int sr_texture_mips(const void* texture, int32_t is_u8, const uint8_t
   float4* out = (float4*)mips;
   const int64_t total = (int64_t)R * R;
   if (is_u8)
-    hipLaunchKernelGGL(mips_first<uint8_t>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, (const uint8_t*)texture, valid, total, out);
+    sr_launch_stream(mips_first<uint8_t>, total, 256, st, (const uint8_t*)texture, valid, total, out);
   else
-    hipLaunchKernelGGL(mips_first<float>, dim3(sr_stream_grid(total, 256)), dim3(256), 0, st, (const float*)texture, valid, total, out);
+    sr_launch_stream(mips_first<float>, total, 256, st, (const float*)texture, valid, total, out);
   for (int l = 1; l < lay.L; ++l)
-    hipLaunchKernelGGL(mips_next, dim3(sr_stream_grid((int64_t)lay.side[l] * lay.side[l], 256)), dim3(256), 0, st, (const float4*)(out + lay.off[l - 1]),
-                       lay.side[l - 1], lay.side[l], out + lay.off[l]);
+    sr_launch_stream(mips_next, (int64_t)lay.side[l] * lay.side[l], 256, st, (const float4*)(out + lay.off[l - 1]), lay.side[l - 1], lay.side[l],
+                     out + lay.off[l]);
   return sr_launch_status();
 }
 
@@ -175,8 +172,7 @@ extern "C" int sr_texture_face_lod(const float* xy_pix, const int64_t* faces, co
   if (!xy_pix || !faces || !vt || !ft || !lod || N <= 0 || V <= 0 || F <= 0 || Vt <= 0 || R <= 0 || R > 32768 || L != mip_layout(R).L ||
       ((uintptr_t)xy_pix & 7) || ((uintptr_t)vt & 7))
     return SR_EINVAL;
-  hipLaunchKernelGGL(face_lod, dim3(sr_stream_grid(N * F, 256)), dim3(256), 0, (hipStream_t)stream, xy_pix, faces, vt, ft, N, V, F, Vt, (float)R, bias,
-                     (float)(L - 1), lod);
+  sr_launch_stream(face_lod, N * F, 256, stream, xy_pix, faces, vt, ft, N, V, F, Vt, (float)R, bias, (float)(L - 1), lod);
   return sr_launch_status();
 }
 
@@ -189,7 +185,7 @@ extern "C" int sr_shade_textured(const int64_t* pix_to_face, const float* bary, 
   ShadeColours col;
   for (int k = 0; k < 3; ++k) { col.bg[k] = host_background[k]; col.hole[k] = host_hole[k]; }
   const int64_t HW = (int64_t)H * W;
-  hipLaunchKernelGGL(shade_textured, dim3(sr_stream_grid(N * HW, 256)), dim3(256), 0, (hipStream_t)stream, pix_to_face, bary, N, F, HW, ft, vt, Vt,
-                     (const float4*)mips, mip_layout(R), lod, col, bg_image, (float4*)rgba, coverage);
+  sr_launch_stream(shade_textured, N * HW, 256, stream, pix_to_face, bary, N, F, HW, ft, vt, Vt, (const float4*)mips, mip_layout(R), lod, col, bg_image,
+                   (float4*)rgba, coverage);
   return sr_launch_status();
 }

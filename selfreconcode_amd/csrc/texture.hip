@@ -17,6 +17,7 @@
 // All of it is gather / stream work bound by HBM and L2: no LDS tiling, no MFMA.  No float atomics, and "empty" is the view id -1, never
 // a NaN.
 #include "sr_common.h"
+#include "mesh_device.h"
 #include "uv_device.h"
 
 namespace {
@@ -68,10 +69,6 @@ __global__ __launch_bounds__(256) void uv_finish(const float* __restrict__ vt, c
   }
 }
 
-__device__ __forceinline__ bool mesh_face_ok(int64_t a, int64_t b, int64_t c, int64_t V) {
-  return a >= 0 && b >= 0 && c >= 0 && a < V && b < V && c < V;
-}
-
 // visible[p] = 1 for every packed face index p = view * F + face that owns a pixel (plain byte stores of the same value: benign)
 __global__ __launch_bounds__(256) void vis_mark(const int64_t* __restrict__ pix_to_face, int64_t npix, int64_t NF, uint8_t* __restrict__ visible) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(256) void vis_finish(const int64_t* __restrict__ fa
     if (!visible[i]) continue;
     const int64_t n = i / F, f = i - n * F;
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    bool ok = mesh_face_ok(a, b, c, V);
+    bool ok = sr_face_ok(a, b, c, V);
     if (ok) {
       const float* P = xy + n * V * 2;
       const uint8_t* M = mask + n * (int64_t)H * W;
@@ -140,7 +137,7 @@ __global__ __launch_bounds__(256) void tex_accumulate(int64_t T, const int32_t* 
     const int64_t f = tface[t];
     if (f < 0 || f >= F) continue;
     const int64_t a = faces[f * 3], b = faces[f * 3 + 1], c = faces[f * 3 + 2];
-    if (!mesh_face_ok(a, b, c, V)) continue;
+    if (!sr_face_ok(a, b, c, V)) continue;
     const float b0 = tbary[t * 3], b1 = tbary[t * 3 + 1], b2 = tbary[t * 3 + 2];
     int32_t n = count[t], mi = min_idx[t];
     float mc = min_cos[t];
@@ -336,8 +333,8 @@ extern "C" int sr_uv_rasterize(const float* vt, const int64_t* ft, int64_t Vt, i
   hipStream_t st = (hipStream_t)stream;
   const int64_t texels = (int64_t)R * R;
   if (hipMemsetAsync(face, 0x7f, (size_t)texels * 4, st) != hipSuccess) return SR_ELAUNCH;
-  hipLaunchKernelGGL(uv_claim, dim3(sr_stream_grid(F * SR_WAVE, 256)), dim3(256), 0, st, vt, ft, Vt, F, R, face);
-  hipLaunchKernelGGL(uv_finish, dim3(sr_stream_grid(texels, 256)), dim3(256), 0, st, vt, ft, Vt, F, R, face, bary);
+  sr_launch_stream(uv_claim, F * SR_WAVE, 256, st, vt, ft, Vt, F, R, face);
+  sr_launch_stream(uv_finish, texels, 256, st, vt, ft, Vt, F, R, face, bary);
   return sr_launch_status();
 }
 
@@ -347,14 +344,14 @@ extern "C" int sr_face_visibility(const int64_t* pix_to_face, const int64_t* fac
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(visible, 0, (size_t)(N * F), st) != hipSuccess) return SR_ELAUNCH;
   const int64_t npix = N * (int64_t)H * W;
-  hipLaunchKernelGGL(vis_mark, dim3(sr_stream_grid(npix, 256)), dim3(256), 0, st, pix_to_face, npix, N * F, visible);
-  hipLaunchKernelGGL(vis_finish, dim3(sr_stream_grid(N * F, 256)), dim3(256), 0, st, faces, N, V, F, xy_pix, mask, H, W, visible);
+  sr_launch_stream(vis_mark, npix, 256, st, pix_to_face, npix, N * F, visible);
+  sr_launch_stream(vis_finish, N * F, 256, st, faces, N, V, F, xy_pix, mask, H, W, visible);
   return sr_launch_status();
 }
 
 extern "C" int sr_view_alpha(const float* verts, const float* normals, const float* cam_pos, int64_t N, int64_t V, float* alpha, void* stream) {
   if (!verts || !normals || !cam_pos || !alpha || N <= 0 || V <= 0) return SR_EINVAL;
-  hipLaunchKernelGGL(view_alpha, dim3(sr_stream_grid(N * V, 256)), dim3(256), 0, (hipStream_t)stream, verts, normals, cam_pos, N, V, alpha);
+  sr_launch_stream(view_alpha, N * V, 256, stream, verts, normals, cam_pos, N, V, alpha);
   return sr_launch_status();
 }
 
@@ -365,8 +362,8 @@ extern "C" int sr_texture_accumulate(int64_t T, const int32_t* tface, const floa
   if (!tface || !tbary || !faces || !visible || !alpha || !xy_pix || !images || !fids || !slot_cos || !slot_rgb || !slot_view || !count || !min_cos ||
       !min_idx || T <= 0 || F <= 0 || V <= 0 || N <= 0 || H <= 0 || W <= 0 || agg_num <= 0 || !(cosv0 >= 0.f))
     return SR_EINVAL;
-  hipLaunchKernelGGL(tex_accumulate, dim3(sr_stream_grid(T, 256)), dim3(256), 0, (hipStream_t)stream, T, tface, tbary, faces, F, V, N, visible, alpha,
-                     xy_pix, images, H, W, fids, agg_num, cosv0, slot_cos, slot_rgb, slot_view, count, min_cos, min_idx);
+  sr_launch_stream(tex_accumulate, T, 256, stream, T, tface, tbary, faces, F, V, N, visible, alpha, xy_pix, images, H, W, fids, agg_num, cosv0, slot_cos,
+                   slot_rgb, slot_view, count, min_cos, min_idx);
   return sr_launch_status();
 }
 
@@ -375,8 +372,7 @@ extern "C" int sr_texture_resolve(int64_t T, const int32_t* texel, int32_t agg_n
                                   float* tex_median, void* stream) {
   if (!texel || !slot_cos || !slot_rgb || !slot_view || !count || !mask_final || !view_id || !tex_median || T <= 0 || agg_num <= 0 || check_num <= 0)
     return SR_EINVAL;
-  hipLaunchKernelGGL(tex_resolve, dim3(sr_stream_grid(T, 256)), dim3(256), 0, (hipStream_t)stream, T, texel, agg_num, cosv0, check_num, slot_cos,
-                     slot_rgb, slot_view, count, mask_final, view_id, tex_median);
+  sr_launch_stream(tex_resolve, T, 256, stream, T, texel, agg_num, cosv0, check_num, slot_cos, slot_rgb, slot_view, count, mask_final, view_id, tex_median);
   return sr_launch_status();
 }
 
@@ -405,11 +401,11 @@ extern "C" int sr_texture_fill(const float* tex_median, const uint8_t* mask_fina
   const int g = sr_stream_grid(texels, 256);
   hipLaunchKernelGGL(dilate_axis, dim3(g), dim3(256), 0, st, tex_mask, R, dilate, 1, rows);
   hipLaunchKernelGGL(dilate_axis, dim3(g), dim3(256), 0, st, (const uint8_t*)rows, R, dilate, 0, region);
-  hipLaunchKernelGGL(push_first, dim3(sr_stream_grid((int64_t)n[0] * n[0], 256)), dim3(256), 0, st, tex_median, mask_final, R, n[0], level[0]);
+  sr_launch_stream(push_first, (int64_t)n[0] * n[0], 256, st, tex_median, mask_final, R, n[0], level[0]);
   for (int l = 1; l < L; ++l)
-    hipLaunchKernelGGL(push_level, dim3(sr_stream_grid((int64_t)n[l] * n[l], 256)), dim3(256), 0, st, (const float4*)level[l - 1], n[l - 1], n[l], level[l]);
+    sr_launch_stream(push_level, (int64_t)n[l] * n[l], 256, st, (const float4*)level[l - 1], n[l - 1], n[l], level[l]);
   for (int l = L - 2; l >= 0; --l)
-    hipLaunchKernelGGL(pull_level, dim3(sr_stream_grid((int64_t)n[l] * n[l], 256)), dim3(256), 0, st, (const float4*)level[l + 1], n[l + 1], level[l], n[l]);
+    sr_launch_stream(pull_level, (int64_t)n[l] * n[l], 256, st, (const float4*)level[l + 1], n[l + 1], level[l], n[l]);
   hipLaunchKernelGGL(pull_final, dim3(g), dim3(256), 0, st, tex_median, mask_final, (const uint8_t*)region, (const float4*)level[0], n[0], R, texture);
   return sr_launch_status();
 }

@@ -57,7 +57,7 @@ extern "C" int sr_newton_update(const sr_newton_args* a, void* stream) {
   if (a->M == 0) return SR_OK;
   if (!a->sdf4 || !a->y || !a->rays || !a->cam || !a->converged || !a->p) return SR_EINVAL;
   if (a->group == 4 && a->p_out && (!a->off4 || !a->jlbs)) return SR_EINVAL;
-  hipLaunchKernelGGL(newton_kernel, dim3(sr_stream_grid(a->M, 256)), dim3(256), 0, (hipStream_t)stream, *a);
+  sr_launch_stream(newton_kernel, a->M, 256, stream, *a);
   return sr_launch_status();
 }
 
@@ -114,13 +114,13 @@ extern "C" int sr_newton_prepare(const sr_newton2_args* a, void* stream) {
   if (a->M == 0) return SR_OK;
   if (!a->sdf || !a->y || !a->rays || !a->cam || !a->converged) return SR_EINVAL;
   if (a->t_out && (!a->jlbs || !a->s_out || a->ld_t < 3)) return SR_EINVAL;
-  hipLaunchKernelGGL(newton_prepare_kernel, dim3(sr_stream_grid(a->M, 256)), dim3(256), 0, (hipStream_t)stream, *a);
+  sr_launch_stream(newton_prepare_kernel, a->M, 256, stream, *a);
   return sr_launch_status();
 }
 extern "C" int sr_newton_apply(const sr_newton2_args* a, void* stream) {
   if (!a || a->M < 0) return SR_EINVAL;
   if (a->M == 0) return SR_OK;
   if (!a->sdf || !a->converged || !a->t_out || !a->s_out || !a->grad_f || !a->grad_off || !a->p || !a->p_out) return SR_EINVAL;
-  hipLaunchKernelGGL(newton_apply_kernel, dim3(sr_stream_grid(a->M, 256)), dim3(256), 0, (hipStream_t)stream, *a);
+  sr_launch_stream(newton_apply_kernel, a->M, 256, stream, *a);
   return sr_launch_status();
 }

@@ -50,17 +50,22 @@ def _clustered(verts, faces, lo, n, cell):
     return vmap, cells, remapped, keep
 
 
-def _placement(placement, reg):
-    """The checked (placement, reg): ValueError for a placement that is not one of PLACEMENTS or a reg that is not finite and positive."""
-    if placement not in PLACEMENTS:
-        raise ValueError(f"placement must be one of {PLACEMENTS}, got {placement!r}")
+def _reg(reg):
+    """The checked reg as a float: ValueError for one that is not finite and positive."""
     try:
         reg = float(reg)
     except (TypeError, ValueError):
         raise ValueError(f"reg must be a finite positive number, got {reg!r}") from None
     if not (np.isfinite(reg) and reg > 0):
         raise ValueError(f"reg must be a finite positive number, got {reg}")
-    return placement, reg
+    return reg
+
+
+def _placement(placement, reg):
+    """The checked (placement, reg): ValueError for a placement that is not one of PLACEMENTS or a reg that _reg refuses."""
+    if placement not in PLACEMENTS:
+        raise ValueError(f"placement must be one of {PLACEMENTS}, got {placement!r}")
+    return placement, _reg(reg)
 
 
 def simplify_mesh(verts, faces, cell, placement="mean", reg=1e-3, report=None):
@@ -183,7 +188,7 @@ def simplify_collapse(verts, faces, target_faces, reg=1e-3, flip_cos=0.2, max_ro
     points against the normal of the triangle their three survivors made at their original positions, or has vanished
     (mesh_prep_ops.face_flips with every face as its own source).  `flipped` measures how far survivors have travelled, not folds: a
     vertex that has moved past a neighbour's old place counts, on a flat grid too; every collapse has passed the flip test."""
-    _, reg = _placement("mean", reg)
+    reg = _reg(reg)
     flip_cos = float(flip_cos)
     if not -1. <= flip_cos < 1.:
         raise ValueError(f"flip_cos must lie in [-1, 1), got {flip_cos}")

@@ -165,6 +165,20 @@ def face_classes(verts, faces):
     return cls
 
 
+def _jump_to_fixed_point(entry, P, Q, changed, passes, limit, stuck):
+    """Pointer doubling of the forest P with the double-buffered kernel `entry` (sr_chart_jump, sr_collapse_map_jump) until a pass changes
+    nothing: one launch and one flag read per pass.  -> (the fixed point, the other buffer, `passes` plus the passes made here).
+    RuntimeError(stuck) when the count has gone past `limit` and the last pass still changed something."""
+    while True:
+        _lib.launch(entry, P, P, P.shape[0], Q, changed)
+        passes += 1
+        P, Q = Q, P
+        if not int(changed):
+            return P, Q, passes
+        if passes > limit:
+            raise RuntimeError(stuck.format(passes=passes))
+
+
 def chart_components(faces, V, cls):
     """(label [F] int32, rounds): label = the lowest face index of the connected component of faces of equal class that share an edge
     (all faces on a non-manifold edge are connected).  Min-label hooking of roots, then pointer doubling until every tree is a star,
@@ -183,15 +197,7 @@ def chart_components(faces, V, cls):
         rounds += 1
         if not int(changed):
             return P, rounds
-        P, Q = Q, P
-        while True:
-            _lib.launch("sr_chart_jump", faces, P, F, Q, changed)
-            rounds += 1
-            P, Q = Q, P
-            if not int(changed):
-                break
-            if rounds > MAX_ROUNDS:
-                raise RuntimeError(f"chart_components: no fixed point after {rounds} passes")
+        P, Q, rounds = _jump_to_fixed_point("sr_chart_jump", Q, P, changed, rounds, MAX_ROUNDS, "chart_components: no fixed point after {passes} passes")
 
 
 def chart_boxes(verts, faces, cls, chart, C):
@@ -346,12 +352,7 @@ def collapse_roots(target):
     """root [V] int64 of the forest target [V] (target[v] = v for a root) by pointer doubling (sr_collapse_map_jump; one flag read per
     pass, at most 64 passes: a chain of V links needs log2 V)."""
     _lib.require_gpu(target)
-    P = _lib.i64c(target).clone(); N = torch.empty_like(P)
-    V = P.shape[0]
+    P = _lib.i64c(target).clone()
     changed = torch.zeros((1,), dtype=torch.int32, device=P.device)
-    for _ in range(64):
-        _lib.launch("sr_collapse_map_jump", P, P, V, N, changed)
-        P, N = N, P
-        if not int(changed):
-            return P
-    raise RuntimeError("collapse_roots: target is not a forest")
+    # (limit 63: a 64th pass that still changes something raises)
+    return _jump_to_fixed_point("sr_collapse_map_jump", P, torch.empty_like(P), changed, 0, 63, "collapse_roots: target is not a forest")[0]
