@@ -913,7 +913,13 @@ int sr_mesh_sample(const float* tri, const double* cum_area, int64_t F, int64_t 
  *     t <- o + (1 + sigma) exp(omega) (t - o) + rho tau; done <- max |xi| < tol.  Row `it` of history [iters, SR_ICP_HISTORY]: kept
  *     pairs, the rms of their d (before this update), max |xi|, rank, sqrt(|M|_F^2 / 3), done.  With the done flag set on entry the
  *     state is left alone and the row repeats row it - 1 with done = 1.
- * SR_EINVAL: a NULL pointer, S <= 0, tri not 16-byte aligned, a bad grid, rho <= 0, max_dist < 0 or NaN, a wrong block count,
+ *   sr_icp_score (one 256-lane workgroup per candidate): row c of table [N,12] float64 is M (3 x 3, row major)
+ *     then t of a candidate transform.  For every sample p of points [S,3] float32: q as in sr_icp_accumulate; a q that is not finite
+ *     is skipped; d = sr_surfdist_query's distance of q; e = fminf(d, trunc[c]) (trunc [N] float32, +Inf: no truncation).  score
+ *     [N,2] float64: row c = (the sum of (double)e (double)e, the number of samples that took part).  A lane adds its samples i = lane,
+ *     lane + 256, ... in that order, a wave adds its lanes by the xor butterfly (distances 32 down to 1), the workgroup adds its
+ *     waves as ((r0 + r1) + r2) + r3: no atomics, and two launches give identical bits.
+ * SR_EINVAL: a NULL pointer, S <= 0, N <= 0, tri not 16-byte aligned, a bad grid, rho <= 0, max_dist < 0 or NaN, a wrong block count,
  * iters <= 0, `it` outside [0, iters). */
 #define SR_ICP_MAX_BLOCKS 1024
 #define SR_ICP_COLS 40
@@ -925,6 +931,9 @@ int sr_icp_accumulate(const float* points, int64_t S, const float* tri, int64_t 
                       double rho, float max_dist, int32_t measure, double* partial, int32_t blocks, void* stream);
 int sr_icp_solve(const double* partial, int32_t blocks, double ox, double oy, double oz, double rho, int32_t scale, double tol, int32_t it,
                  int32_t iters, double* state, double* history, void* stream);
+int sr_icp_score(const float* points, int64_t S, const double* table, int32_t N, const float* tri, int64_t F, const float* lo, float cell,
+                 int32_t nx, int32_t ny, int32_t nz, const int64_t* cell_start, const int32_t* cell_faces, int64_t pairs, const float* trunc,
+                 double* score, void* stream);
 
 #ifdef __cplusplus
 }

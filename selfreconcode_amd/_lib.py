@@ -311,6 +311,7 @@ SIGNATURES = {
     "sr_icp_accumulate": [_vp, _i64, _vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp, _i64, _vp] + [ctypes.c_double] * 4
                          + [ctypes.c_float, ctypes.c_int32, _vp, ctypes.c_int32, _vp],
     "sr_icp_solve": [_vp, ctypes.c_int32] + [ctypes.c_double] * 4 + [ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
+    "sr_icp_score": [_vp, _i64, _vp, ctypes.c_int32, _vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp, _i64, _vp, _vp, _vp],
 }
 _RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64,
             "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64, "sr_smpl_regress_workspace_floats": _i64,

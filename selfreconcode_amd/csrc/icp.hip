@@ -10,14 +10,19 @@
 //  * sr_icp_solve: one wave.  Lane k sums column k of `partial` over the blocks in ascending order; lane 0 solves the scaled normal
 //    equations by Cholesky (a pivot below 2^-20 drops its unknown), composes the update with the exact rotation exp(omega) and
 //    writes the state, a row of `history` and the `done` flag.
+//  * sr_icp_score: one 256-lane workgroup per candidate transform of a table, lanes striding over the samples.  The
+//    same q and the same grid search; min(d, trunc)^2 and a count stay in registers, are reduced over the wave by sr_wave_sum and over
+//    the four waves through the LDS, and leave as score [c] = (sum, count).  No atomics.
 //
 // Once `done` is set both kernels return without touching the state (sr_icp_solve repeats the last history row), so the number of
 // launches is fixed before the loop starts.  Everything in double is compiled without contraction and in a stated order, so a sum of
 // one sample is the restatement's to the bit and two runs give identical bits.  Every loop runs over an integer range fixed before it
 // starts.
+#include "sr_wave.h"
 #include "surfdist_device.h"
 
 #define ICP_SUMS 38                                    /* 36 products, the kept count, the sum of d^2 */
+#define ICP_TABLE 12                                   /* doubles per candidate transform: M (row major), t */
 #define ICP_UNKNOWNS 7                                 /* omega (3), tau (3), sigma */
 #define ICP_PIVOT_MIN 9.5367431640625e-7               /* 2^-20, on the system scaled to a unit diagonal */
 #define ICP_COLUMN_MIN 1.4210854715202004e-14          /* 2^-46 = (2^-23)^2: a column whose mean square is below it is dropped */
@@ -213,6 +218,47 @@ __global__ __launch_bounds__(SR_WAVE) void icp_solve(const double* __restrict__ 
   row[5] = done ? 1. : 0.;
 }
 
+// One workgroup per candidate c: T_c(p) = M p + t from row c of table [N, ICP_TABLE].  The samples come sorted by their cell keys in
+// their own mesh's grid; a similarity keeps neighbours neighbours, so a wave walks adjacent cells of the target under every candidate.
+// A candidate far from the target walks many rings: exactness is kept.
+__global__ __launch_bounds__(256) void icp_score(const float* __restrict__ points, int64_t S, const double* __restrict__ table,
+                                                  const float4* __restrict__ tri, int64_t F, const float* __restrict__ lo, float cell, int32_t nx,
+                                                  int32_t ny, int32_t nz, const int64_t* __restrict__ cell_start,
+                                                  const int32_t* __restrict__ cell_faces, int64_t pairs, const float* __restrict__ trunc,
+                                                  double* __restrict__ score) {
+#pragma clang fp contract(off)
+  const Grid g{tri, F, lo, cell, nx, ny, nz, cell_start, cell_faces, pairs};
+  const double* __restrict__ row = table + (int64_t)blockIdx.x * ICP_TABLE;
+  double M[9], t[3];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) M[k] = row[k];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) t[k] = row[9 + k];
+  const float cap = trunc[blockIdx.x];
+  double sum = 0., count = 0.;
+  for (int64_t i = threadIdx.x; i < S; i += 256) {
+    const double px = (double)points[i * 3], py = (double)points[i * 3 + 1], pz = (double)points[i * 3 + 2];
+    const float q[3] = {(float)(((M[0] * px + M[1] * py) + M[2] * pz) + t[0]), (float)(((M[3] * px + M[4] * py) + M[5] * pz) + t[1]),
+                        (float)(((M[6] * px + M[7] * py) + M[8] * pz) + t[2])};
+    if (!(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]))) continue;
+    const Best b = grid_search(q, g);
+    if (b.f == INT32_MAX) continue;
+    const float e = fminf(sqrtf(b.d2), cap);
+    sum += (double)e * (double)e;
+    count += 1.;
+  }
+  __shared__ double red[4][2];
+  const int lane = threadIdx.x & (SR_WAVE - 1), wave = threadIdx.x / SR_WAVE;
+  sum = sr_wave_sum(sum);
+  count = sr_wave_sum(count);
+  if (lane == 0) { red[wave][0] = sum; red[wave][1] = count; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const int k = threadIdx.x;
+    score[(int64_t)blockIdx.x * 2 + k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+  }
+}
+
 int32_t icp_blocks(int64_t S) {
   const int64_t b = sr_cdiv(S, 256);
   return (int32_t)(b < SR_ICP_MAX_BLOCKS ? b : SR_ICP_MAX_BLOCKS);
@@ -237,5 +283,16 @@ extern "C" int sr_icp_solve(const double* partial, int32_t blocks, double ox, do
       bad_frame(ox, oy, oz, rho) || !(tol >= 0.))
     return SR_EINVAL;
   hipLaunchKernelGGL(icp_solve, dim3(1), dim3(SR_WAVE), 0, (hipStream_t)stream, partial, blocks, ox, oy, oz, rho, scale, tol, it, state, history);
+  return sr_launch_status();
+}
+
+extern "C" int sr_icp_score(const float* points, int64_t S, const double* table, int32_t N, const float* tri, int64_t F, const float* lo, float cell,
+                            int32_t nx, int32_t ny, int32_t nz, const int64_t* cell_start, const int32_t* cell_faces, int64_t pairs,
+                            const float* trunc, double* score, void* stream) {
+  if (!points || !table || !tri || !lo || !cell_start || !cell_faces || !trunc || !score || S <= 0 || N <= 0 || F <= 0 || F >= INT32_MAX ||
+      pairs < 0 || misaligned(tri) || bad_grid(cell, nx, ny, nz))
+    return SR_EINVAL;
+  hipLaunchKernelGGL(icp_score, dim3(N), dim3(256), 0, (hipStream_t)stream, points, S, table, (const float4*)tri, F, lo, cell, nx, ny, nz,
+                     cell_start, cell_faces, pairs, trunc, score);
   return sr_launch_status();
 }

@@ -4,13 +4,17 @@ triangle meshes (csrc/surfdist.hip, surfdist_ops.py).
     python -m selfreconcode_amd.evaluate --gpu-ids 0 --pred A.ply --gt B.ply [--samples N] [--seed S] [--tau t ...] [--out FILE.json]
     python -m selfreconcode_amd.evaluate --gpu-ids 0 --rec-root R --gt-root G [--frames N] [--samples N] [--seed S] [--tau t ...]
     ... [--align {none,rigid,similarity}] [--align-samples N] [--align-iters K] [--align-max-dist d] [--align-shared]
+    ... [--align-init {centroid,none,axes,search}] [--align-candidates N] [--align-top K]
 
 Mesh-pair mode prints the metrics of two files.  Folder mode compares every posed mesh `R/meshs/<fid>.npy` of an `infer` run (faces
 from `R/tmp.ply`) with `G/<fid>.ply` or `G/<fid>.obj` and writes `R/geometry_errors.txt` and `R/geometry_errors.json`.  By default no
 alignment and no scaling is applied: both meshes are taken in the coordinates they are given.  `--align rigid` / `--align similarity`
 first takes the predicted mesh onto the ground truth by point-to-plane ICP (align.py; local: it starts from matched
 centroids), per frame, or with `--align-shared` once on the first compared frame for all of them (a constant camera-frame offset).
-Out of scope: signed distance, global registration, quads.
+`--align-init axes` / `--align-init search` put a rotation search in front of the ICP for a scan in another
+orientation -- another up axis, facing the other way --: the 24 rotations of the cube, or those and `--align-candidates` more, of
+which the `--align-top` best are refined; the frame's line is then followed by one that says what the search chose.
+Out of scope: signed distance, partial overlap, reflections, quads.
 """
 import argparse
 import json
@@ -61,8 +65,9 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     results come to the host in one copy (the two index builds read their sizes on the way).
 
     `align` = None: no alignment or scaling.  "rigid" / "similarity": pred is first taken onto gt by align.icp_align (keywords in
-    `align_opts`: samples, seed, iters, max_dist, tol, init), its vertices are replaced by Alignment.apply of them, and `alignment`
-    in the result carries matrix, scale, iterations, converged, rank, rms_before and rms_after.  An Alignment is applied as it is."""
+    `align_opts`: samples, seed, iters, max_dist, tol, init, candidates, search_samples, top, refine_iters), its vertices are
+    replaced by Alignment.apply of them, and `alignment` in the result carries matrix, scale, iterations, converged, rank, rms_before
+    and rms_after, and `search` (Alignment.search) when `init` asked for a rotation search.  An Alignment is applied as it is."""
     _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
     samples = int(samples)
     if samples <= 0:
@@ -138,6 +143,13 @@ def write_geometry_errors(path, fids, chamfer, p2s):
             ff.write("\n")
 
 
+def search_line(search):
+    """What folder mode prints under a frame whose alignment started from a rotation search."""
+    k = search["top"].index(search["winner"])
+    return "      search %s: candidate %d of %d, %.1f deg from the centroid start, J %.3g -> %.3g" % (
+        search["kind"], search["winner"], search["candidates"], search["angle_deg"], search["score"][k], search["refined"][k])
+
+
 def _frame_ids(folder):
     fids = [os.path.splitext(f)[0] for f in os.listdir(folder) if f.endswith(".npy")]
     return sorted(fids, key=lambda s: (0, int(s), s) if s.lstrip("-").isdigit() else (1, 0, s))
@@ -167,6 +179,9 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
                 align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
             per[fid] = surface_metrics(pred, gt, samples, seed, taus, align, align_opts)
         out("%4s: chamfer %.6f p2s %.6f" % (fid, per[fid]["chamfer"], per[fid]["p2s"]))
+        found = per[fid].get("alignment", {}).get("search")
+        if found is not None:
+            out(search_line(found))
     out("%d frames compared, %d skipped (no ground-truth file)" % (len(per), len(skipped)))
     if not per:
         raise ValueError(f"evaluate: no frame of {rec_root}/meshs has a ground-truth file in {gt_root}")
@@ -201,6 +216,11 @@ def build_parser():
     parser.add_argument("--align-samples", default=100_000, type=int, metavar="N", help="surface samples of the predicted mesh the alignment uses")
     parser.add_argument("--align-iters", default=30, type=int, metavar="K", help="ICP iterations launched (they stop updating once converged)")
     parser.add_argument("--align-max-dist", default=None, type=float, metavar="d", help="only pairs within this distance take part (default: all)")
+    parser.add_argument("--align-init", default="centroid", choices=al.INITS,
+                        help="the start of the ICP: matched centroids, nothing, or a rotation search in front of it -- the 24 rotations of the "
+                             "cube (axes), or those and --align-candidates more (search) -- for a scan in any orientation")
+    parser.add_argument("--align-candidates", default=4096, type=int, metavar="N", help="rotations --align-init search tries beyond the 24")
+    parser.add_argument("--align-top", default=8, type=int, metavar="K", help="candidates of the search that are refined by short ICP runs")
     parser.add_argument("--align-shared", action="store_true",
                         help="folder mode: estimate the alignment on the first compared frame and use it for every frame (default: per frame)")
     return parser
@@ -225,6 +245,10 @@ def parse_args(argv=None):
         parser.error("--align-samples and --align-iters must be positive")
     if args.align_max_dist is not None and not args.align_max_dist >= 0:
         parser.error("--align-max-dist must not be negative")
+    if args.align_candidates <= 0 or args.align_top <= 0:
+        parser.error("--align-candidates and --align-top must be positive")
+    if args.align == "none" and args.align_init != "centroid":
+        parser.error("--align-init needs --align rigid or similarity")
     if args.align_shared and (args.align == "none" or not all(folder)):
         parser.error("--align-shared needs folder mode and --align rigid or similarity")
     return args
@@ -234,7 +258,8 @@ def _align_args(args):
     """(align, align_opts) of surface_metrics from the parsed arguments."""
     if args.align == "none":
         return None, None
-    return args.align, {"samples": args.align_samples, "seed": args.seed, "iters": args.align_iters, "max_dist": args.align_max_dist}
+    return args.align, {"samples": args.align_samples, "seed": args.seed, "iters": args.align_iters, "max_dist": args.align_max_dist,
+                        "init": args.align_init, "candidates": args.align_candidates, "top": args.align_top}
 
 
 def main(argv=None, out=print):
