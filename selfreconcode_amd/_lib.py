@@ -8,141 +8,25 @@ import ctypes
 import os
 import torch
 
+from . import _abi
 from .build import LIB
 
-_i64, _vp, _int = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
-
-
-class SrTensor5(ctypes.Structure):
-    _fields_ = [("size", _i64 * 5), ("stride", _i64 * 5)]
-
-
-class SrGemmArgs(ctypes.Structure):
-    _fields_ = [("A", _vp), ("lda", _i64), ("B", _vp), ("ldb", _i64), ("C", _vp), ("ldc", _i64),
-                ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("bias", _vp),
-                ("group", ctypes.c_int32), ("act", ctypes.c_int32), ("mode", ctypes.c_int32), ("out_scale", ctypes.c_float),
-                ("aux", _vp), ("ldaux", _i64), ("naux_fwd", ctypes.c_int32), ("nact_bwd", ctypes.c_int32),
-                ("aux_scale", ctypes.c_float)]
-
-
-class SrGemmTnArgs(ctypes.Structure):
-    _fields_ = [("Z", _vp), ("ldz", _i64), ("A", _vp), ("lda", _i64), ("dW", _vp), ("lddw", _i64), ("partial", _vp),
-                ("R", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("splits", ctypes.c_int32),
-                ("accumulate", ctypes.c_int32), ("db", _vp), ("db_partial", _vp), ("group", ctypes.c_int32)]
-
-
-SR_TN_GROUP_MAX = 12
-
-
-class SrGemmTnGroupArgs(ctypes.Structure):
-    _fields_ = [("n", ctypes.c_int32), ("p", SrGemmTnArgs * SR_TN_GROUP_MAX)]
-
-
-class SrLbsArgs(ctypes.Structure):
-    _fields_ = [("p", _vp), ("tp", _vp), ("P", _i64), ("A", _vp), ("trans", _vp), ("nframes", ctypes.c_int32),
-                ("batch_inds", _vp), ("points_per_frame", _i64), ("vol", _vp), ("D", ctypes.c_int32), ("H", ctypes.c_int32),
-                ("W", ctypes.c_int32), ("bmin", ctypes.c_float * 3), ("bmax", ctypes.c_float * 3), ("y", _vp), ("jac", _vp)]
-
-
-class SrNewtonArgs(ctypes.Structure):
-    _fields_ = [("M", _i64), ("group", ctypes.c_int32), ("sdf4", _vp), ("ld_sdf", _i64), ("off4", _vp), ("ld_off", _i64),
-                ("y", _vp), ("jlbs", _vp), ("rays", _vp), ("cam", _vp), ("p", _vp), ("p_out", _vp), ("converged", _vp),
-                ("dthreshold", ctypes.c_float), ("athreshold", ctypes.c_float), ("w1", ctypes.c_float), ("w2", ctypes.c_float)]
-
-
-class SrNewton2Args(ctypes.Structure):
-    _fields_ = [("M", _i64), ("sdf", _vp), ("ld_sdf", _i64), ("y", _vp), ("jlbs", _vp), ("rays", _vp), ("cam", _vp), ("converged", _vp),
-                ("t_out", _vp), ("ld_t", _i64), ("s_out", _vp), ("grad_f", _vp), ("grad_off", _vp), ("p", _vp), ("p_out", _vp),
-                ("dthreshold", ctypes.c_float), ("athreshold", ctypes.c_float), ("w1", ctypes.c_float), ("w2", ctypes.c_float)]
-
-
-SR_CHAIN_MAX_LAYERS = 10
-
-
-class SrChainArgs(ctypes.Structure):
-    _fields_ = [("nlayers", ctypes.c_int32), ("nprob", ctypes.c_int32 * SR_CHAIN_MAX_LAYERS), ("g", (SrGemmArgs * 2) * SR_CHAIN_MAX_LAYERS),
-                ("m_dev", _vp), ("m_mul", ctypes.c_int32), ("m_cap", ctypes.c_int32)]
-
-
-class SrRefineArgs(ctypes.Structure):
-    _f, _i32 = ctypes.c_float, ctypes.c_int32
-    _fields_ = [("P", _i32), ("times", _i32), ("p0", _vp), ("rays", _vp), ("batch_inds", _vp), ("cam", _vp),
-                ("L_sdf", _i32), ("w_sdf", _vp), ("L_def", _i32), ("w_def", _vp), ("conds", _vp), ("ld_conds", _i64), ("E", _i32),
-                ("A", _vp), ("trans", _vp), ("nframes", _i32), ("vol", _vp), ("D", _i32), ("H", _i32), ("W", _i32),
-                ("bmin", _f * 3), ("bmax", _f * 3), ("dthreshold", _f), ("athreshold", _f), ("w1", _f), ("w2", _f),
-                ("live", _vp), ("x", _vp * 2), ("v", _vp * 2), ("frame", _vp * 2), ("orig", _vp * 2), ("unit", _vp),
-                ("a0", _vp), ("ld_a0", _i64), ("a0d", _vp), ("ld_a0d", _i64), ("sdf_out", _vp), ("ld_sdf", _i64), ("def_out", _vp), ("ld_def", _i64),
-                ("conv", _vp), ("t", _vp), ("s", _vp), ("a0bar", _vp), ("ld_a0bar", _i64), ("skipbar", _vp), ("ld_skipbar", _i64), ("n_skip", _i32),
-                ("a0dbar", _vp), ("ld_a0dbar", _i64), ("p_out", _vp), ("conv_out", _vp)]
-
-
-SR_PACK_MAX_LAYERS = 16
-
-
-class SrPackLayer(ctypes.Structure):
-    _fields_ = [("v", _vp), ("g", _vp), ("W", _vp), ("WT", _vp), ("norms", _vp), ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("ldw", _i64), ("ldwt", _i64)]
-
-
-class SrPackTable(ctypes.Structure):
-    _fields_ = [("nlayers", ctypes.c_int32), ("layer", SrPackLayer * SR_PACK_MAX_LAYERS)]
-
-
-class SrUnpackLayer(ctypes.Structure):
-    _fields_ = [("dW", _vp), ("lddw", _i64), ("v", _vp), ("g", _vp), ("norms", _vp), ("gv", _vp), ("gg", _vp), ("db", _vp), ("gb", _vp),
-                ("N", ctypes.c_int32), ("K", ctypes.c_int32), ("accumulate", ctypes.c_int32), ("pad_", ctypes.c_int32)]
-
-
-SR_ADAM_MAX_TENSORS = 64
-
-
-class SrAdamTensor(ctypes.Structure):
-    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("numel", _i64), ("lr", ctypes.c_float), ("bias1", ctypes.c_float),
-                ("inv_sqrt_bias2", ctypes.c_float), ("pad_", ctypes.c_float)]
-
-
-class SrAdamTable(ctypes.Structure):
-    _fields_ = [("ntensors", ctypes.c_int32), ("beta1", ctypes.c_float), ("beta2", ctypes.c_float), ("eps", ctypes.c_float),
-                ("one_minus_beta1", ctypes.c_float), ("one_minus_beta2", ctypes.c_float), ("pad_", ctypes.c_int32 * 2),
-                ("tensor", SrAdamTensor * SR_ADAM_MAX_TENSORS)]
-
-
-class SrUnpackTable(ctypes.Structure):
-    _fields_ = [("nlayers", ctypes.c_int32), ("layer", SrUnpackLayer * SR_PACK_MAX_LAYERS)]
-
-
-SR_STEP_MAX_FRAMES = 8
-SR_STEP_LOSS_SLOTS = 1 + 2 * SR_STEP_MAX_FRAMES
-
-
-class SrCamera(ctypes.Structure):
-    _fields_ = [("R", _vp), ("T", _vp), ("f", _vp), ("c", _vp), ("W", ctypes.c_float), ("H", ctypes.c_float),
-                ("one_minus_inv_w", ctypes.c_float), ("one_minus_inv_h", ctypes.c_float)]
-
-
-class SrRayPixels(ctypes.Structure):
-    _fields_ = [("b", _vp), ("r", _vp), ("c", _vp), ("P", _i64), ("N", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
-
-
-SR_FRAMES_MAX_BATCH = 16
-
-
-class SrFrameIds(ctypes.Structure):
-    _fields_ = [("id", ctypes.c_int32 * SR_FRAMES_MAX_BATCH)]
-
-
-SR_LOG_MAX_SLOTS = 32
-SR_LOG_EMPTY, SR_LOG_F32, SR_LOG_I64, SR_LOG_IMM = 0, 1, 2, 3
-
-
-class SrLogSlots(ctypes.Structure):
-    _fields_ = [("src", _vp * SR_LOG_MAX_SLOTS), ("imm", ctypes.c_float * SR_LOG_MAX_SLOTS), ("kind", ctypes.c_uint8 * SR_LOG_MAX_SLOTS)]
+# include/selfrecon_hip.h is the one statement of the boundary: its #defines, argument structs and prototypes are read from it here,
+# once per process, and nothing of them is restated in Python (tests/test_abi.py checks the reading against gcc).
+try:
+    _DEFINES, _STRUCTS, _PROTOTYPES = _abi.load()
+except (OSError, _abi.AbiError) as e:
+    raise ImportError(f"{_abi.HEADER}: {e}") from e
+globals().update(_DEFINES)                                        # SR_TN_GROUP_MAX = 12, ...: every integer #define
+globals().update({c.__name__: c for c in _STRUCTS.values()})      # SrTensor5 (sr_tensor5), SrGemmArgs (sr_gemm_args), ...
 
 
 class SrError(RuntimeError):
     pass
 
 
-_CODES = {-1: "SR_EINVAL (bad argument)", -2: "SR_ELAUNCH (kernel launch failed)", -3: "SR_ENOSPC (workspace too small)"}
+_CODES = {_DEFINES["SR_EINVAL"]: "SR_EINVAL (bad argument)", _DEFINES["SR_ELAUNCH"]: "SR_ELAUNCH (kernel launch failed)",
+          _DEFINES["SR_ENOSPC"]: "SR_ENOSPC (workspace too small)"}
 
 if "SELFRECON_HIP_LIB" in os.environ:
     LIB = os.environ["SELFRECON_HIP_LIB"]         # tuning hook: point at an experimental build of the same ABI
@@ -158,164 +42,8 @@ if not os.path.isfile(LIB):
                       "There is no CPU fallback for the HIP hot path.")
 _lib = ctypes.CDLL(LIB)
 
-# name -> argtypes; mirrors include/selfrecon_hip.h one to one (tests/test_abi.py checks the set)
-_T5 = SrTensor5
-SIGNATURES = {
-    "sr_minv3x3_fwd_f32": [_vp, _vp, _vp, _i64, _vp],
-    "sr_minv3x3_fwd_f64": [_vp, _vp, _vp, _i64, _vp],
-    "sr_minv3x3_bwd_f32": [_vp, _vp, _vp, _i64, _vp],
-    "sr_minv3x3_bwd_f64": [_vp, _vp, _vp, _i64, _vp],
-    "sr_gridsample3d_fwd_f16": [_vp, _T5, _vp, _T5, _vp, _T5, _vp],
-    "sr_gridsample3d_bwd_f16": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp],
-    "sr_gridsample3d_dbwd_f16": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp, _vp],
-    "sr_gridsample3d_fwd_f32": [_vp, _T5, _vp, _T5, _vp, _T5, _vp],
-    "sr_gridsample3d_fwd_f64": [_vp, _T5, _vp, _T5, _vp, _T5, _vp],
-    "sr_gridsample3d_bwd_f32": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp],
-    "sr_gridsample3d_bwd_f64": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp],
-    "sr_gridsample3d_dbwd_f32": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp, _vp],
-    "sr_gridsample3d_dbwd_f64": [_vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _T5, _vp, _vp, _vp],
-    "sr_mlp_gemm_nt": [_vp, _vp],
-    "sr_mlp_gemm_nt_tile": [ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_mlp_chain": [_vp, _vp],
-    "sr_refine_init": [_vp, _vp],
-    "sr_refine_embed": [_vp, ctypes.c_int32, _vp],
-    "sr_refine_mid": [_vp, ctypes.c_int32, ctypes.c_int32, _vp],
-    "sr_refine_finish": [_vp, ctypes.c_int32, _vp],
-    "sr_mlp_gemm_tn_workspace_floats": [ctypes.c_int32, ctypes.c_int32, _i64, _vp],
-    "sr_mlp_gemm_tn": [_vp, _vp],
-    "sr_mlp_gemm_tn_group": [_vp, _vp],
-    "sr_lbs_chain_fwd": [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_lbs_chain_bwd": [_vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_lbs_fwd": [_vp, _vp],
-    "sr_lbs_bwd_workspace_floats": [_i64, ctypes.c_int32],
-    "sr_lbs_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_lbs_jac_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_newton_update": [_vp, _vp],
-    "sr_newton_prepare": [_vp, _vp],
-    "sr_newton_apply": [_vp, _vp],
-    "sr_mc_workspace_bytes": [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32],
-    "sr_mc_count": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp],
-    "sr_mc_emit": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp] + [ctypes.c_float] * 6 + [_vp, _vp, _vp],
-    "sr_rows_pad": [_vp, _i64, ctypes.c_int32, _vp, _i64, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _i64, ctypes.c_int32, _vp],
-    "sr_rows_frame_sum_workspace_floats": [_i64, ctypes.c_int32, ctypes.c_int32],
-    "sr_rows_frame_sum": [_vp, _i64, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_adam_step": [_vp, _vp],
-    "sr_stream_stamp": [_vp, _vp],
-    "sr_stream_flag_set": [_vp, ctypes.c_uint32, _vp],
-    "sr_stream_flag_wait": [_vp, ctypes.c_uint32, _vp, ctypes.c_int32, _vp],
-    "sr_pack_weights": [_vp, _vp],
-    "sr_unpack_grads": [_vp, _vp],
-    "sr_svd3x3": [_vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_step_reduce_blocks": [_i64],
-    "sr_step_param_blocks": [_i64],
-    "sr_cam_project_ndc_fwd": [_vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_cam_project_ndc_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_cam_view_rays_fwd": [_vp, _i64, _vp, _vp, _vp],
-    "sr_cam_view_rays_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp],
-    "sr_cardinal_rays_fwd": [_vp, _vp, _i64, _vp, _vp, _vp],
-    "sr_cardinal_rays_bwd": [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_deformed_normals": [_vp, _vp, _i64, _vp, _vp],
-    "sr_color_loss_fwd": [_vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_color_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_normal_loss_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_normal_loss_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp],
-    "sr_eikonal_loss_fwd": [_vp, _i64, _vp, _vp, _vp],
-    "sr_eikonal_loss_bwd": [_vp, _i64, _vp, _vp, _vp],
-    "sr_def_regu_loss_fwd": [_vp, _i64, ctypes.c_float, _vp, _vp, _vp],
-    "sr_def_regu_loss_bwd": [_vp, _vp, _vp, _i64, ctypes.c_float, _vp, _vp, _vp],
-    "sr_svd3x3_bwd": [_vp, _vp, _vp, _i64, _vp, _vp],
-    "sr_mask_iou_loss_fwd": [_vp, _vp, ctypes.c_int32, _i64, _vp, _vp, _vp],
-    "sr_mask_iou_loss_bwd": [_vp, _vp, ctypes.c_int32, _i64, _vp, _vp, _vp, _vp],
-    "sr_implicit_solve": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp],
-    "sr_points_silhouette_workspace_bytes": [_i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float],
-    "sr_points_silhouette_fwd": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_points_silhouette_bwd": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp, _vp],
-    "sr_interp2x3d_fwd_f32": [_vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp],
-    "sr_interp2x3d_fwd_f64": [_vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_float, _vp, _vp, _vp],
-    "sr_interp2x3d_bwd_f32": [_vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_interp2x3d_bwd_f64": [_vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_seg3d_candidates": [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_rasterize_meshes": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp],
-    "sr_vertex_adjacency": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "sr_vertex_normals": [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "sr_shade_phong": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_uv_rasterize": [_vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_face_visibility": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_view_alpha": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
-    "sr_texture_accumulate": [_i64, _vp, _vp, _vp, _i64, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, ctypes.c_int32,
-                              ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_texture_resolve": [_i64, _vp, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_texture_fill_workspace_bytes": [ctypes.c_int32],
-    "sr_texture_fill": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_texture_mips": [_vp, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp],
-    "sr_texture_face_lod": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_int32, ctypes.c_float, ctypes.c_int32, _vp, _vp],
-    "sr_shade_textured": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp,
-                          _vp, _vp, _vp, _vp],
-    "sr_meshprep_bounds": [_vp, _i64, _vp, _vp],
-    "sr_meshprep_cell_keys": [_vp, _i64, _vp, ctypes.c_float, _i64, _i64, _i64, _vp, _vp],
-    "sr_meshprep_cell_mean": [_vp, _i64, _vp, _vp, _i64, _vp, _vp],
-    "sr_meshprep_face_keys": [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "sr_meshprep_face_first": [_vp, _vp, _vp, _i64, _vp, _vp],
-    "sr_meshprep_cell_faces": [_vp, _i64, _vp, _i64, _i64, _vp, _vp],
-    "sr_meshprep_cell_quadric": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, ctypes.c_float, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp],
-    "sr_meshprep_face_flips": [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
-    "sr_collapse_vertex_quadrics": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_collapse_edge_keys": [_vp, _i64, _i64, _vp, _vp],
-    "sr_collapse_edge_heads": [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_collapse_candidates": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp],
-    "sr_collapse_min1": [_vp, _vp, _i64, _i64, _vp, _vp],
-    "sr_collapse_min2": [_vp, _i64, _i64, _vp, _vp, _vp],
-    "sr_collapse_select": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "sr_collapse_apply_vertices": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
-    "sr_collapse_apply_faces": [_vp, _i64, _vp, _i64, _vp, _vp, _vp],
-    "sr_collapse_map_jump": [_vp, _i64, _vp, _vp, _vp],
-    "sr_chart_classify": [_vp, _i64, _vp, _i64, _vp, _vp],
-    "sr_chart_edge_keys": [_vp, _i64, _i64, _vp, _vp, _vp],
-    "sr_chart_hook": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp],
-    "sr_chart_jump": [_vp, _i64, _vp, _vp, _vp],
-    "sr_chart_bbox": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_chart_uv": [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_uv_overlap_count": [_vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_double, _vp, _vp, _vp],
-    "sr_lbsw_knn_blend": [_vp, _vp, _i64] + [ctypes.c_int32] * 5 + [_vp, _vp, ctypes.c_int32, _vp, _vp],
-    "sr_lbsw_smooth": [_vp, _vp] + [ctypes.c_int32] * 4 + [_vp],
-    "sr_smpl_shape": [_vp, _vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _vp],
-    "sr_smpl_regress_workspace_floats": [ctypes.c_int32, _i64, ctypes.c_int32],
-    "sr_smpl_regress": [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_smpl_pose": [_vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
-    "sr_smpl_skin": [_vp, _i64, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp],
-    "sr_smpl_regress_bwd": [_vp, _vp, ctypes.c_int32, _i64, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_smpl_shape_bwd_workspace_floats": [ctypes.c_int32, ctypes.c_int32, _i64],
-    "sr_smpl_shape_bwd": [_vp, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp, _vp, _vp],
-    "sr_smpl_skin_bwd_workspace_floats": [ctypes.c_int32, _i64],
-    "sr_smpl_skin_bwd": [_vp, _i64, _vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _i64, _vp, _vp, _vp, _vp, _vp],
-    "sr_smpl_pose_bwd": [_vp, _vp, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "sr_keypoint_energy": [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp],
-    "sr_edt": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_contour_flags": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "sr_silhouette_energy": [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, ctypes.c_float] + [ctypes.c_int32] * 5 + [_vp] * 10,
-    "sr_meshreg_workspace_bytes": [_i64, _i64],
-    "sr_meshreg_fwd": [_vp, _i64, _vp, _vp, _i64, _vp, _i64, ctypes.c_int32, ctypes.c_float] + [_vp] * 6,
-    "sr_meshreg_bwd": [_i64, _vp, _vp, _i64, _vp, _vp, _i64] + [_vp] * 8,
-    "sr_frames_fetch": [_vp, _vp, _vp, _i64, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, ctypes.c_int32, _vp, _vp, _vp, _vp],
-    "sr_log_row": [_vp, ctypes.c_int32, _vp, ctypes.c_int32, ctypes.c_int32, _i64, _vp],
-    "sr_pe_embed_bwd": [_vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp],
-    "sr_pe_embed": [_vp, _i64, ctypes.c_int32, _vp, _vp, _i64, ctypes.c_int32, _vp, ctypes.c_int32, _vp, _i64, _vp],
-    "sr_jpeg_transform": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_jpeg_entropy": [_vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
-    "sr_jpeg_gather": [_vp, _vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _i64, _vp, _vp],
-    "sr_surfdist_face_cells": [_vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp],
-    "sr_surfdist_emit_pairs": [_vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _i64, _vp, _vp, _vp],
-    "sr_surfdist_query": [_vp, _i64, _vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_surfdist_brute": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp],
-    "sr_mesh_sample": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp],
-    "sr_icp_accumulate": [_vp, _i64, _vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp, _i64, _vp] + [ctypes.c_double] * 4
-                         + [ctypes.c_float, ctypes.c_int32, _vp, ctypes.c_int32, _vp],
-    "sr_icp_solve": [_vp, ctypes.c_int32] + [ctypes.c_double] * 4 + [ctypes.c_int32, ctypes.c_double, ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp],
-    "sr_icp_score": [_vp, _i64, _vp, ctypes.c_int32, _vp, _i64, _vp, ctypes.c_float] + [ctypes.c_int32] * 3 + [_vp, _vp, _i64, _vp, _vp, _vp],
-}
-_RESTYPE = {"sr_rows_frame_sum_workspace_floats": _i64, "sr_lbs_bwd_workspace_floats": _i64, "sr_mlp_gemm_tn_workspace_floats": _i64, "sr_mc_workspace_bytes": _i64, "sr_points_silhouette_workspace_bytes": _i64,
-            "sr_texture_fill_workspace_bytes": _i64, "sr_meshreg_workspace_bytes": _i64, "sr_smpl_regress_workspace_floats": _i64,
-            "sr_smpl_shape_bwd_workspace_floats": _i64, "sr_smpl_skin_bwd_workspace_floats": _i64}
+_INFO = ("sr_abi_version", "sr_build_arch", "sr_build_digest")   # (called through the functions below, not through call())
+SIGNATURES = {name: argtypes for name, (_, argtypes) in _PROTOTYPES.items() if name not in _INFO}     # name -> argtypes
 
 _fn = {}
 for _name, _args in SIGNATURES.items():
@@ -324,11 +52,10 @@ for _name, _args in SIGNATURES.items():
     except AttributeError as e:  # pragma: no cover
         raise ImportError(f"{LIB} does not export {_name}; rebuild it") from e
     _f.argtypes = _args
-    _f.restype = _RESTYPE.get(_name, _int)
+    _f.restype = _PROTOTYPES[_name][0]
     _fn[_name] = _f
-_lib.sr_abi_version.restype = _int
-_lib.sr_build_arch.restype = ctypes.c_char_p
-_lib.sr_build_digest.restype = ctypes.c_char_p
+for _name in _INFO:
+    getattr(_lib, _name).restype, getattr(_lib, _name).argtypes = _PROTOTYPES[_name]
 
 
 def abi_version():

@@ -19,7 +19,7 @@ from . import _lib
 from . import mesh_prep_ops as mp
 from . import surfdist_ops as sd
 
-MAX_BLOCKS, COLS, HISTORY, STATE, DONE = 1024, 40, 6, 16, 12          # SR_ICP_* of the header
+MAX_BLOCKS, COLS, HISTORY, STATE, DONE = _lib.SR_ICP_MAX_BLOCKS, _lib.SR_ICP_COLS, _lib.SR_ICP_HISTORY, _lib.SR_ICP_STATE, _lib.SR_ICP_DONE
 TABLE = 12                                                            # doubles per candidate transform of sr_icp_score: M (row major), t
 INIT_BOUND = 1e-6                                                     # |M M^T / s^2 - I| of an `init` matrix (a float32 matrix passes)
 INITS = ("centroid", "none", "axes", "search")

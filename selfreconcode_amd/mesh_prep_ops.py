@@ -7,7 +7,7 @@ from . import _lib
 from .ops import _faces
 
 MAX_ROUNDS = 4096          # passes of the component search before it is declared stuck (a 40 000-face strip needs about 20)
-QUADRIC_CLAMPED, QUADRIC_NO_PLANES = 1, 2          # bits of cell_quadric_optima's flags (SR_QUADRIC_* of the header)
+QUADRIC_CLAMPED, QUADRIC_NO_PLANES = _lib.SR_QUADRIC_CLAMPED, _lib.SR_QUADRIC_NO_PLANES          # bits of cell_quadric_optima's flags
 
 
 def _verts2(verts):

@@ -27,8 +27,8 @@ import torch
 
 from . import _lib
 
-ACT_NONE, ACT_SOFTPLUS100, ACT_RELU = 0, 1, 2
-EPI_FWD, EPI_BWD = 0, 1
+ACT_NONE, ACT_SOFTPLUS100, ACT_RELU = _lib.SR_ACT_NONE, _lib.SR_ACT_SOFTPLUS100, _lib.SR_ACT_RELU
+EPI_FWD, EPI_BWD = _lib.SR_EPI_FWD, _lib.SR_EPI_BWD
 
 # Weight-gradient GEMMs on a stream of their own.  In a reverse sweep dW_l = Zbar_l^T X_{l-1} and the backward-data GEMM
 # Zbar_{l-1} = (Zbar_l W_l) . act' depend on the same Zbar_l and on nothing of each other; on one stream they alternate, every launch

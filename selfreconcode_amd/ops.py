@@ -174,7 +174,7 @@ def shade_phong(verts, normals, faces, frags, cam_pos, light_loc=PHONG_LIGHT, am
 
 
 # ------------------------------------------------------------------ skinning-weight field of a body mesh (csrc/lbsw.hip)
-LBSW_MAX_K = 32
+LBSW_MAX_K = _lib.SR_LBSW_MAX_K
 
 
 def lbsw_knn_blend(verts, vert_ws, bmin, bmax, resolutions, k, align_corners=False):
@@ -213,7 +213,7 @@ def lbsw_smooth(field, times, consume=False):
 
 
 # ------------------------------------------------------------------ SMPL body model, forward only (csrc/smpl.hip)
-SMPL_BATCH_TILE = 8              # SR_SMPL_BATCH_TILE: batch items per workgroup of the skin kernel
+SMPL_BATCH_TILE = _lib.SR_SMPL_BATCH_TILE      # batch items per workgroup of the skin kernel
 SMPL_NJ, SMPL_NPOSE = 24, 207
 
 
@@ -370,7 +370,7 @@ def keypoint_energy(joints, trans, kp, joint_weights, camera, sigma):
 
 
 # ------------------------------------------------------------------ silhouette term of smpl_fit.py (csrc/silfit.hip)
-EDT_EMPTY = 1 << 30                     # every entry of the squared distance field of a frame without a mask pixel
+EDT_EMPTY = _lib.SR_EDT_EMPTY           # (1 << 30) every entry of the squared distance field of a frame without a mask pixel
 EDT_MAX_DIM = 8192
 SIL_MAX_SAMPLES = 65536
 
@@ -439,7 +439,7 @@ def silhouette_energy(points, d2, samples, counts, camera, sigma, margin):
 
 
 # ------------------------------------------------------------------ mesh regularisers of the template step (csrc/mesh_reg.hip)
-MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = 1, 2, 4
+MESHREG_LAP, MESHREG_EDGE, MESHREG_NORMAL = _lib.SR_MESHREG_LAP, _lib.SR_MESHREG_EDGE, _lib.SR_MESHREG_NORMAL
 
 
 def _meshreg_i32(t, numel, name):
