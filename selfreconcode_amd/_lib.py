@@ -58,6 +58,30 @@ for _name in _INFO:
     getattr(_lib, _name).restype, getattr(_lib, _name).argtypes = _PROTOTYPES[_name]
 
 
+def bind_header(path):
+    """(defines, structs) of an extension header next to the kernels (csrc/*_abi.h, read by _abi.parse like the main header): its
+    prototypes get their argtypes / restype on the loaded library and join `_fn`, so call, launch, raw and workspace serve them.
+    SIGNATURES and this module's SR_* attributes stay the main header's.  ImportError for a header that does not parse, a name the
+    main header already declares, or a symbol the library lacks -- there is no fallback."""
+    try:
+        with open(path) as fh:
+            defines, structs, prototypes = _abi.parse(fh.read())
+    except (OSError, _abi.AbiError) as e:
+        raise ImportError(f"{path}: {e}") from e
+    fresh = {}
+    for name, (restype, argtypes) in prototypes.items():
+        if name in _PROTOTYPES:
+            raise ImportError(f"{path}: {name} is declared by {_abi.HEADER}")
+        try:
+            f = getattr(_lib, name)
+        except AttributeError as e:
+            raise ImportError(f"{LIB} does not export {name}; rebuild it") from e
+        f.argtypes, f.restype = argtypes, restype
+        fresh[name] = f
+    _fn.update(fresh)
+    return defines, structs
+
+
 def abi_version():
     return _lib.sr_abi_version()
 

@@ -5,6 +5,7 @@ triangle meshes (csrc/surfdist.hip, surfdist_ops.py).
     python -m selfreconcode_amd.evaluate --gpu-ids 0 --rec-root R --gt-root G [--frames N] [--samples N] [--seed S] [--tau t ...]
     ... [--align {none,rigid,similarity}] [--align-samples N] [--align-iters K] [--align-max-dist d] [--align-shared]
     ... [--align-init {centroid,none,axes,search}] [--align-candidates N] [--align-top K]
+    ... [--signed] [--beta b] [--error-range d] [--error-mesh FILE.ply | --error-meshes]
 
 Mesh-pair mode prints the metrics of two files.  Folder mode compares every posed mesh `R/meshs/<fid>.npy` of an `infer` run (faces
 from `R/tmp.ply`) with `G/<fid>.ply` or `G/<fid>.obj` and writes `R/geometry_errors.txt` and `R/geometry_errors.json`.  By default no
@@ -14,7 +15,12 @@ centroids), per frame, or with `--align-shared` once on the first compared frame
 `--align-init axes` / `--align-init search` put a rotation search in front of the ICP for a scan in another
 orientation -- another up axis, facing the other way --: the 24 rotations of the cube, or those and `--align-candidates` more, of
 which the `--align-top` best are refined; the frame's line is then followed by one that says what the search chose.
-Out of scope: signed distance, partial overlap, reflections, quads.
+`--signed` adds on which side the surfaces lie of each other (the generalized winding number, winding_ops.py): the mean
+signed distance and the share of samples inside, per direction, and both signed volumes.  `--error-mesh FILE.ply` (mesh-pair mode) /
+`--error-meshes` (folder mode: `R/geometry_errors/<fid>.ply`) write the predicted mesh, aligned if an alignment was asked for, coloured
+by each vertex's distance to the ground truth: white to red up to `--error-range` (default: the 95th percentile of |d| over the mesh,
+which is printed), and with `--signed` white to blue for the vertices inside the ground truth.
+Out of scope: partial overlap, reflections, quads, rendering the error map to an image.
 """
 import argparse
 import json
@@ -26,14 +32,31 @@ import torch
 from . import _lib
 from . import align as al
 from . import surfdist_ops as sd
-from .mesh_io import read_mesh, read_ply
+from . import winding_ops as wn
+from .mesh_io import read_mesh, read_ply, write_ply
 
 
 def _directed(src, dst, samples, seed):
-    """samples of mesh index `src` against mesh index `dst`: (dist [n], dot of the sample's and the closest face's normal [n])."""
+    """samples of mesh index `src` against mesh index `dst`: (dist [n], dot of the sample's and the closest face's normal [n], the
+    samples [n,3])."""
     pts, _, nrm = sd._sample(src.tri, src.cum_area, samples, seed)
     dist, face, _ = sd.closest_point(pts, dst)
-    return dist, (nrm * dst.face_normals()[face]).sum(1)
+    return dist, (nrm * dst.face_normals()[face]).sum(1), pts
+
+
+def _signed(dist, w):
+    """-dist where w >= 1/2, else dist; a distance of 0 stays +0 and NaN stays NaN."""
+    return torch.where((w >= 0.5) & (dist > 0), -dist, dist)
+
+
+def signed_distance(points, mesh_index, winding_index, beta=wn.BETA):
+    """(signed [P], winding [P]) float32 of points [P,3] against one mesh given as its MeshIndex and its WindingIndex: the exact
+    distance (closest_point), negative where the winding number (winding_number with `beta`) is >= 1/2, that is inside; a distance of
+    0 stays +0; a non-finite point gives NaN in both.  On an open mesh the sign is that of the surface closed smoothly over its
+    holes."""
+    dist = sd.closest_point(points, mesh_index)[0]
+    w = wn.winding_number(points, winding_index, beta=beta)
+    return _signed(dist, w), w
 
 
 ALIGN_MODES = ("rigid", "similarity")
@@ -52,7 +75,7 @@ def _alignment(pred, index, align, align_opts):
     return al.icp_index(pred, index, scale=align == "similarity", **opts)
 
 
-def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, align_opts=None):
+def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, align_opts=None, signed=False, beta=wn.BETA):
     """Distances between the surfaces of pred = (verts [V,3], faces [F,3]) and gt, GPU tensors, as a dict of Python floats.
 
     `samples` points are drawn on each surface (surfdist_ops.sample_surface: area-weighted, stratified; pred with `seed`, gt with
@@ -67,7 +90,13 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     `align` = None: no alignment or scaling.  "rigid" / "similarity": pred is first taken onto gt by align.icp_align (keywords in
     `align_opts`: samples, seed, iters, max_dist, tol, init, candidates, search_samples, top, refine_iters), its vertices are
     replaced by Alignment.apply of them, and `alignment` in the result carries matrix, scale, iterations, converged, rank, rms_before
-    and rms_after, and `search` (Alignment.search) when `init` asked for a rotation search.  An Alignment is applied as it is."""
+    and rms_after, and `search` (Alignment.search) when `init` asked for a rotation search.  An Alignment is applied as it is.
+
+    `signed` = True adds the block `signed`: per direction `mean`, the mean of the same samples' distances taken negative where the
+    sample lies inside the other mesh (signed_distance with `beta`; a positive pred_to_gt mean says the prediction lies outside the
+    ground truth there: inflated), and `inside_share`, the share of the samples inside; and `volume_pred` / `volume_gt`, the signed
+    volumes of the two meshes (pred after the alignment).  It reuses the samples and distances, and its reductions ride in the same
+    copy.  With `signed` = False the result is what it is without the keyword."""
     _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
     samples = int(samples)
     if samples <= 0:
@@ -82,8 +111,8 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     for name, m in (("pred", a), ("gt", b)):
         if not m.area > 0:
             raise ValueError(f"surface_metrics: the {name} mesh has no area")
-    d_ab, n_ab = _directed(a, b, samples, seed)
-    d_ba, n_ba = _directed(b, a, samples, seed + 1)
+    d_ab, n_ab, p_ab = _directed(a, b, samples, seed)
+    d_ba, n_ba, p_ba = _directed(b, a, samples, seed + 1)
     names, vals = [], []
     for name, d in (("pred_to_gt", d_ab.double()), ("gt_to_pred", d_ba.double())):
         names += [(name, "mean"), (name, "rms"), (name, "max")]
@@ -94,11 +123,19 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     for t in taus:
         names += [("P", t), ("R", t)]
         vals += [(d_ab < t).sum().double(), (d_ba < t).sum().double()]                 # (counts: the shares are divided on the host)
+    if signed:
+        wa, wb = wn.WindingIndex.build(a.verts, a.faces), wn.WindingIndex.build(b.verts, b.faces)
+        for name, d, pts, other in (("pred_to_gt", d_ab, p_ab, wb), ("gt_to_pred", d_ba, p_ba, wa)):
+            w = wn.winding_number(pts, other, beta=beta)
+            names += [("S", name, "mean"), ("S", name, "inside_share")]
+            vals += [_signed(d, w).double().mean(), (w >= 0.5).sum().double()]
     host = torch.stack(vals).cpu().tolist()
     out, pr = {"pred_to_gt": {}, "gt_to_pred": {}}, {}
     for name, v in zip(names, host):
         if name == "normal_consistency":
             out[name] = v
+        elif name[0] == "S":
+            out.setdefault("signed", {"pred_to_gt": {}, "gt_to_pred": {}})[name[1]][name[2]] = v / samples if name[2] == "inside_share" else v
         elif name[0] in ("P", "R"):
             pr[name] = v
         else:
@@ -108,21 +145,64 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     for t in taus:
         p, r = pr[("P", t)] / samples, pr[("R", t)] / samples
         out[f"fscore@{t:g}"] = 2. * p * r / (p + r) if p + r > 0 else 0.
+    if signed:
+        out["signed"]["volume_pred"], out["signed"]["volume_gt"] = wa.volume, wb.volume
     if found is not None:
         out["alignment"] = found.summary()
     return out
 
 
-def vertex_to_surface(verts, gt, align=None, align_opts=None, faces=None):
-    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh.  `align`
-    as in surface_metrics; "rigid" / "similarity" need the `faces` [F,3] of verts, whose surface is what gets aligned."""
+def vertex_to_surface(verts, gt, align=None, align_opts=None, faces=None, signed=False, beta=wn.BETA):
+    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh
+    (error_colors, write_error_mesh).  `align` as in surface_metrics; "rigid" / "similarity" need the `faces` [F,3] of verts, whose
+    surface is what gets aligned.  With `signed` the distance of a vertex inside gt is negative (signed_distance with `beta`)."""
     _lib.require_gpu(verts, gt[0], gt[1])
     index = sd.MeshIndex.build(gt[0], gt[1])
     if align is not None:
         if faces is None and not isinstance(align, al.Alignment):
             raise ValueError("vertex_to_surface: estimating an alignment needs the faces of verts")
         verts = _alignment((verts, faces), index, align, align_opts).apply(verts)
+    if signed:
+        return signed_distance(verts, index, wn.WindingIndex.build(index.verts, index.faces), beta)[0]
     return sd.closest_point(verts, index)[0]
+
+
+def error_colors(d, limit, signed):
+    """uint8 [V,3] red / green / blue of distances d [V] (torch ops on d's device): with t = clamp(d / limit, -1, 1), for t >= 0
+    (255, 255 (1 - t), 255 (1 - t)), white to red -- outside, or too far --, and for t < 0 (255 (1 + t), 255 (1 + t), 255), white to
+    blue -- inside.  Channels are rounded half up: floor(x + 1/2), in double.  `signed` = False uses the red half only: t = clamp(d
+    / limit, 0, 1).  A NaN distance gives grey (128, 128, 128)."""
+    limit = float(limit)
+    if not (limit > 0 and np.isfinite(limit)):
+        raise ValueError(f"error_colors: limit > 0 expected, got {limit}")
+    t = (d.detach().double() / limit).clamp(-1. if signed else 0., 1.)
+    fade = torch.floor(255. * (1. - t.abs()) + 0.5)
+    full = torch.full_like(fade, 255.)
+    rgb = torch.stack([torch.where(t >= 0, full, fade), fade, torch.where(t >= 0, fade, full)], 1)
+    return torch.where(torch.isnan(t)[:, None], torch.full_like(rgb, 128.), rgb).to(torch.uint8)
+
+
+def error_range(d):
+    """The default range of the error map: the 95th percentile of |d| over the finite entries (the ceil(0.95 n)-th smallest), 1 when
+    that is 0 or nothing is finite.  One device -> host read."""
+    mag = d.detach().abs()
+    mag = mag[torch.isfinite(mag)]
+    if mag.numel() == 0:
+        return 1.
+    limit = float(torch.kthvalue(mag, max(1, int(np.ceil(0.95 * mag.numel()))))[0])
+    return limit if limit > 0 else 1.
+
+
+def write_error_mesh(path, pred, gt, alignment=None, signed=False, beta=wn.BETA, limit=None, out=print):
+    """Writes pred = (verts, faces), taken through `alignment` (an Alignment or None), as a PLY coloured by error_colors of
+    vertex_to_surface against gt; `limit` = None takes error_range of those distances and says so through `out`.  -> the limit."""
+    verts = pred[0] if alignment is None else alignment.apply(pred[0])
+    d = vertex_to_surface(verts, gt, signed=signed, beta=beta)
+    if limit is None:
+        limit = error_range(d)
+        out("      error range %.6g (95th percentile of |d|) for %s" % (limit, path))
+    write_ply(path, verts.cpu().numpy(), pred[1].cpu().numpy(), error_colors(d, limit, signed).cpu().numpy())
+    return limit
 
 
 def _to_device(mesh, device):
@@ -143,6 +223,25 @@ def write_geometry_errors(path, fids, chamfer, p2s):
             ff.write("\n")
 
 
+def write_geometry_signed(path, fids, pred_to_gt, gt_to_pred):
+    """geometry_signed.txt in the layout of geometry_errors.txt: the signed means of both directions per frame."""
+    with open(path, "w") as ff:
+        ff.write("      pred_to_gt gt_to_pred\n")
+        for fid, a, b in zip(fids, pred_to_gt, gt_to_pred):
+            ff.write("%4s: %.6f %.6f\n" % (fid, a, b))
+        for name, col in (("pred_to_gt", np.asarray(pred_to_gt, np.float64)), ("gt_to_pred", np.asarray(gt_to_pred, np.float64))):
+            ff.write("%s mean: %.6f, max: %.6f, min: %.6f, maxinds:" % (name, col.mean(), col.max(), col.min()))
+            for ind in (-col).argsort()[:10]:
+                ff.write("%d " % ind)
+            ff.write("\n")
+
+
+def signed_line(block):
+    """What folder mode prints under a frame with --signed."""
+    return "      signed pred_to_gt %.6f (inside %.3f) gt_to_pred %.6f (inside %.3f)" % (
+        block["pred_to_gt"]["mean"], block["pred_to_gt"]["inside_share"], block["gt_to_pred"]["mean"], block["gt_to_pred"]["inside_share"])
+
+
 def search_line(search):
     """What folder mode prints under a frame whose alignment started from a rotation search."""
     k = search["top"].index(search["winner"])
@@ -156,9 +255,10 @@ def _frame_ids(folder):
 
 
 def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, seed=0, taus=(), out=print, align=None, align_opts=None,
-                    align_shared=False):
+                    align_shared=False, signed=False, beta=wn.BETA, error_meshes=False, limit=None):
     """Folder mode (see the module text).  -> dict(frames: {fid: metrics}, skipped: [fid], summary).  With `align_shared` the
-    alignment is estimated on the first compared frame and applied to every frame."""
+    alignment is estimated on the first compared frame and applied to every frame.  `signed` adds the signed blocks, a line per frame
+    and geometry_signed.txt; `error_meshes` writes geometry_errors/<fid>.ply (write_error_mesh with `limit`)."""
     _, faces = read_ply(os.path.join(rec_root, "tmp.ply"))
     faces_d = torch.from_numpy(faces).to(device)
     fids = _frame_ids(os.path.join(rec_root, "meshs"))
@@ -172,22 +272,33 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
             continue
         verts = torch.from_numpy(np.load(os.path.join(rec_root, "meshs", fid + ".npy")).astype(np.float32).reshape(-1, 3)).to(device)
         pred, gt = (verts, faces_d), _to_device(read_mesh(gt_file), device)
+        extra = {"signed": True, "beta": beta} if signed else {}
         if align is None:
-            per[fid] = surface_metrics(pred, gt, samples, seed, taus)
+            per[fid] = surface_metrics(pred, gt, samples, seed, taus, **extra)
+            used = None
         else:
             if align_shared and not isinstance(align, al.Alignment):
                 align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
-            per[fid] = surface_metrics(pred, gt, samples, seed, taus, align, align_opts)
+            used = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts) if error_meshes else align
+            per[fid] = surface_metrics(pred, gt, samples, seed, taus, used, align_opts, **extra)
         out("%4s: chamfer %.6f p2s %.6f" % (fid, per[fid]["chamfer"], per[fid]["p2s"]))
         found = per[fid].get("alignment", {}).get("search")
         if found is not None:
             out(search_line(found))
+        if signed:
+            out(signed_line(per[fid]["signed"]))
+        if error_meshes:
+            os.makedirs(os.path.join(rec_root, "geometry_errors"), exist_ok=True)
+            write_error_mesh(os.path.join(rec_root, "geometry_errors", fid + ".ply"), pred, gt, used, signed, beta, limit, out)
     out("%d frames compared, %d skipped (no ground-truth file)" % (len(per), len(skipped)))
     if not per:
         raise ValueError(f"evaluate: no frame of {rec_root}/meshs has a ground-truth file in {gt_root}")
     order = list(per)
     chamfer, p2s = [per[f]["chamfer"] for f in order], [per[f]["p2s"] for f in order]
     write_geometry_errors(os.path.join(rec_root, "geometry_errors.txt"), order, chamfer, p2s)
+    if signed:
+        write_geometry_signed(os.path.join(rec_root, "geometry_signed.txt"), order, [per[f]["signed"]["pred_to_gt"]["mean"] for f in order],
+                              [per[f]["signed"]["gt_to_pred"]["mean"] for f in order])
     result = {"frames": per, "skipped": skipped,
               "summary": {"chamfer_mean": float(np.mean(chamfer)), "chamfer_max": float(np.max(chamfer)), "p2s_mean": float(np.mean(p2s)),
                           "p2s_max": float(np.max(p2s)), "samples": int(samples), "seed": int(seed)}}
@@ -223,6 +334,15 @@ def build_parser():
     parser.add_argument("--align-top", default=8, type=int, metavar="K", help="candidates of the search that are refined by short ICP runs")
     parser.add_argument("--align-shared", action="store_true",
                         help="folder mode: estimate the alignment on the first compared frame and use it for every frame (default: per frame)")
+    parser.add_argument("--signed", action="store_true",
+                        help="also say on which side the surfaces lie: signed means, inside shares and volumes (winding number)")
+    parser.add_argument("--beta", default=wn.BETA, type=float, metavar="b",
+                        help="--signed: a cluster of faces counts as one dipole from farther than b of its radii (>= 1; inf: never)")
+    parser.add_argument("--error-range", default=None, type=float, metavar="d",
+                        help="the distance at which the error map saturates (default: the 95th percentile of |d| over the mesh, printed)")
+    parser.add_argument("--error-mesh", default=None, metavar="FILE.ply",
+                        help="mesh-pair mode: write the (aligned) predicted mesh coloured by its vertices' distance to the ground truth")
+    parser.add_argument("--error-meshes", action="store_true", help="folder mode: write such a mesh per frame, R/geometry_errors/<fid>.ply")
     return parser
 
 
@@ -251,6 +371,14 @@ def parse_args(argv=None):
         parser.error("--align-init needs --align rigid or similarity")
     if args.align_shared and (args.align == "none" or not all(folder)):
         parser.error("--align-shared needs folder mode and --align rigid or similarity")
+    if args.error_mesh is not None and not all(pair):
+        parser.error("--error-mesh needs mesh-pair mode (folder mode: --error-meshes)")
+    if args.error_meshes and not all(folder):
+        parser.error("--error-meshes needs folder mode (mesh-pair mode: --error-mesh FILE.ply)")
+    if args.error_range is not None and not (args.error_range > 0 and np.isfinite(args.error_range)):
+        parser.error("--error-range must be positive")
+    if not args.beta >= 1:
+        parser.error("--beta must be at least 1")
     return args
 
 
@@ -266,16 +394,21 @@ def main(argv=None, out=print):
     args = parse_args(argv)
     device = torch.device("cuda", args.gpu_ids[0])
     align, align_opts = _align_args(args)
+    extra = {"signed": True, "beta": args.beta} if args.signed else {}
     if args.pred:
-        m = surface_metrics(_to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device), args.samples, args.seed, args.tau,
-                            align, align_opts)
+        pred, gt = _to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device)
+        if args.error_mesh is not None and align is not None:
+            align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
+        m = surface_metrics(pred, gt, args.samples, args.seed, args.tau, align, align_opts, **extra)
         out(json.dumps(m))
+        if args.error_mesh is not None:
+            write_error_mesh(args.error_mesh, pred, gt, align, args.signed, args.beta, args.error_range, out)
         if args.out:
             with open(args.out, "w") as fh:
                 json.dump(m, fh, indent=1)
         return m
     return evaluate_folder(args.rec_root, args.gt_root, device, args.frames, args.samples, args.seed, args.tau, out, align, align_opts,
-                           args.align_shared)
+                           args.align_shared, args.signed, args.beta, args.error_meshes, args.error_range)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
-"""Every mesh file of the package, on the standard library and numpy: PLY read (ASCII, binary little-endian) and written (ASCII), OBJ
-geometry as the evaluation takes it from anywhere (read_obj) and template/uvmap.obj, the OBJ with texture coordinates of the texture and
+"""Every mesh file of the package, on the standard library and numpy: PLY read (ASCII, binary little-endian) and written (ASCII, with
+or without vertex colours), OBJ geometry as the evaluation takes it from anywhere (read_obj) and template/uvmap.obj, the OBJ with
+texture coordinates of the texture and
 render stages (read_obj_uv / write_obj_uv).  The OBJ readers stay two parsers: one streams, counts a negative index back from the vertices
 read so far and checks no range; the other counts from all `v` / `vt` lines, checks both ranges and demands a texture index."""
 import os
@@ -118,14 +119,23 @@ def read_ply(path):
     return verts, faces
 
 
-def write_ply(path, verts, faces):
-    """ASCII PLY of a triangle mesh (verts [V,3] float, faces [F,3] int)."""
+def write_ply(path, verts, faces, colors=None):
+    """ASCII PLY of a triangle mesh (verts [V,3] float, faces [F,3] int).  `colors` [V,3] uint8, when given, are written as `uchar
+    red / green / blue` vertex properties (read_ply skips them); without them the file is what it always was."""
     v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
     f = np.asarray(faces, dtype=np.int64).reshape(-1, 3)
+    if colors is not None:
+        c = np.asarray(colors)
+        if c.dtype != np.uint8 or c.shape != v.shape:
+            raise ValueError(f"write_ply: colors [{len(v)},3] uint8 expected, got {c.dtype} {c.shape}")
     with open(path, "w") as fh:
-        fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
-                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % (len(v), len(f)))
-        fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+        fh.write("ply\nformat ascii 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n%s"
+                 "element face %d\nproperty list uchar int vertex_indices\nend_header\n"
+                 % (len(v), "" if colors is None else "property uchar red\nproperty uchar green\nproperty uchar blue\n", len(f)))
+        if colors is None:
+            fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+        else:
+            fh.writelines("%.9g %.9g %.9g %d %d %d\n" % (*p, *q) for p, q in zip(v.tolist(), c.tolist()))
         fh.writelines("3 %d %d %d\n" % tuple(t) for t in f.tolist())
 
 
