@@ -7,8 +7,9 @@ tens of degrees on a body-like shape).  The default start only matches centroids
 another up axis, a scan facing the other way -- `init="axes"` / `init="search"` put a deterministic coarse-to-fine rotation search in
 front: every rotation of a fixed table about the matched centroids gets a symmetric truncated score in one launch per
 direction (sr_icp_score), the best few are refined by short ICP runs, and the ordinary ICP starts from the best of those.  An `init`
-matrix is taken as it is.  Out of scope: partial overlap and outlier-robust registration, reflections, non-rigid alignment,
-point-to-point and symmetric ICP objectives, quantile trimming."""
+matrix is taken as it is.  Either mesh may be a surfdist_ops.Surface, which prepares it once and keeps its grid: pred is prepared once
+per call (the search's reverse direction uses the same Surface), gt's grid is the caller's to keep (icp_index).  Out of scope: partial
+overlap and outlier-robust registration, reflections, non-rigid alignment, point-to-point and symmetric ICP objectives, quantile trimming."""
 from dataclasses import dataclass
 import itertools
 
@@ -16,7 +17,6 @@ import numpy as np
 import torch
 
 from . import _lib
-from . import mesh_prep_ops as mp
 from . import surfdist_ops as sd
 
 MAX_BLOCKS, COLS, HISTORY, STATE, DONE = _lib.SR_ICP_MAX_BLOCKS, _lib.SR_ICP_COLS, _lib.SR_ICP_HISTORY, _lib.SR_ICP_STATE, _lib.SR_ICP_DONE
@@ -95,10 +95,9 @@ def check_init(init):
 
 
 def frame_of(index):
-    """((ox, oy, oz), rho) as Python floats: the centre and the half diagonal of the box of the index's vertices (rho = 1 for a mesh
-    that is one point).  One device -> host copy."""
-    lo, hi = mp.mesh_bounds(index.verts)
-    box = torch.cat([lo, hi]).cpu().numpy().astype(np.float64)
+    """((ox, oy, oz), rho) as Python floats: the centre and the half diagonal of the box of the vertices of `index` (a MeshIndex or a
+    Surface: its `box`; rho = 1 for a mesh that is one point)."""
+    box = index.box.astype(np.float64)
     o = 0.5 * (box[:3] + box[3:])
     rho = 0.5 * float(np.sqrt(((box[3:] - box[:3]) ** 2).sum()))
     return (float(o[0]), float(o[1]), float(o[2])), rho if rho > 0 else 1.
@@ -110,9 +109,8 @@ def accumulate(points, index, state, frame, max_dist, partial, measure=False):
     if partial.shape != (blocks_of(S), COLS) or partial.dtype != torch.float64 or not partial.is_contiguous():
         raise ValueError(f"partial [{blocks_of(S)}, {COLS}] float64 expected")
     o, rho = frame
-    n = index.n
-    _lib.launch("sr_icp_accumulate", points, points, S, index.tri, index.faces.shape[0], index.lo, index.cell, n[0], n[1], n[2], index.cell_start,
-                index.cell_faces, index.pairs, state, o[0], o[1], o[2], rho, float(max_dist), int(bool(measure)), partial, partial.shape[0])
+    _lib.launch("sr_icp_accumulate", points, points, S, *index.args(), state, o[0], o[1], o[2], rho, float(max_dist), int(bool(measure)), partial,
+                partial.shape[0])
 
 
 def solve(partial, frame, scale, tol, it, iters, state, history):
@@ -172,9 +170,7 @@ def score_candidates(points, index, table, trunc):
     if trunc.shape != (N,) or trunc.dtype != torch.float32 or not trunc.is_contiguous():
         raise ValueError(f"trunc [{N}] float32 expected, got {tuple(trunc.shape)} {trunc.dtype}")
     score = torch.empty((N, 2), dtype=torch.float64, device=points.device)
-    n = index.n
-    _lib.launch("sr_icp_score", points, points, points.shape[0], table, N, index.tri, index.faces.shape[0], index.lo, index.cell, n[0], n[1], n[2],
-                index.cell_start, index.cell_faces, index.pairs, trunc, score)
+    _lib.launch("sr_icp_score", points, points, points.shape[0], table, N, *index.args(), trunc, score)
     return score
 
 
@@ -203,8 +199,7 @@ def _iterate(p, index, frame, M, t, iters, scale, max_dist, tol):
     state[:9] = M.reshape(9)
     state[9:12] = t
     # a wave walks neighbouring cells: the samples in the order of their cell keys under the initial transform (part of the sums' definition)
-    order = torch.sort(mp.cell_keys(transform_points(M, t, p), index.lo, index.cell, index.n), stable=True)[1]
-    p = p[order].contiguous()
+    p = sd.in_key_order(p, index.keys(transform_points(M, t, p)))[0]
     partial = torch.zeros((blocks_of(p.shape[0]), COLS), dtype=torch.float64, device=dev)
     for it in range(iters):
         accumulate(p, index, state, frame, max_dist, partial)
@@ -214,7 +209,7 @@ def _iterate(p, index, frame, M, t, iters, scale, max_dist, tol):
 
 def _in_cell_order(points, index):
     """points in the order of their cell keys in the grid of `index` (stable)."""
-    return points[torch.sort(mp.cell_keys(points, index.lo, index.cell, index.n), stable=True)[1]].contiguous()
+    return sd.in_key_order(points, index.keys(points))[0]
 
 
 def symmetric_score(P, G, index, index_pred, M, t, max_dist):
@@ -233,12 +228,12 @@ def symmetric_score(P, G, index, index_pred, M, t, max_dist):
     return torch.where((there[:, 1] > 0) & (here[:, 1] > 0) & ~torch.isnan(J), J, torch.full_like(J, float("inf")))
 
 
-def _search(kind, verts, faces, index, frame, seed, scale, max_dist, tol, candidates, search_samples, top, refine_iters):
-    """The rotation search of DESIGN.md 3.22 -> (M [3,3], t [3], record) on the device: the refined transform of the winner, and
-    record = (top indices [K], their J [K], their refined J [K], the winner's position in top, its refined M and t [12]) as one
-    float64 tensor.  Nothing is read back."""
-    index_pred = sd.MeshIndex.build(verts, faces)
-    P = sd._sample(index_pred.tri, index_pred.cum_area, search_samples, seed)[0]
+def _search(kind, pred, index, frame, seed, scale, max_dist, tol, candidates, search_samples, top, refine_iters):
+    """The rotation search of DESIGN.md 3.22 for the Surface `pred` -> (M [3,3], t [3], record) on the device: the refined transform of
+    the winner, and record = (top indices [K], their J [K], their refined J [K], the winner's position in top, its refined M and t
+    [12]) as one float64 tensor.  The reverse direction walks pred.grid(); its pair total is the only read."""
+    index_pred = pred.grid()
+    P = pred.sample(search_samples, seed)[0]
     G = sd._sample(index.tri, index.cum_area, search_samples, seed + 1)[0]
     cp, cg, s = _centroids(P, G, scale)
     P, G = _in_cell_order(P, index_pred), _in_cell_order(G, index)
@@ -266,7 +261,7 @@ def _search_record(kind, N, K, rec):
 
 def icp_index(pred, index, samples=100_000, seed=0, iters=30, scale=False, max_dist=None, tol=2. ** -23, init="centroid", candidates=4096,
               search_samples=4096, top=8, refine_iters=10):
-    """icp_align against a MeshIndex of the target that the caller already has."""
+    """icp_align against a MeshIndex of the target that the caller already has; pred, a Surface or a pair, is prepared once."""
     samples, iters, tol = int(samples), int(iters), float(tol)
     if samples <= 0 or iters <= 0:
         raise ValueError(f"samples > 0 and iters > 0 expected, got {samples} and {iters}")
@@ -281,15 +276,13 @@ def icp_index(pred, index, samples=100_000, seed=0, iters=30, scale=False, max_d
     fixed = None if isinstance(init, str) else check_init(init)
     if fixed is None and init not in INITS:
         raise ValueError(f"init must be 'centroid', 'none', 'axes', 'search' or a 4 x 4 matrix, got {init!r}")
-    verts, faces = sd._mesh(pred[0], pred[1], "icp_align")
-    dev = verts.device
-    cum = sd.face_areas_cum(verts, faces)
-    sizes = torch.stack([cum[-1], index.cum_area[-1]]).cpu().tolist()
-    for name, area in zip(("pred", "gt"), sizes):
+    pred = sd.Surface.of(pred, "icp_align")
+    dev = pred.verts.device
+    for name, area in (("pred", pred.area), ("gt", index.area)):
         if not (area > 0 and np.isfinite(area)):
             raise ValueError(f"icp_align: the {name} mesh has total area {area}")
     frame = frame_of(index)
-    p = sd._sample(sd._pack(verts, faces), cum, samples, seed)[0]
+    p = pred.sample(samples, seed)[0]
     record = torch.zeros((0,), dtype=torch.float64, device=dev)
     if fixed is not None:
         M, t = torch.from_numpy(fixed[0]).to(dev), torch.from_numpy(fixed[1]).to(dev)
@@ -298,7 +291,7 @@ def icp_index(pred, index, samples=100_000, seed=0, iters=30, scale=False, max_d
     elif init == "none":
         M, t = torch.eye(3, dtype=torch.float64, device=dev), torch.zeros(3, dtype=torch.float64, device=dev)
     else:
-        M, t, record = _search(init, verts, faces, index, frame, seed, scale, max_dist, tol, candidates, search_samples, top, refine_iters)
+        M, t, record = _search(init, pred, index, frame, seed, scale, max_dist, tol, candidates, search_samples, top, refine_iters)
     p, buf, partial = _iterate(p, index, frame, M, t, iters, scale, max_dist, tol)
     accumulate(p, index, buf[:STATE], frame, max_dist, partial, measure=True)             # the kept pairs under the result
     host = torch.cat([buf, partial[:, 36:38].sum(0), record]).cpu().numpy()
@@ -321,8 +314,9 @@ def icp_index(pred, index, samples=100_000, seed=0, iters=30, scale=False, max_d
 
 def icp_align(pred, gt, samples=100_000, seed=0, iters=30, scale=False, max_dist=None, tol=2. ** -23, init="centroid", candidates=4096,
               search_samples=4096, top=8, refine_iters=10):
-    """The Alignment that takes pred = (verts [V,3], faces [F,3]) onto gt, GPU tensors: point-to-plane ICP of `samples` surface samples
-    of pred (surfdist_ops.sample_surface with `seed`) against the mesh gt, rigid, or a similarity with `scale`.
+    """The Alignment that takes pred = (verts [V,3], faces [F,3]) onto gt, GPU tensors (each a pair or a surfdist_ops.Surface, whose
+    grid is then used and kept): point-to-plane ICP of `samples` surface samples of pred (surfdist_ops.sample_surface with `seed`)
+    against the mesh gt, rigid, or a similarity with `scale`.
 
     Every iteration is two launches: sr_icp_accumulate transforms the samples with the float64 state, finds every sample's closest
     point on gt (the exact float32 search of closest_point), keeps the pairs within `max_dist` (float32, `<=`; default: all) and sums
@@ -339,7 +333,5 @@ def icp_align(pred, gt, samples=100_000, seed=0, iters=30, scale=False, max_dist
     `refine_iters` ICP iterations on the search samples and are scored again; the ICP proper starts from the lowest refined J.  Ties go
     to the lower index.  `Alignment.search` records the choice.  ICP itself is local: with "centroid", a large rotation ends in a
     converged, wrong alignment.  ValueError for a mesh without area, and RuntimeError for CPU tensors."""
-    _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
-    return icp_index(pred, sd.MeshIndex.build(gt[0], gt[1]), samples, seed, iters, scale, max_dist, tol, init, candidates, search_samples, top,
-                     refine_iters)
-
+    gt = sd.Surface.of(gt, "MeshIndex.build")
+    return icp_index(pred, gt.grid(), samples, seed, iters, scale, max_dist, tol, init, candidates, search_samples, top, refine_iters)

@@ -20,6 +20,8 @@ signed distance and the share of samples inside, per direction, and both signed 
 `--error-meshes` (folder mode: `R/geometry_errors/<fid>.ply`) write the predicted mesh, aligned if an alignment was asked for, coloured
 by each vertex's distance to the ground truth: white to red up to `--error-range` (default: the 95th percentile of |d| over the mesh,
 which is printed), and with `--signed` white to blue for the vertices inside the ground truth.
+Every mesh is prepared once, as a surfdist_ops.Surface that owns its grid, pyramid and normals: both modes make one per ground-truth
+file, resolve the alignment once against its grid and pass the Alignment on, and the functions here take a Surface in place of a pair.
 Out of scope: partial overlap, reflections, quads, rendering the error map to an image.
 """
 import argparse
@@ -29,7 +31,6 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
 from . import align as al
 from . import surfdist_ops as sd
 from . import winding_ops as wn
@@ -37,10 +38,10 @@ from .mesh_io import read_mesh, read_ply, write_ply
 
 
 def _directed(src, dst, samples, seed):
-    """samples of mesh index `src` against mesh index `dst`: (dist [n], dot of the sample's and the closest face's normal [n], the
-    samples [n,3])."""
-    pts, _, nrm = sd._sample(src.tri, src.cum_area, samples, seed)
-    dist, face, _ = sd.closest_point(pts, dst)
+    """samples of Surface `src` against Surface `dst`: (dist [n], dot of the sample's and the closest face's normal [n], the samples
+    [n,3])."""
+    pts, _, nrm = src.sample(samples, seed)
+    dist, face, _ = sd.closest_point(pts, dst.grid())
     return dist, (nrm * dst.face_normals()[face]).sum(1), pts
 
 
@@ -62,21 +63,22 @@ def signed_distance(points, mesh_index, winding_index, beta=wn.BETA):
 ALIGN_MODES = ("rigid", "similarity")
 
 
-def _alignment(pred, index, align, align_opts):
-    """The Alignment `align` asks for: "rigid" / "similarity" estimate it (pred = (verts, faces) against the MeshIndex of gt, with
-    `align_opts` as keywords of align.icp_align), an Alignment is taken as it is."""
-    if isinstance(align, al.Alignment):
+def _alignment(pred, gt, align, align_opts):
+    """The Alignment `align` asks for: "rigid" / "similarity" estimate it (pred, a pair or a Surface, against the grid of the Surface
+    gt, with `align_opts` as keywords of align.icp_align), an Alignment or None is taken as it is."""
+    if align is None or isinstance(align, al.Alignment):
         return align
     if align not in ALIGN_MODES:
         raise ValueError(f"align must be None, 'rigid', 'similarity' or an Alignment, got {align!r}")
     opts = dict(align_opts or {})
     if "scale" in opts:
         raise ValueError("align_opts: `scale` is what `align` decides")
-    return al.icp_index(pred, index, scale=align == "similarity", **opts)
+    return al.icp_index(pred, gt.grid(), scale=align == "similarity", **opts)
 
 
 def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, align_opts=None, signed=False, beta=wn.BETA):
-    """Distances between the surfaces of pred = (verts [V,3], faces [F,3]) and gt, GPU tensors, as a dict of Python floats.
+    """Distances between the surfaces of pred = (verts [V,3], faces [F,3]) and gt, GPU tensors, as a dict of Python floats.  Either
+    may be a surfdist_ops.Surface instead of a pair: what it has built is used, what is built here stays with it for the next call.
 
     `samples` points are drawn on each surface (surfdist_ops.sample_surface: area-weighted, stratified; pred with `seed`, gt with
     `seed + 1`) and each is given its exact distance to the other mesh (closest_point).  Per direction, `pred_to_gt` and `gt_to_pred`:
@@ -85,7 +87,7 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     over both directions of the dot product between the sample's face normal and the unit normal of the closest face (signed; 0 for a
     closest face without area).  `fscore@tau` for every tau: 2 P R / (P + R) with P the share of pred_to_gt < tau and R the share of
     gt_to_pred < tau (0 when both are 0).  Reductions are torch's on fixed shapes, in double; two calls give identical numbers; the
-    results come to the host in one copy (the two index builds read their sizes on the way).
+    results come to the host in one copy (preparing a mesh and building its grid read their sizes on the way).
 
     `align` = None: no alignment or scaling.  "rigid" / "similarity": pred is first taken onto gt by align.icp_align (keywords in
     `align_opts`: samples, seed, iters, max_dist, tol, init, candidates, search_samples, top, refine_iters), its vertices are
@@ -97,17 +99,13 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
     ground truth there: inflated), and `inside_share`, the share of the samples inside; and `volume_pred` / `volume_gt`, the signed
     volumes of the two meshes (pred after the alignment).  It reuses the samples and distances, and its reductions ride in the same
     copy.  With `signed` = False the result is what it is without the keyword."""
-    _lib.require_gpu(pred[0], pred[1], gt[0], gt[1])
     samples = int(samples)
     if samples <= 0:
         raise ValueError(f"samples > 0 expected, got {samples}")
-    found = None
-    if align is None:
-        a, b = sd.MeshIndex.build(pred[0], pred[1]), sd.MeshIndex.build(gt[0], gt[1])
-    else:
-        b = sd.MeshIndex.build(gt[0], gt[1])
-        found = _alignment(pred, b, align, align_opts)
-        a = sd.MeshIndex.build(found.apply(pred[0]), pred[1])
+    a, b = sd.Surface.of(pred, "MeshIndex.build"), sd.Surface.of(gt, "MeshIndex.build")
+    found = _alignment(a, b, align, align_opts)
+    if found is not None:
+        a = a.moved(found.apply(a.verts))
     for name, m in (("pred", a), ("gt", b)):
         if not m.area > 0:
             raise ValueError(f"surface_metrics: the {name} mesh has no area")
@@ -124,7 +122,7 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
         names += [("P", t), ("R", t)]
         vals += [(d_ab < t).sum().double(), (d_ba < t).sum().double()]                 # (counts: the shares are divided on the host)
     if signed:
-        wa, wb = wn.WindingIndex.build(a.verts, a.faces), wn.WindingIndex.build(b.verts, b.faces)
+        wa, wb = a.pyramid(), b.pyramid()
         for name, d, pts, other in (("pred_to_gt", d_ab, p_ab, wb), ("gt_to_pred", d_ba, p_ba, wa)):
             w = wn.winding_number(pts, other, beta=beta)
             names += [("S", name, "mean"), ("S", name, "inside_share")]
@@ -153,18 +151,17 @@ def surface_metrics(pred, gt, samples=1_000_000, seed=0, taus=(), align=None, al
 
 
 def vertex_to_surface(verts, gt, align=None, align_opts=None, faces=None, signed=False, beta=wn.BETA):
-    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) -- for colouring a mesh
+    """dist [V] float32: the distance of every vertex of verts [V,3] to the mesh gt = (verts, faces) or Surface -- for colouring a mesh
     (error_colors, write_error_mesh).  `align` as in surface_metrics; "rigid" / "similarity" need the `faces` [F,3] of verts, whose
     surface is what gets aligned.  With `signed` the distance of a vertex inside gt is negative (signed_distance with `beta`)."""
-    _lib.require_gpu(verts, gt[0], gt[1])
-    index = sd.MeshIndex.build(gt[0], gt[1])
+    gt = sd.Surface.of(gt, "MeshIndex.build")
     if align is not None:
         if faces is None and not isinstance(align, al.Alignment):
             raise ValueError("vertex_to_surface: estimating an alignment needs the faces of verts")
-        verts = _alignment((verts, faces), index, align, align_opts).apply(verts)
+        verts = _alignment((verts, faces), gt, align, align_opts).apply(verts)
     if signed:
-        return signed_distance(verts, index, wn.WindingIndex.build(index.verts, index.faces), beta)[0]
-    return sd.closest_point(verts, index)[0]
+        return signed_distance(verts, gt.grid(), gt.pyramid(), beta)[0]
+    return sd.closest_point(verts, gt.grid())[0]
 
 
 def error_colors(d, limit, signed):
@@ -195,41 +192,35 @@ def error_range(d):
 
 def write_error_mesh(path, pred, gt, alignment=None, signed=False, beta=wn.BETA, limit=None, out=print):
     """Writes pred = (verts, faces), taken through `alignment` (an Alignment or None), as a PLY coloured by error_colors of
-    vertex_to_surface against gt; `limit` = None takes error_range of those distances and says so through `out`.  -> the limit."""
-    verts = pred[0] if alignment is None else alignment.apply(pred[0])
+    vertex_to_surface against gt (each a pair or a Surface); `limit` = None takes error_range of those distances and says so through
+    `out`.  -> the limit."""
+    verts, faces = pred
+    if alignment is not None:
+        verts = alignment.apply(verts)
     d = vertex_to_surface(verts, gt, signed=signed, beta=beta)
     if limit is None:
         limit = error_range(d)
         out("      error range %.6g (95th percentile of |d|) for %s" % (limit, path))
-    write_ply(path, verts.cpu().numpy(), pred[1].cpu().numpy(), error_colors(d, limit, signed).cpu().numpy())
+    write_ply(path, verts.cpu().numpy(), faces.cpu().numpy(), error_colors(d, limit, signed).cpu().numpy())
     return limit
 
 
-def _to_device(mesh, device):
-    return torch.from_numpy(np.asarray(mesh[0], np.float32)).to(device), torch.from_numpy(np.asarray(mesh[1], np.int64)).to(device)
+def _surface(mesh, device):
+    """The Surface, on `device`, of mesh = (verts, faces) as numpy arrays: a file is prepared once for everything asked of it."""
+    verts, faces = torch.from_numpy(np.asarray(mesh[0], np.float32)).to(device), torch.from_numpy(np.asarray(mesh[1], np.int64)).to(device)
+    return sd.Surface(verts, faces, "MeshIndex.build")
 
 
-def write_geometry_errors(path, fids, chamfer, p2s):
-    """geometry_errors.txt in the layout of infer's errors.txt: one line per frame, then mean / max / min and the ten worst frames (as
-    positions in the list of compared frames, like `maxinds` there) of each column."""
+def write_columns(path, fids, columns):
+    """geometry_errors.txt / geometry_signed.txt in the layout of infer's errors.txt: a line of the names of `columns` (name -> one
+    value per frame), one line per frame, then mean / max / min and the ten worst frames (as positions in the list of compared frames,
+    like `maxinds` there) of each column."""
     with open(path, "w") as ff:
-        ff.write("      chamfer p2s\n")
-        for fid, c, p in zip(fids, chamfer, p2s):
-            ff.write("%4s: %.6f %.6f\n" % (fid, c, p))
-        for name, col in (("chamfer", np.asarray(chamfer, np.float64)), ("p2s", np.asarray(p2s, np.float64))):
-            ff.write("%s mean: %.6f, max: %.6f, min: %.6f, maxinds:" % (name, col.mean(), col.max(), col.min()))
-            for ind in (-col).argsort()[:10]:
-                ff.write("%d " % ind)
-            ff.write("\n")
-
-
-def write_geometry_signed(path, fids, pred_to_gt, gt_to_pred):
-    """geometry_signed.txt in the layout of geometry_errors.txt: the signed means of both directions per frame."""
-    with open(path, "w") as ff:
-        ff.write("      pred_to_gt gt_to_pred\n")
-        for fid, a, b in zip(fids, pred_to_gt, gt_to_pred):
-            ff.write("%4s: %.6f %.6f\n" % (fid, a, b))
-        for name, col in (("pred_to_gt", np.asarray(pred_to_gt, np.float64)), ("gt_to_pred", np.asarray(gt_to_pred, np.float64))):
+        ff.write("      %s\n" % " ".join(columns))
+        for fid, row in zip(fids, zip(*columns.values())):
+            ff.write("%4s: %s\n" % (fid, " ".join("%.6f" % v for v in row)))
+        for name, col in columns.items():
+            col = np.asarray(col, np.float64)
             ff.write("%s mean: %.6f, max: %.6f, min: %.6f, maxinds:" % (name, col.mean(), col.max(), col.min()))
             for ind in (-col).argsort()[:10]:
                 ff.write("%d " % ind)
@@ -271,16 +262,10 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
             skipped.append(fid)
             continue
         verts = torch.from_numpy(np.load(os.path.join(rec_root, "meshs", fid + ".npy")).astype(np.float32).reshape(-1, 3)).to(device)
-        pred, gt = (verts, faces_d), _to_device(read_mesh(gt_file), device)
-        extra = {"signed": True, "beta": beta} if signed else {}
-        if align is None:
-            per[fid] = surface_metrics(pred, gt, samples, seed, taus, **extra)
-            used = None
-        else:
-            if align_shared and not isinstance(align, al.Alignment):
-                align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
-            used = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts) if error_meshes else align
-            per[fid] = surface_metrics(pred, gt, samples, seed, taus, used, align_opts, **extra)
+        pred, gt = sd.Surface(verts, faces_d, "MeshIndex.build"), _surface(read_mesh(gt_file), device)
+        used = _alignment(pred, gt, align, align_opts)                                           # once per frame, against gt's kept grid
+        align = used if align_shared else align
+        per[fid] = surface_metrics(pred, gt, samples, seed, taus, used, signed=signed, beta=beta)
         out("%4s: chamfer %.6f p2s %.6f" % (fid, per[fid]["chamfer"], per[fid]["p2s"]))
         found = per[fid].get("alignment", {}).get("search")
         if found is not None:
@@ -295,10 +280,10 @@ def evaluate_folder(rec_root, gt_root, device, frames=None, samples=1_000_000, s
         raise ValueError(f"evaluate: no frame of {rec_root}/meshs has a ground-truth file in {gt_root}")
     order = list(per)
     chamfer, p2s = [per[f]["chamfer"] for f in order], [per[f]["p2s"] for f in order]
-    write_geometry_errors(os.path.join(rec_root, "geometry_errors.txt"), order, chamfer, p2s)
+    write_columns(os.path.join(rec_root, "geometry_errors.txt"), order, {"chamfer": chamfer, "p2s": p2s})
     if signed:
-        write_geometry_signed(os.path.join(rec_root, "geometry_signed.txt"), order, [per[f]["signed"]["pred_to_gt"]["mean"] for f in order],
-                              [per[f]["signed"]["gt_to_pred"]["mean"] for f in order])
+        write_columns(os.path.join(rec_root, "geometry_signed.txt"), order,
+                      {k: [per[f]["signed"][k]["mean"] for f in order] for k in ("pred_to_gt", "gt_to_pred")})
     result = {"frames": per, "skipped": skipped,
               "summary": {"chamfer_mean": float(np.mean(chamfer)), "chamfer_max": float(np.max(chamfer)), "p2s_mean": float(np.mean(p2s)),
                           "p2s_max": float(np.max(p2s)), "samples": int(samples), "seed": int(seed)}}
@@ -394,12 +379,10 @@ def main(argv=None, out=print):
     args = parse_args(argv)
     device = torch.device("cuda", args.gpu_ids[0])
     align, align_opts = _align_args(args)
-    extra = {"signed": True, "beta": args.beta} if args.signed else {}
     if args.pred:
-        pred, gt = _to_device(read_mesh(args.pred), device), _to_device(read_mesh(args.gt), device)
-        if args.error_mesh is not None and align is not None:
-            align = _alignment(pred, sd.MeshIndex.build(gt[0], gt[1]), align, align_opts)
-        m = surface_metrics(pred, gt, args.samples, args.seed, args.tau, align, align_opts, **extra)
+        pred, gt = _surface(read_mesh(args.pred), device), _surface(read_mesh(args.gt), device)
+        align = _alignment(pred, gt, align, align_opts)
+        m = surface_metrics(pred, gt, args.samples, args.seed, args.tau, align, signed=args.signed, beta=args.beta)
         out(json.dumps(m))
         if args.error_mesh is not None:
             write_error_mesh(args.error_mesh, pred, gt, align, args.signed, args.beta, args.error_range, out)

@@ -1,6 +1,7 @@
 """Operators of the winding-number inside / outside test (csrc/winding.hip): GPU tensors only, no autograd.
 `evaluate.py` is the public interface.  The stable sort of the leaf keys and the run starts are torch's; everything per face, per node
-and per point is a HIP kernel.  Two calls give identical bits.
+and per point is a HIP kernel.  Two calls give identical bits.  A WindingIndex is built from a surfdist_ops.Surface, which prepares
+the mesh once, shares its packed corners with the grid and keeps the pyramid of the default depth (Surface.pyramid).
 
 The entry points are declared in csrc/winding_abi.h and bound here (_lib.bind_header): a library without them fails this import."""
 import math
@@ -12,7 +13,7 @@ import torch
 from . import _lib
 from . import surfdist_ops as sd
 from .build import CSRC
-from .mesh_prep_ops import mesh_bounds
+from .mesh_prep_ops import _lists
 
 _DEFINES, _ = _lib.bind_header(os.path.join(CSRC, "winding_abi.h"))
 MAX_LEVELS = _DEFINES["SR_WINDING_MAX_LEVELS"]
@@ -52,48 +53,42 @@ def signed_volume(verts, faces):
 
 
 class WindingIndex:
-    """The octree pyramid of a mesh (layout: csrc/winding_abi.h): `corner` [3] (device), `cell` (the leaf's side), `levels`, `nodes`
+    """The octree pyramid of a Surface (layout: csrc/winding_abi.h): `corner` [3] (device), `cell` (the leaf's side), `levels`, `nodes`
     [(8^(levels+1) - 1) / 7, NODE_FLOATS] float32, `leaf_start` [8^levels + 1] int64, `leaf_faces` [F] int32 (every leaf's faces in
-    ascending index); the mesh: `verts`, `faces` (cleaned), `tri` [F,12]; `volume`, its signed volume as a Python float, and `flipped`
-    = volume < 0: the faces wind inward, and winding_number returns -w so that inside stays w >= 1/2."""
+    ascending index); shared with the Surface: `verts`, `faces`, `tri`; `volume`, the mesh's signed volume as a Python float, and
+    `flipped` = volume < 0: the faces wind inward, and winding_number returns -w so that inside stays w >= 1/2."""
 
-    def __init__(self, verts, faces, tri, corner, cell, levels, nodes, leaf_start, leaf_faces, volume):
-        self.verts, self.faces, self.tri, self.corner, self.cell, self.levels = verts, faces, tri, corner, cell, levels
-        self.nodes, self.leaf_start, self.leaf_faces = nodes, leaf_start, leaf_faces
-        self.volume, self.flipped = volume, volume < 0
+    def __init__(self, surface, levels=None, leaf_factor=None):
+        """`levels` in [0, MAX_LEVELS] defaults to default_levels of the cube's side, the total area and F, with `leaf_factor`
+        (default LEAF_FACTOR).  One device -> host read: the signed volume."""
+        verts, faces, tri = self.verts, self.faces, self.tri = surface.verts, surface.faces, surface.tri
+        corner_h, side = cube(surface.box[:3], surface.box[3:])
+        F, dev = tri.shape[0], tri.device
+        if levels is None:
+            leaf_factor = LEAF_FACTOR if leaf_factor is None else leaf_factor
+            if not (leaf_factor > 0 and math.isfinite(leaf_factor)):
+                raise ValueError(f"leaf_factor must be a positive float, got {leaf_factor}")
+            levels = default_levels(side, surface.area, F, leaf_factor)
+        self.levels = levels = int(levels)
+        if not 0 <= levels <= MAX_LEVELS:
+            raise ValueError(f"levels in [0, {MAX_LEVELS}] expected, got {levels}")
+        self.cell = float(side / np.float32(1 << levels))
+        self.corner = torch.from_numpy(corner_h).to(dev)
+        key = torch.empty((F,), dtype=torch.int64, device=dev)
+        _lib.launch("sr_winding_keys", tri, tri, F, 1, self.corner, self.cell, levels, key)
+        order, self.leaf_start = _lists(key, 1 << (3 * levels))
+        self.leaf_faces = order.to(torch.int32).contiguous()
+        self.nodes = torch.empty((level_offset(levels + 1), NODE_FLOATS), dtype=torch.float32, device=dev)
+        _lib.launch("sr_winding_leaves", tri, tri, F, self.leaf_start, self.leaf_faces, levels, self.nodes)
+        for level in range(levels - 1, -1, -1):
+            _lib.launch("sr_winding_fold", self.nodes, self.nodes, level, levels)
+        self.volume = float(signed_volume(verts, faces))
+        self.flipped = self.volume < 0
 
     @classmethod
     def build(cls, verts, faces, levels=None, leaf_factor=LEAF_FACTOR):
-        """The pyramid of verts [V,3] / faces [F,3] (GPU tensors), refused as MeshIndex.build refuses: rows with a negative index are
-        dropped; ValueError for an index >= V, no faces left, or a non-finite vertex.  `levels` in [0, MAX_LEVELS] defaults to
-        default_levels of the cube's side, the total area and F.  Device -> host reads: the box, the area (for the default) and the
-        signed volume."""
-        verts, faces = sd._mesh(verts, faces, "WindingIndex.build")
-        lo, hi = mesh_bounds(verts)
-        corner_h, side = cube(lo.cpu().numpy(), hi.cpu().numpy())
-        F, dev = faces.shape[0], verts.device
-        if levels is None:
-            if not (leaf_factor > 0 and math.isfinite(leaf_factor)):
-                raise ValueError(f"leaf_factor must be a positive float, got {leaf_factor}")
-            levels = default_levels(side, float(sd.face_areas_cum(verts, faces)[-1]), F, leaf_factor)
-        levels = int(levels)
-        if not 0 <= levels <= MAX_LEVELS:
-            raise ValueError(f"levels in [0, {MAX_LEVELS}] expected, got {levels}")
-        cell = float(side / np.float32(1 << levels))
-        tri = sd._pack(verts, faces)
-        corner = torch.from_numpy(corner_h).to(dev)
-        key = torch.empty((F,), dtype=torch.int64, device=dev)
-        _lib.launch("sr_winding_keys", tri, tri, F, 1, corner, cell, levels, key)
-        key, perm = torch.sort(key, stable=True)
-        leaves = 1 << (3 * levels)
-        leaf_start = torch.zeros((leaves + 1,), dtype=torch.int64, device=dev)
-        leaf_start[1:] = torch.cumsum(torch.bincount(key, minlength=leaves), 0)
-        leaf_faces = perm.to(torch.int32).contiguous()
-        nodes = torch.empty((level_offset(levels + 1), NODE_FLOATS), dtype=torch.float32, device=dev)
-        _lib.launch("sr_winding_leaves", tri, tri, F, leaf_start, leaf_faces, levels, nodes)
-        for level in range(levels - 1, -1, -1):
-            _lib.launch("sr_winding_fold", nodes, nodes, level, levels)
-        return cls(verts, faces, tri, corner, cell, levels, nodes, leaf_start, leaf_faces, float(signed_volume(verts, faces)))
+        """The pyramid of verts [V,3] / faces [F,3] (GPU tensors), refused as surfdist_ops.Surface refuses."""
+        return cls(sd.Surface(verts, faces, "WindingIndex.build"), levels, leaf_factor)
 
 
 def winding_number(points, index, method="tree", beta=BETA, presort=True):
@@ -117,16 +112,12 @@ def winding_number(points, index, method="tree", beta=BETA, presort=True):
     if method == "brute":
         _lib.launch("sr_winding_brute", points, points, P, index.tri, F, w)
         return -w if index.flipped else w
-    order = None
     if presort:
         key = torch.empty((P,), dtype=torch.int64, device=dev)
         _lib.launch("sr_winding_keys", points, points, P, 0, index.corner, index.cell, index.levels, key)
-        order = torch.sort(key, stable=True)[1]
-        points = points[order].contiguous()
+        points, back = sd.in_key_order(points, key)
     _lib.launch("sr_winding_query", points, points, P, index.tri, F, index.nodes, index.levels, index.leaf_start, index.leaf_faces,
                 beta, int(math.isinf(beta)), w)
-    if order is not None:
-        inv = torch.empty_like(order)
-        inv[order] = torch.arange(P, dtype=torch.int64, device=dev)
-        w = w[inv]
+    if presort:
+        w = back(w)[0]
     return -w if index.flipped else w
