@@ -12,9 +12,18 @@ def pose_template(net, verts, frame_ids, ratio=None):
     `ratio` is given -> (def_verts [N,V,3] detached, defconds = [d_cond, [poses, trans]], rendcond), all of one fetch of the frames' parameters."""
     with torch.no_grad():
         poses, trans, d_cond, rendcond = [t.detach() for t in net.dataset.get_grad_parameters(frame_ids, frame_ids.device)]
-        defconds = [d_cond, [poses, trans]]
-        def_verts = net.deformer(verts[None, :, :].expand(frame_ids.numel(), -1, 3), defconds, ratio=ratio or FULL_RATIO).detach().contiguous()
+    def_verts, defconds = pose_with(net, verts, poses, trans, d_cond, ratio)
     return def_verts, defconds, rendcond
+
+
+def pose_with(net, verts, poses, trans, d_cond, ratio=None):
+    """pose_template with the frames' parameters supplied: `verts` [V,3] posed by the trained deformer for poses [N,24,3] (or what the
+    dataset's table holds per frame), trans [N,3] and the non-rigid deformer's codes d_cond [N,condlen] -- captured frames' rows or
+    anything else (animate.py) -> (def_verts [N,V,3] detached, defconds = [d_cond, [poses, trans]])."""
+    with torch.no_grad():
+        defconds = [d_cond.detach(), [poses.detach(), trans.detach()]]
+        def_verts = net.deformer(verts[None, :, :].expand(poses.shape[0], -1, 3), defconds, ratio=ratio or FULL_RATIO).detach().contiguous()
+    return def_verts, defconds
 
 
 def rasterize_posed(def_verts, faces, cameras, H, W, pixels=False):
