@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE -- freezes what the reference-pin tests take from the host builds of the reference's own kernels (oracle/_ref,
 see oracle/Makefile) into tests/golden/ref_pins.npz, so that the pins hold where neither the reference tree nor oracle/_ref exists:
   mc*    marching cubes (tests/test_mc_reference_pin.py): digests of the canonical (vertices, edge keys, faces) of both builds per case,
-         the largest vertex difference between them, the iso-value cases, and the vertices / sorted faces of the GPU cases;
+         the largest vertex difference between them, the iso-value cases, the vertices / sorted faces of the GPU cases, and the
+         all-cases block volume of tests/_mc_volumes.py (tests/test_mc_paths_cpu.py);
   minv*  3x3 inverse (tests/test_minv_reference_pin.py): digests of inverse / flag / backward of the uncontracted build, its backward
          as an array (compared with a tolerance), and the agreement statistics of the contracted build;
   gs*    grid sampler (tests/test_gs_reference_pin.py): the relative difference of the contracted build's outputs from the uncontracted
@@ -18,6 +19,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import mc as mco, minv_ref, gs_ref  # noqa: E402
 from oracle.fixtures import digest  # noqa: E402
 import test_mc_reference_pin as tmc  # noqa: E402
+import _mc_volumes as mv  # noqa: E402
 import test_minv_reference_pin as tmi  # noqa: E402
 import test_gs_reference_pin as tgs  # noqa: E402
 
@@ -35,6 +37,8 @@ for i, iso in enumerate(tmc.ISOS):
 for n, (shape, kind) in enumerate(tmc.GPU_CASES):
     vf, kf, ff = mco.canonical(*mco.reference_marching_cubes(tmc.field(shape, kind), tmc.STEP, tmc.ORG, 0.0, "fma"))
     out[f"mcgpu{n}_v"], out[f"mcgpu{n}_f"] = digest(vf), digest(ff)
+for name, x in zip("vkf", mco.canonical(*mco.reference_marching_cubes(mv.volume(mv.ALL_CASES), mv.STEP, mv.ORG, 0.0, "fma"))):
+    out[f"mc_all_cases_{name}"] = digest(x)              # tests/test_mc_paths_cpu.py: each of the 256 cases in a block of its own
 for dtype, tag in ((np.float32, "f32"), (np.float64, "f64")):
     m = tmi._matrices(5000, dtype)
     inv_r, ok_r = minv_ref.forward(m, "nofma")

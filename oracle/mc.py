@@ -14,21 +14,31 @@ def build():
     return SO
 
 
-def marching_cubes(sdf, step=(1., 1., 1.), origin=(0., 0., 0.), iso=0.0):
+def capacity(size, full=False):
+    """(vertex, face) capacity of marching_cubes' buffers for a volume of `size` voxels.  The default -- half a vertex and one face per
+    voxel -- holds the thin shells of a signed-distance volume.  full=True cannot overflow on any field: a cell owns 3 lattice edges and
+    emits at most 5 triangles."""
+    if full:
+        return max(1024, 3 * size), max(2048, 5 * size)
+    cap = max(1024, int(size * 0.5))
+    return cap, cap * 2
+
+
+def marching_cubes(sdf, step=(1., 1., 1.), origin=(0., 0., 0.), iso=0.0, full=False):
     """sdf: float32 [NX,NY,NZ] (C order).  Returns verts [V,3] f32, keys [V] i64, faces [F,3] i64
-    in the oracle's sequential (cell-major) order."""
+    in the oracle's sequential (cell-major) order.  full=True sizes the buffers for a field as dense as white noise (see capacity)."""
     lib = ctypes.CDLL(build())
     sdf = np.ascontiguousarray(sdf, dtype=np.float32)
     NX, NY, NZ = sdf.shape
-    cap = max(1024, int(sdf.size * 0.5))
-    verts = np.zeros((cap, 3), np.float32); keys = np.zeros(cap, np.int64); faces = np.zeros((cap * 2, 3), np.int64)
+    cap, cap_f = capacity(sdf.size, full)
+    verts = np.zeros((cap, 3), np.float32); keys = np.zeros(cap, np.int64); faces = np.zeros((cap_f, 3), np.int64)
     nv, nf = ctypes.c_int64(0), ctypes.c_int64(0)
     f32 = ctypes.c_float
     lib.mc_oracle.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, f32, f32, f32, f32, f32, f32, f32,
                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
                               ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
     rc = lib.mc_oracle(sdf.ctypes.data, NX, NY, NZ, iso, step[0], step[1], step[2], origin[0], origin[1], origin[2],
-                       verts.ctypes.data, keys.ctypes.data, cap, faces.ctypes.data, cap * 2, ctypes.byref(nv), ctypes.byref(nf))
+                       verts.ctypes.data, keys.ctypes.data, cap, faces.ctypes.data, cap_f, ctypes.byref(nv), ctypes.byref(nf))
     assert rc == 0, rc
     return verts[:nv.value].copy(), keys[:nv.value].copy(), faces[:nf.value].copy()
 
@@ -59,7 +69,8 @@ def reference_marching_cubes(sdf, step=(1., 1., 1.), origin=(0., 0., 0.), iso=0.
     cv, cf = ctypes.c_int64(0), ctypes.c_int64(0)
     lib.mc_ref_capacity(NX, NY, NZ, ctypes.byref(cv), ctypes.byref(cf))
     # the reference never checks its 5 %-of-cells scratch (CudaKernels.cu:590-592): make sure this volume fits BEFORE running it
-    vo, _, fo = marching_cubes(sdf, step, origin, iso)
+    # (with buffers that cannot overflow where they are affordable, so that a dense small volume is refused below, not by an assert)
+    vo, _, fo = marching_cubes(sdf, step, origin, iso, full=sdf.size <= 1 << 22)
     if len(vo) > cv.value or len(fo) > cf.value:
         raise ValueError(f"volume needs {len(vo)} vertices / {len(fo)} faces, the reference's scratch holds {cv.value} / {cf.value}")
     verts = np.zeros((cv.value, 3), np.float32); keys = np.zeros(cv.value, np.int64); faces = np.zeros((cf.value, 3), np.int64)
@@ -78,6 +89,7 @@ def canonical(verts, keys, faces):
     """Order vertices by lattice-edge key, rewrite faces to the new ids, sort face rows."""
     order = np.argsort(keys, kind="stable")
     rank = np.empty_like(order); rank[order] = np.arange(order.size)
-    f = np.where(faces >= 0, rank[np.clip(faces, 0, None)], -1)
+    # (no vertex at all: every face corner is -1 already -- a cell against the far faces of the volume can emit such a face)
+    f = np.where(faces >= 0, rank[np.clip(faces, 0, None)], -1) if order.size else faces.copy()
     f = f[np.lexsort((f[:, 2], f[:, 1], f[:, 0]))]
     return verts[order], keys[order], f

@@ -272,20 +272,17 @@ __global__ __launch_bounds__(256) void mc_vertex_kernel(const float* __restrict_
     const int j = (int)(row - (int64_t)i * d.NY);
     const float v0 = sdf[c];
     const float vn = sdf[c + (dir == 0 ? strideX : dir == 1 ? strideY : 1)];
-    // Lattice coordinate of the crossing as CudaKernels.cu:363-365 writes it, fX + (offset + t * dir): the products are exact
-    // (dir is 0 or +-1), so they are folded here.  The scaling v*step+min of d_scale_vertices (:517-519) is ONE fused
-    // multiply-add, as nvcc's default -fmad=true compiles it: bit-equal to the reference's kernels built that way
-    // (oracle/_ref/libmc_ref_fma.so, tests/test_mc_reference_pin.py).
-    float x = (float)i, y = (float)j, z = (float)k;
-    if (dir == 0) {          // cube edge 0: v0 -> v1, direction +x
-      x = x + (0.0f + edge_offset(v0, vn, iso));
-    } else if (dir == 1) {   // cube edge 3: v3 -> v0, direction -y, starting at (0,1,0)
-      y = y + (1.0f + -edge_offset(vn, v0, iso));
-    } else {                 // cube edge 8: v0 -> v4, direction +z
-      z = z + (0.0f + edge_offset(v0, vn, iso));
-    }
-    x = __builtin_fmaf(x, sx, ox); y = __builtin_fmaf(y, sy, oy); z = __builtin_fmaf(z, sz, oz);
-    verts[vid * 3 + 0] = x; verts[vid * 3 + 1] = y; verts[vid * 3 + 2] = z;
+    // Lattice coordinate of the crossing as CudaKernels.cu:363-365 writes it, fX + (offset + t * dir) on ALL three axes: the products
+    // are exact (dir is 0 or +-1) while t is finite, but a NaN t (a NaN sample, inf - inf) makes 0 * t NaN as well, and the reference
+    // then returns the vertex with three NaN coordinates, not one -- so the products with 0 stay.  The scaling v*step+min of
+    // d_scale_vertices (:517-519) is ONE fused multiply-add, as nvcc's default -fmad=true compiles it: bit-equal to the reference's
+    // kernels built that way (oracle/_ref/libmc_ref_fma.so, tests/test_mc_reference_pin.py).
+    // cube edge 0: v0 -> v1, direction +x;  cube edge 3: v3 -> v0, direction -y, starting at (0,1,0);  cube edge 8: v0 -> v4, direction +z
+    const float t = dir == 1 ? edge_offset(vn, v0, iso) : edge_offset(v0, vn, iso);
+    const float x = (float)i + (0.0f + t * (dir == 0 ? 1.0f : 0.0f));
+    const float y = (float)j + ((dir == 1 ? 1.0f : 0.0f) + t * (dir == 1 ? -1.0f : 0.0f));
+    const float z = (float)k + (0.0f + t * (dir == 2 ? 1.0f : 0.0f));
+    verts[vid * 3 + 0] = __builtin_fmaf(x, sx, ox); verts[vid * 3 + 1] = __builtin_fmaf(y, sy, oy); verts[vid * 3 + 2] = __builtin_fmaf(z, sz, oz);
   }
 }
 
@@ -375,7 +372,7 @@ int sr_mc_count(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float iso,
 // Pass 2: emit into exactly-sized outputs (verts [V,3] f32 already scaled v*step+min, faces [F,3] i64).
 int sr_mc_emit(const float* sdf, int32_t nx, int32_t ny, int32_t nz, float iso, const void* workspace, float xstep, float ystep,
                float zstep, float xmin, float ymin, float zmin, float* verts, int64_t* faces, void* stream) {
-  if (nx <= 0 || ny <= 0 || nz <= 0 || !sdf || !workspace || !verts || !faces) return SR_EINVAL;
+  if (nx <= 0 || ny <= 0 || nz <= 0 || !sdf || !workspace || ((uintptr_t)workspace & 7) || !verts || !faces) return SR_EINVAL;
   const McLayout L = mc_layout(nx, ny, nz);
   const uint64_t* planes = (const uint64_t*)workspace;
   const uint32_t* voff64 = (const uint32_t*)(planes + L.G * MC_PLANES);

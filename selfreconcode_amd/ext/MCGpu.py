@@ -36,6 +36,8 @@ def mc_gpu(sdfs, xstep=1.0, ystep=1.0, zstep=1.0, xmin=0.0, ymin=0.0, zmin=0.0, 
     verts = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     faces = torch.empty((nf, 3), dtype=torch.int64, device=dev)
     if nv or nf:
+        # a cell next to the far faces of the volume can emit a face whose three edges no cell owns -- F = 1, V = 0 -- and an empty tensor
+        # has no address to pass: sr_mc_emit gets one row it will not touch
         _lib.launch("sr_mc_emit", sdfs, sdfs, nx, ny, nz, float(fTargetValue), ws, float(xstep), float(ystep), float(zstep), float(xmin), float(ymin),
-                    float(zmin), verts, faces)
+                    float(zmin), verts if nv else verts.new_empty((1, 3)), faces if nf else faces.new_empty((1, 3)))
     return [verts, faces]
